@@ -7,7 +7,7 @@ bytes back on the host (the boundary of p2gpu_prove_dev).  N > 1: one process pe
 (torch.distributed / RCCL), every rank proves its own independent proofs (replicas, weak
 scaling, no data-path collective); time = max over ranks between two barriers.
 
-BASELINE.json's metric has two halves and the line carries both: `value` = proofs/sec, the throughput of
+BASELINE.json's metric has two halves and a --full line carries both: `value` = proofs/sec, the throughput of
 a proving service that keeps --in-flight proofs (default 4; separate circuit handles / HIP streams, one
 host thread each) in flight per GPU, K steps = K proofs, ms_per_step = wall time / K; and
 `latency_ms_single_proof` = the prove latency, measured in its own pass with exactly one proof on the GPU
@@ -15,8 +15,10 @@ at a time (`single_proof` also gives that pass's proofs/sec -- the round-1 headl
 the GPU idle at its eleven Fiat-Shamir sync points and under-filled in the top levels of every Merkle tree
 (one dependent Keccak-f per level); other proofs' kernels fill those holes.
 
-The timed region runs the production path only: no per-launch events, no oracle.  After it, in
-the same process, separate passes collect what the JSON line reports beside `value`:
+The timed region runs the production path only: no per-launch events, no oracle.  It is exactly --steps proofs (one pass;
+--min-timed-s repeats it and takes the median).  A plain run ends there: --dump-outputs DIR writes the proof of the last
+step (DIR/proof.npy), and the JSON line carries the timed region's fields.  With --full, separate passes in the same process
+then collect what the line reports beside `value`:
   * `single_proof`: one proof at a time (latency);
   * `host_witness`: the same proofs through p2gpu_prove (witness in host RAM, the 245 MB H2D inside
     the call) -- SURVEY.md 8(d)'s boundary-to-boundary number, never `value`;
@@ -26,11 +28,11 @@ the same process, separate passes collect what the JSON line reports beside `val
   * `cpu_baseline` (N = 1): the oracle = CPU port, on THIS workload, all host cores, unscaled;
   * `cold_process` (N = 1): a fresh process that reads the circuit and the witness, creates the handle and proves ONCE
     (the plain-C `p2gpu-prove --timing`) -- what one invocation of the reference's CLI would see (prove_action.rs:27-43).
-Prints ONE JSON line (< 6 KB: compact_line) on rank 0; the full result goes to bench_detail.json beside it (--detail).
+Prints ONE JSON line (< 6 KB: compact_line) on rank 0; with --full the full result goes to bench_detail.json beside it (--detail).
 
 `--gpus N` with N > 1 is self-contained: started WITHOUT torchrun the command itself launches N ranks (one process per
 device, RCCL) and exits non-zero if the box has fewer than N devices; started BY torchrun (WORLD_SIZE set) it is one of
-the ranks and insists that WORLD_SIZE == N.  One run measures both halves of BASELINE.json's metric: `value` = replicas
+the ranks and insists that WORLD_SIZE == N.  One --full run measures both halves of BASELINE.json's metric: `value` = replicas
 (proofs/s over all N devices), and ONE proof sharded over the N devices -- `latency_ms_sharded` through RCCL called by
 the library from the N ranks, `latency_ms_sharded_group` through a device group of ONE process (peer copies), with the
 per-exchange microseconds (HIP events) and the peer-access matrix of the group.
@@ -163,9 +165,9 @@ def main():
                     help="degree bits of the one-thread oracle leg: -1 (default) = the benchmarked circuit itself up to 2^17 gates "
                          "(~27 s at 2^20 LDE rows, unscaled), 0 = skip the one-thread leg")
     ap.add_argument("--profile-steps", type=int, default=4)
-    ap.add_argument("--min-timed-s", type=float, default=None,
-                    help="repeat the K-proof timed region until at least this much proving has been timed (default 1.5 s; 0 with "
-                         "--timed-only): ms_per_step is the MEDIAN over the repeats, min / max / repeats are in the line")
+    ap.add_argument("--min-timed-s", type=float, default=0.0,
+                    help="repeat the K-proof timed region until at least this much proving has been timed (default 0: exactly K timed "
+                         "proofs): ms_per_step is the MEDIAN over the repeats, min / max / repeats are in the line")
     ap.add_argument("--sharded-steps", type=int, default=6,
                     help="N > 1: proofs of the sharded-latency half (ONE proof over the N devices; 0 = skip that half)")
     ap.add_argument("--no-group-probe", action="store_true",
@@ -176,15 +178,22 @@ def main():
                     help="rank plumbing only, no GPU work: rendezvous + barrier + max-over-ranks, one JSON line naming the ranks "
                          "(the CPU-side test of `--gpus N`)")
     ap.add_argument("--detail", default="",
-                    help="where the full result goes (default bench_detail.json beside bench.py); stdout is ONE line under 6 KB")
+                    help="where the full result of a --full run goes (default bench_detail.json beside bench.py); stdout is ONE line under 6 KB")
     ap.add_argument("--timed-only", action="store_true",
                     help="warm-up + timed region only (no host-witness / pipelined / event-profile / CPU passes): the command "
                          "rocprofv3 wraps (scratch/prof.sh), so that its per-kernel averages are those of the timed path")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the separate passes (lone latency, host witness, pipelined, kernel profile + "
+                         "roofline, the sharded half, cold_process, cpu_baseline) and write the detail file; without it a run is "
+                         "warm-up + timed region + the result line only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path returned in its last step to DIR/proof.npy: the proof bytes (public inputs "
+                         "included), one float32 per byte")
     args = ap.parse_args()
-    if args.min_timed_s is None:
-        args.min_timed_s = 0.0 if args.timed_only else 1.5
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     # --gpus N > 1 outside torchrun: this process launches the N ranks itself
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.group:
         sys.exit(launch_ranks(args, sys.argv[1:]))
@@ -296,7 +305,7 @@ def main():
     import threading
 
     def run(handles, n_proofs, collect=None, w=None):
-        """n_proofs proofs over the handles (thread i proves every len(handles)-th proof)."""
+        """n_proofs proofs over the handles (thread i proves every len(handles)-th proof); returns the last one's result."""
         w = wires_dev if w is None else w
         k = len(handles)
 
@@ -319,7 +328,7 @@ def main():
                 t.start()
             for t in th:
                 t.join()
-        return next(r for r in results if r is not None)
+        return results[(n_proofs - 1) % k]
 
     # ---- warm-up, then the timed region: K proofs, nothing but the production path ----
     tw0 = time.perf_counter()
@@ -354,19 +363,77 @@ def main():
             if k.endswith("_ms"):
                 phase[k] = phase.get(k, 0.0) + v / len(rep_s)
 
-    if args.timed_only:
-        if rank == 0:
-            print(json.dumps({"metric": f"proofs/sec at 2^{d + 3} LDE rows, {S} proof(s) in flight per GPU", "value": (args.steps if sharded else world * args.steps) / dt,
-                              "unit": "proofs/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-                              "proofs_in_process": args.steps * len(rep_s) + max(args.warmup, S) + extra_warm, "clock_warmup_proofs": extra_warm, "repeats": len(rep_s), "timed_only": True}), flush=True)
+    def finish():
         for c_ in cds:
             c_.close()
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
+
+    # what a caller of the timed path received in its last step (every input is seeded: two builds compare output for output)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "proof.npy"), np.frombuffer(proof.to_bytes(), dtype=np.uint8).astype(np.float32))
+
+    if args.timed_only:
+        if rank == 0:
+            print(json.dumps({"metric": f"proofs/sec at 2^{d + 3} LDE rows, {S} proof(s) in flight per GPU", "value": (args.steps if sharded else world * args.steps) / dt,
+                              "unit": "proofs/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+                              "proofs_in_process": args.steps * len(rep_s) + max(args.warmup, S) + extra_warm, "clock_warmup_proofs": extra_warm, "repeats": len(rep_s), "timed_only": True}), flush=True)
+        finish()
         return
 
-    # ---- separate passes (not part of `value`) ----
+    # ---- the result line's headline: what the timed region measured ----
+    total_proofs = args.steps if sharded else world * args.steps
+    hdr = blob[:256].view(np.uint32)
+    W, CS = int(hdr[3]), int(hdr[5]) + int(hdr[4])
+    ms_step = dt / args.steps * 1e3
+    out = {
+        "metric": (f"prove latency (ms) + proofs/sec at 2^{d + 3} LDE rows, {world} GPU(s): value = proofs/sec, witness resident in HBM, {S} proof(s) in "
+                   f"flight per GPU; latency_ms_single_proof = lone resident proof; *_host_witness = p2gpu_prove from host RAM (PCIe inside the call)"
+                   + ("; latency_ms_sharded[_group] = ONE proof over the N GPUs (RCCL ranks / one-process device group)" if world > 1 else "")),
+        "value": total_proofs / dt,
+        "unit": "proofs/sec",
+        "n_gpus": world,
+        "ranks_share_devices": bool(world > 1 and args.backend != "nccl"),   # gloo test mode: functional run, not a scaling point
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "clock_warmup_proofs": extra_warm,   # untimed proofs beyond W (--clock-warmup-ms): steady-state clocks in the timed region
+        "ms_per_step": ms_step,
+        "ms_per_step_min": min(rep_s) / args.steps * 1e3,
+        "ms_per_step_max": max(rep_s) / args.steps * 1e3,
+        "repeats": len(rep_s),
+        "timed_seconds": sum(rep_s),
+        "higher_is_better": True,
+        "scaling": "strong" if sharded else "weak",
+        "vs_baseline": None,
+        "dtype": "u64",
+        "data": "synthetic",
+        "config": {
+            "workload": (f"synth(d={d},{mix})" if args.workload == "synth" else f"SHA-256 of a {args.sha_blocks}-block message: {args.sha_blocks} "
+                         f"chained Sha256Compression opcodes through the restated reference translator (translate.py)") +
+                        f": {1 << d} gates -> 2^{d + 3} LDE rows, {W} wires / 80 routed, "
+                        f"{'Poseidon' if args.hasher == 'poseidon' else 'Keccak'}GoldilocksConfig, rate 8, cap 2^4, 28 queries, 16 PoW bits (BASELINE configs[2] shape)",
+            "degree_bits": d, "lde_rows": 1 << (d + 3), "mix": mix, "public_inputs": args.public_inputs,
+            "parallelism": (f"ONE process, device group {group}: each proof coset-sharded over {len(group)} ranks (8/{len(group)} LDE cosets each), "
+                            f"peer-to-peer exchanges between the ranks' streams" if group else
+                            f"one proof coset-sharded over {world} GPUs (8/{world} LDE cosets each; RCCL all-gather of caps, "
+                            f"quotient interpolants, query openings)" if sharded else
+                            f"replicas x{world} (independent proofs per GPU, no data-path collective), "
+                            f"{S} proof(s) in flight per GPU"),
+            "proof_bytes": len(proof),
+            "witness": "resident in HBM when the timed region starts (p2gpu_prove_dev); proof bytes returned to host",
+        },
+        "in_flight_per_gpu": S,
+        "device": pkg.device_info()["name"],
+    }
+    if not args.full:
+        if rank == 0:
+            print(compact_line(out, None), flush=True)
+        finish()
+        return
+
+    # ---- separate passes (--full; not part of `value`) ----
     cd = cds[0]
     # (0) prove latency: exactly one proof on the GPU at a time (same handle, same resident witness)
     if S == 1:
@@ -630,11 +697,7 @@ def main():
             cold = {"error": str(e)[:300]}
 
     if rank == 0:
-        total_proofs = args.steps if sharded else world * args.steps
-        hdr = blob[:256].view(np.uint32)
-        W, CS = int(hdr[3]), int(hdr[5]) + int(hdr[4])
         steps_b, total_b = survey_bytes(d, W, CS)
-        ms_step = dt / args.steps * 1e3
         # The roofline is that of ONE kernel, and every figure in it divides by that kernel's LONE launch time (one proof on the GPU
         # at a time: per-launch HIP events on the library's launch stream, what `rocprofv3 --kernel-trace --stats` of scratch/prof.sh
         # agrees with).  With S proofs in flight an event pair measures a span the kernel shares with the other proofs' kernels;
@@ -673,42 +736,7 @@ def main():
                               "valu_lane_instr_per_s": iss_["achieved"] if iss_ else None,
                               "valu_frac_of_peak": iss_["frac"] if iss_ else None,
                               "valu_frac_of_mix_ceiling": iss_["frac_of_mix_ceiling"] if iss_ else None}
-        out = {
-            "metric": (f"prove latency (ms) + proofs/sec at 2^{d + 3} LDE rows, {world} GPU(s): value = proofs/sec, witness resident in HBM, {S} proof(s) in "
-                       f"flight per GPU; latency_ms_single_proof = lone resident proof; *_host_witness = p2gpu_prove from host RAM (PCIe inside the call)"
-                       + ("; latency_ms_sharded[_group] = ONE proof over the N GPUs (RCCL ranks / one-process device group)" if world > 1 else "")),
-            "value": total_proofs / dt,
-            "unit": "proofs/sec",
-            "n_gpus": world,
-            "ranks_share_devices": bool(world > 1 and args.backend != "nccl"),   # gloo test mode: functional run, not a scaling point
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "clock_warmup_proofs": extra_warm,   # untimed proofs beyond W (--clock-warmup-ms): steady-state clocks in the timed region
-            "ms_per_step": ms_step,
-            "ms_per_step_min": min(rep_s) / args.steps * 1e3,
-            "ms_per_step_max": max(rep_s) / args.steps * 1e3,
-            "repeats": len(rep_s),
-            "timed_seconds": sum(rep_s),
-            "higher_is_better": True,
-            "scaling": "strong" if sharded else "weak",
-            "vs_baseline": None,
-            "dtype": "u64",
-            "data": "synthetic",
-            "config": {
-                "workload": (f"synth(d={d},{mix})" if args.workload == "synth" else f"SHA-256 of a {args.sha_blocks}-block message: {args.sha_blocks} "
-                             f"chained Sha256Compression opcodes through the restated reference translator (translate.py)") +
-                            f": {1 << d} gates -> 2^{d + 3} LDE rows, {W} wires / 80 routed, "
-                            f"{'Poseidon' if args.hasher == 'poseidon' else 'Keccak'}GoldilocksConfig, rate 8, cap 2^4, 28 queries, 16 PoW bits (BASELINE configs[2] shape)",
-                "degree_bits": d, "lde_rows": 1 << (d + 3), "mix": mix, "public_inputs": args.public_inputs,
-                "parallelism": (f"ONE process, device group {group}: each proof coset-sharded over {len(group)} ranks (8/{len(group)} LDE cosets each), "
-                                f"peer-to-peer exchanges between the ranks' streams" if group else
-                                f"one proof coset-sharded over {world} GPUs (8/{world} LDE cosets each; RCCL all-gather of caps, "
-                                f"quotient interpolants, query openings)" if sharded else
-                                f"replicas x{world} (independent proofs per GPU, no data-path collective), "
-                                f"{S} proof(s) in flight per GPU"),
-                "proof_bytes": len(proof),
-                "witness": "resident in HBM when the timed region starts (p2gpu_prove_dev); proof bytes returned to host",
-            },
+        out.update({
             "roofline": {
                 "kernel": name,
                 # The contract's form: ALGORITHMIC bytes per launch / the kernel's average LONE launch duration / 8 TB/s.  The kernel
@@ -767,7 +795,6 @@ def main():
             "value_host_witness": host["proofs_per_sec_in_flight"] or host["proofs_per_sec"] if host else None,
             "single_proof": {"in_flight": 1, "ms_per_proof": single_ms, "proofs_per_sec": (1 if sharded else world) * 1e3 / single_ms,
                              "note": "one proof on the GPU at a time (the round-1 headline configuration)"},
-            "in_flight_per_gpu": S,
             "resident_bytes_per_handle": handle_bytes,
             "blocking_sync": bool(blocking),
             "host_witness": host,
@@ -784,8 +811,7 @@ def main():
                                       f"spans are not durations and nothing is divided by them"},
             "kernel_profile": f"{P} extra proofs one at a time (..._lone, roofline) and {P_inflight} with {S} in flight (kernel_span_ms_per_proof) "
                               f"after the timed region, per-launch HIP events on the library's launch streams (profile = 2: every scoped launch)",
-            "device": pkg.device_info()["name"],
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(pkg, d, mix if args.workload == "synth" else "sha", args.public_inputs, args.cpu_single_thread_bits)
         # stdout carries ONE short line (the driver keeps 8 KB of stdout: round 4's 21 KB line came back unparsed); everything
@@ -802,11 +828,7 @@ def main():
         sys.stdout.flush()
         sys.stderr.flush()
         os._exit(0)
-    for c_ in cds:
-        c_.close()
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

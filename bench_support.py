@@ -221,7 +221,8 @@ LINE_LIMIT = 6000   # bytes of the stdout line (the driver's record keeps the la
 
 def compact_line(out, detail_name="bench_detail.json"):
     """The ONE stdout line: the contract's fields, the latency / host-boundary numbers, `roofline` for ONE kernel and
-    `cpu_baseline`, a few hundred bytes each.  `out` is the full result (what goes to the detail file)."""
+    `cpu_baseline`, a few hundred bytes each.  `out` is the full result (what goes to the detail file); a field the run did not
+    measure (a plain run: everything but the timed region) is left off the line."""
     r = out.get("roofline") or {}
     iss = r.get("valu_issue") or {}
     wp = r.get("whole_proof") or {}
@@ -233,12 +234,14 @@ def compact_line(out, detail_name="bench_detail.json"):
                       "mix": cfg.get("mix"), "public_inputs": cfg.get("public_inputs"), "in_flight_per_gpu": out.get("in_flight_per_gpu"),
                       "parallelism": str(cfg.get("parallelism"))[:200], "proof_bytes": cfg.get("proof_bytes")}
     for k in ("latency_ms_single_proof", "latency_ms_single_proof_host_witness", "value_host_witness", "cold_process_ms"):
-        line[k] = out.get(k)
+        if k in out:
+            line[k] = out[k]
     if (out.get("n_gpus") or 1) > 1 or out.get("peer_access") is not None:
         for k in ("latency_ms_sharded", "latency_ms_sharded_intt", "latency_ms_sharded_all_steps", "latency_ms_sharded_group", "latency_ms_sharded_group_intt",
                   "latency_ms_sharded_group_all_steps", "rccl_ranks", "peer_access",
                   "ranks_share_devices"):
-            line[k] = out.get(k)
+            if k in out:
+                line[k] = out[k]
         sh = out.get("sharded") or {}
         if sh.get("error"):
             line["sharded_error"] = str(sh["error"])[:200]
@@ -271,7 +274,8 @@ def compact_line(out, detail_name="bench_detail.json"):
                                     "sample": str(cb.get("sample"))[:330], "seconds": cb.get("seconds"),
                                     "single_thread": ({"seconds": st.get("seconds"), "cores": 1, "scaled": st.get("scaled")} if "seconds" in st else None)}
     line["device"] = out.get("device")
-    line["detail"] = detail_name
+    if detail_name:
+        line["detail"] = detail_name
     txt = json.dumps(_short(line), separators=(",", ":"))
     if len(txt) > LINE_LIMIT:   # cannot happen with the caps above; if it ever does, drop prose before numbers
         for k in ("timing", "traffic_source"):

@@ -4,7 +4,7 @@
 ARGS=""
 if [ "$1" == "--args" ]; then ARGS="$2"; shift 2; fi
 run() {
-  env $1 python bench.py --no-cpu-baseline --no-cold-process --pipelined 0 --detail /tmp/ab_detail.json $ARGS > /dev/null 2>&1
+  env $1 python bench.py --full --no-cpu-baseline --no-cold-process --pipelined 0 --detail /tmp/ab_detail.json $ARGS > /dev/null 2>&1
   python - "$1" <<'PY'
 import json, sys
 d = json.load(open("/tmp/ab_detail.json"))

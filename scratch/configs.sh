@@ -2,7 +2,7 @@
 # every configuration of DESIGN.md / profiles/NUMBERS.md on one box -> gpurun_out/<tag>_cfg/: the full results (bench.py --detail; copied to
 # profiles/<tag>_bench*.json) and the stdout lines (copied to profiles/<tag>_line*.json)          usage: bash scratch/configs.sh r05
 T=${1:-r05}; O=gpurun_out/${T}_cfg; mkdir -p $O
-b() { name=$1; shift; python bench.py --detail $O/bench$name.json "$@" 2> $O/bench$name.err | grep "^{" | tail -1 > $O/line$name.json; }
+b() { name=$1; shift; python bench.py --full --detail $O/bench$name.json "$@" 2> $O/bench$name.err | grep "^{" | tail -1 > $O/line$name.json; }
 b ""
 b _pi4 --public-inputs 4 --no-cpu-baseline --no-cold-process
 b _d17_ecdsa --mix ecdsa --no-cpu-baseline --no-cold-process

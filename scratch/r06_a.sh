@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 6, first measurement pass: host bulk upload (value_host_witness), 2^24 rows with several proofs in flight, the multi-rank flow
 T=r06; O=gpurun_out/${T}_a; mkdir -p $O
-b() { name=$1; shift; python bench.py --detail $O/bench$name.json "$@" 2> $O/bench$name.err | grep "^{" | tail -1 > $O/line$name.json; tail -3 $O/bench$name.err; }
+b() { name=$1; shift; python bench.py --full --detail $O/bench$name.json "$@" 2> $O/bench$name.err | grep "^{" | tail -1 > $O/line$name.json; tail -3 $O/bench$name.err; }
 b "" --no-cpu-baseline --no-cold-process
 P2GPU_HOST_BULK=0 b _nobulk --no-cpu-baseline --no-cold-process
 b _gloo2 --gpus 2 --backend gloo --steps 16 --warmup 4 --no-cpu-baseline

@@ -2,7 +2,7 @@
 # round 6: half-domain gate evaluation -- parity, then the heavy gate mixes
 T=r06; O=gpurun_out/${T}_c; mkdir -p $O
 python -m pytest tests -m gpu -x -q -k "proof_bytes_match or gate_vectors or baseline_size or half_domain or fuzz or measurement_switches" > $O/pytest.log 2>&1; tail -3 $O/pytest.log
-b() { name=$1; shift; python bench.py --detail $O/bench$name.json "$@" 2> $O/bench$name.err | grep "^{" | tail -1 > $O/line$name.json; tail -2 $O/bench$name.err; }
+b() { name=$1; shift; python bench.py --full --detail $O/bench$name.json "$@" 2> $O/bench$name.err | grep "^{" | tail -1 > $O/line$name.json; tail -2 $O/bench$name.err; }
 b _d17_ecdsa --mix ecdsa --no-cpu-baseline --no-cold-process
 b _d19_ecdsa --degree-bits 19 --mix ecdsa --no-cpu-baseline --no-cold-process --steps 8 --warmup 4 --pipelined 0
 python - <<'PY'

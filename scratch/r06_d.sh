@@ -1,6 +1,6 @@
 #!/bin/bash
 O=gpurun_out/r06_d; mkdir -p $O
-b() { name=$1; shift; python bench.py --detail $O/bench$name.json "$@" 2> $O/bench$name.err | grep "^{" | tail -1 > $O/line$name.json; tail -2 $O/bench$name.err; }
+b() { name=$1; shift; python bench.py --full --detail $O/bench$name.json "$@" 2> $O/bench$name.err | grep "^{" | tail -1 > $O/line$name.json; tail -2 $O/bench$name.err; }
 P2GPU_SUMS_GROUPS=1 b _g1 --mix ecdsa --no-cpu-baseline --no-cold-process
 b _g4 --mix ecdsa --no-cpu-baseline --no-cold-process
 python - <<'PY'

@@ -1,6 +1,6 @@
 #!/bin/bash
 O=gpurun_out/r06_e; mkdir -p $O
-b() { name=$1; shift; python bench.py --detail $O/bench$name.json "$@" 2> $O/bench$name.err | grep "^{" | tail -1 > $O/line$name.json; tail -1 $O/bench$name.err; }
+b() { name=$1; shift; python bench.py --full --detail $O/bench$name.json "$@" 2> $O/bench$name.err | grep "^{" | tail -1 > $O/line$name.json; tail -1 $O/bench$name.err; }
 for f in 4 6 8; do b _if$f --in-flight $f --no-cpu-baseline --no-cold-process; done
 python - <<'PY'
 import json

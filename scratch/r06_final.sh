@@ -2,7 +2,7 @@
 # round 6, last pass: the whole GPU suite, then the configurations touched since scratch/configs.sh ran
 O=gpurun_out/r06_cfg; mkdir -p $O gpurun_out/r06_full
 python -m pytest tests -m gpu -x -q > gpurun_out/r06_full/pytest.log 2>&1; grep -E "passed|failed" gpurun_out/r06_full/pytest.log | tail -1
-b() { name=$1; shift; python bench.py --detail $O/bench$name.json "$@" 2> $O/bench$name.err | grep "^{" | tail -1 > $O/line$name.json; }
+b() { name=$1; shift; python bench.py --full --detail $O/bench$name.json "$@" 2> $O/bench$name.err | grep "^{" | tail -1 > $O/line$name.json; }
 b ""
 b _pi4 --public-inputs 4 --no-cpu-baseline --no-cold-process
 b _d17_ecdsa --mix ecdsa --no-cpu-baseline --no-cold-process

@@ -1,9 +1,12 @@
 """bench.py's stdout contract on a CPU-only host: ONE JSON line, well under the 8 KB of stdout the driver's record keeps
 (round 4's line had grown to 21 KB and came back unparsed), carrying the contract's fields, `roofline` for ONE kernel and
-`cpu_baseline`; everything else lives in the detail file."""
+`cpu_baseline`; everything else lives in the detail file.  A plain run (no --full) carries the timed region's fields only;
+on the GPU box, one such run times exactly --steps proofs and dumps the last one."""
 import importlib.util
 import json
 import os
+
+import pytest
 
 from conftest import ROOT
 
@@ -96,3 +99,50 @@ def test_committed_bench_lines_of_this_round_fit():
         assert 0 < d["roofline"]["frac"] <= 1.0 and d["roofline"]["bound"] in ("hbm", "mfma"), p
         if re.match(r"r\d+_line\.json$", os.path.basename(p)):     # the driver's command: the side configurations skip the CPU legs
             assert d["cpu_baseline"]["kind"] in ("port", "reference") and d["cpu_baseline"]["cores"] >= 1, p
+
+
+def test_plain_line_carries_the_timed_region_only():
+    """A run without --full measures the timed region and nothing else: its line has the contract's fields and no field of a pass
+    that did not run (not even as null), and names no detail file."""
+    bench = _bench()
+    for world in (1, 2):
+        c = _canned(world)
+        plain = {k: c[k] for k in ("metric", "value", "unit", "n_gpus", "ranks_share_devices", "steps", "warmup", "clock_warmup_proofs",
+                                   "ms_per_step", "ms_per_step_min", "ms_per_step_max", "repeats", "timed_seconds", "higher_is_better",
+                                   "scaling", "vs_baseline", "dtype", "data", "config", "device")}
+        plain["in_flight_per_gpu"] = 4
+        d = json.loads(bench.compact_line(plain, None))
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus", "config"):
+            assert k in d, k
+        for k in ("latency_ms_single_proof", "latency_ms_single_proof_host_witness", "value_host_witness", "cold_process_ms", "roofline",
+                  "cpu_baseline", "latency_ms_sharded", "latency_ms_sharded_group", "rccl_ranks", "peer_access", "detail"):
+            assert k not in d, k
+
+
+@pytest.mark.gpu
+def test_plain_run_times_exactly_k_steps_and_dumps_the_last_proof(pkg, tmp_path):
+    """`bench.py --steps K` (no --full): ONE timed pass of exactly K proofs, and --dump-outputs holds the proof of the last step -- the
+    bytes the library gives for the same seeded circuit and witness, accepted by its verifier."""
+    import subprocess
+    import sys
+
+    import numpy as np
+    import torch
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--degree-bits", "13", "--mix", "arith",
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["repeats"] == 1 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert abs(d["value"] * d["ms_per_step"] - 1e3) < 2.0        # value = K / timed seconds, ms_per_step = timed ms / K
+    assert "latency_ms_single_proof" not in d and "roofline" not in d and "cpu_baseline" not in d
+    got = np.load(tmp_path / "out" / "proof.npy")
+    assert got.dtype == np.float32 and len(got) == d["config"]["proof_bytes"]
+    blob, wires = pkg.make_circuit(13, "arith", seed=1)
+    cd = pkg.CircuitData(blob)
+    proof = cd.prove(torch.from_numpy(wires.view(np.int64)).to("cuda:0")).to_bytes()
+    assert got.astype(np.uint8).tobytes() == proof
+    cd.verify(proof)
+    cd.close()

@@ -52,7 +52,8 @@ def _worker(rank, world, port, q):
     q.put((rank, mine, gathered, cap == full, t))
 
 
-def test_two_rank_gloo():
+def test_two_rank_gloo(built):
+    """The workers load the package and the oracle from the tree: `built` first, whatever ran before in the session."""
     import torch.multiprocessing as mp
 
     ctx = mp.get_context("spawn")
