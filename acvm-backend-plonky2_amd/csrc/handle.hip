@@ -710,8 +710,9 @@ static int shard_layout(p2gpu_circuit *c, int rank, int world) {
   // a different number of local cosets changes which part of wires.lde a column's transforms cover
   if (c->wire_clean.p) HIP_TRY(hipMemsetAsync(c->wire_clean.p, 0, sizeof(uint32_t) * c->W, c->stream));
   c->xchg_recv.release();
-  // receive side of the largest exchange: quotient interpolants (K * C * n words in total) or the query gather
-  HIP_TRY(c->xchg_recv.alloc(std::max((size_t)world * c->gather_cap, (size_t)c->K * c->C * c->n) + 64));
+  // receive side of the largest exchange: quotient interpolants (K * C * n words in total), the query gather, or the FRI batch
+  // reduction's partial sums ("shard_reduce": one [2][n] block per rank -- larger than both others when K = 1)
+  HIP_TRY(c->xchg_recv.alloc(std::max({(size_t)world * c->gather_cap, (size_t)c->K * c->C * c->n, (size_t)2 * world * c->n}) + 64));
   return P2GPU_OK;
 }
 static int shard_args_ok(p2gpu_circuit *c, int rank, int world) {

@@ -115,6 +115,12 @@ static int shard_allgather_impl(p2gpu_circuit *c, const void *send_dev, void *re
 }
 }  // namespace
 int shard_allgather(p2gpu_circuit *c, const void *send_dev, void *recv_dev, size_t bytes) {
+  // every rank writes world x bytes from recv_dev on: an exchange that does not fit the scratch it lands in is refused, not run
+  const int world = c->shard_world > 0 ? c->shard_world : 1;
+  if (recv_dev == (void *)c->xchg_recv.p && (size_t)world * bytes > c->xchg_recv.count * sizeof(gl_t)) {
+    set_err("internal: all-gather of %d x %zu bytes exceeds the exchange buffer (%zu bytes)", world, bytes, c->xchg_recv.count * sizeof(gl_t));
+    return P2GPU_E_DEVICE;
+  }
   ProfScope ps(exchange_name(bytes), (double)bytes * (double)(c->shard_world > 0 ? c->shard_world : 1));
   return shard_allgather_impl(c, send_dev, recv_dev, bytes);
 }
