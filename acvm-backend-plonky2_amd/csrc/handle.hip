@@ -1,12 +1,63 @@
 // handle.hip -- the circuit handle behind include/p2gpu.h: device selection, `p2gpu_circuit_create` (the prover-side half of
 // `build()`: tables, plans, the constants / sigmas commitment; plonky2-backend/src/circuit_translation/mod.rs:80-82), knobs,
 // sharding configuration, release -- and the stage-level operators the parity tests drive (inverse transform, LDE, row
-// hashing, commitment, field self-test).  The proof itself is prover.hip; the exchanges of a sharded proof transport.hip.
+// hashing, commitment, field self-test).  The proof itself is prover.hip, the commitment operators commit.hip, the exchanges of a
+// sharded proof transport.hip.
 #include "prover_internal.hpp"
 
 using namespace p2;
 
+namespace {
+
+// hostcore.hip's p2gpu_circuit_destroy calls this for prover handles (it has no HIP code of its own)
+void release_for_destroy(p2gpu_circuit *c) {
+  // rank 0 of a device group owns the other ranks and the rendezvous
+  for (p2gpu_circuit *m : c->group) {
+    m->peer = nullptr;
+    release_for_destroy(m);
+    delete m;
+  }
+  c->group.clear();
+  if (c->peer && c->shard_rank == 0) {
+    for (auto e : c->peer->recv_free) if (e) (void)hipEventDestroy(e);
+    for (auto e : c->peer->sent) if (e) (void)hipEventDestroy(e);
+    delete c->peer;
+  }
+  c->peer = nullptr;
+  (void)hipSetDevice(c->device);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  if (c->rccl_comm) (void)rccl().CommDestroy((ncclComm_t)c->rccl_comm);
+  c->rccl_comm = nullptr;
+  circuit_release(c);
+}
+struct ReleaseHook {
+  ReleaseHook() { p2::g_circuit_release = release_for_destroy; }
+} g_release_hook;
+
+// scratch allocations of the stage-level operators
+struct Scratch {
+  std::vector<void *> ptrs;
+  hipStream_t st = nullptr;
+  ~Scratch() {
+    for (void *p : ptrs) (void)hipFree(p);
+    if (st) (void)hipStreamDestroy(st);
+  }
+  template <class T> T *alloc(size_t n) {
+    void *p = nullptr;
+    if (hipMalloc(&p, (n ? n : 1) * sizeof(T)) != hipSuccess) return nullptr;
+    ptrs.push_back(p);
+    return (T *)p;
+  }
+};
+
+}  // namespace
+
 namespace p2 {
+
+int g_device = -1;
+std::vector<int> g_peer_access;  // [a * n + b]: see p2gpu_peer_access
+std::vector<int> g_devices;  // p2gpu_init's list; more than one entry: circuit handles are device groups
+
 void circuit_release(p2gpu_circuit *c) {
   c->tw_fwd.release(); c->tw_inv.release(); c->scale.release(); c->inv_scale.release(); c->d_kis.release();
   c->d_sigmas.release(); c->fri_scale.release(); c->d_gates.release(); c->qconst.release(); c->l0_lde.release();
@@ -41,44 +92,7 @@ void circuit_release(p2gpu_circuit *c) {
   if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
   if (c->stream) (void)hipStreamDestroy(c->stream);
 }
-}  // namespace p2
-namespace {
 
-// hostcore.hip's p2gpu_circuit_destroy calls this for prover handles (it has no HIP code of its own)
-void release_for_destroy(p2gpu_circuit *c) {
-  // rank 0 of a device group owns the other ranks and the rendezvous
-  for (p2gpu_circuit *m : c->group) {
-    m->peer = nullptr;
-    release_for_destroy(m);
-    delete m;
-  }
-  c->group.clear();
-  if (c->peer && c->shard_rank == 0) {
-    for (auto e : c->peer->recv_free) if (e) (void)hipEventDestroy(e);
-    for (auto e : c->peer->sent) if (e) (void)hipEventDestroy(e);
-    delete c->peer;
-  }
-  c->peer = nullptr;
-  (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (c->rccl_comm) (void)rccl().CommDestroy((ncclComm_t)c->rccl_comm);
-  c->rccl_comm = nullptr;
-  circuit_release(c);
-}
-struct ReleaseHook {
-  ReleaseHook() { p2::g_circuit_release = release_for_destroy; }
-} g_release_hook;
-
-}  // namespace
-namespace p2 {
-int g_device = -1;
-std::vector<int> g_peer_access;  // [a * n + b]: see p2gpu_peer_access
-std::vector<int> g_devices;  // p2gpu_init's list; more than one entry: circuit handles are device groups
-}  // namespace p2
-namespace {
-
-}  // namespace
-namespace p2 {
 int ensure_device() {
   if (g_device >= 0) return 0;
   int cnt = 0;
@@ -95,34 +109,10 @@ int ensure_device() {
   g_peer_access.assign(1, -1);
   return 0;
 }
+
 }  // namespace p2
-namespace {
-
-
-}  // namespace
-
-
-// scratch allocations of the stage-level operators
-namespace {
-struct Scratch {
-  std::vector<void *> ptrs;
-  hipStream_t st = nullptr;
-  ~Scratch() {
-    for (void *p : ptrs) (void)hipFree(p);
-    if (st) (void)hipStreamDestroy(st);
-  }
-  template <class T> T *alloc(size_t n) {
-    void *p = nullptr;
-    if (hipMalloc(&p, (n ? n : 1) * sizeof(T)) != hipSuccess) return nullptr;
-    ptrs.push_back(p);
-    return (T *)p;
-  }
-};
-}  // namespace
-
 
 extern "C" {
-
 
 int p2gpu_init(const int *device_ids, int n_devices) {
   int cnt = 0;
@@ -314,13 +304,10 @@ static int circuit_create_one(const uint8_t *blob, size_t len, int device, p2gpu
     // balance by an estimate of modmuls per row, group 0 starts with the permutation argument
     // (a PoseidonGate is not part of this: it has its own kernel, plonk.hip poseidon_gate_kernel)
     auto cost = [](const GateDesc &g) { return g.kind == G_POSEIDON ? 0u : 4u * g.num_constraints + 8u; };
-    const char *pce = getenv("P2GPU_PERM_COST");  // balance experiments only
-    const uint32_t perm_cost = pce ? (uint32_t)atoi(pce) : 8u * c->R + 100u;
+    const uint32_t perm_cost = (uint32_t)env_uint("P2GPU_PERM_COST", 8u * c->R + 100u);  // balance experiments only
     uint32_t total = 0;
     for (auto &g : c->gates) total += cost(g);
-    const char *env = getenv("P2GPU_GATE_GROUPS");
-    c->gate_groups = env ? (uint32_t)atoi(env) : (total > 2 * perm_cost ? 4u : 1u);
-    if (c->gate_groups != 4) c->gate_groups = 1;
+    c->gate_groups = env_uint("P2GPU_GATE_GROUPS", total > 2 * perm_cost ? 4u : 1u) == 4 ? 4u : 1u;
     uint32_t load[4] = {perm_cost, 0, 0, 0};
     std::vector<uint32_t> order(c->gates.size());
     for (size_t i = 0; i < order.size(); i++) order[i] = (uint32_t)i;
@@ -334,9 +321,9 @@ static int circuit_create_one(const uint8_t *blob, size_t len, int device, p2gpu
     }
     // Gates of degree <= 4 with enough constraints to pay for two transforms per challenge: evaluated on the even cosets only
     // (plonk.hip gate_sums_kernel).  The degree is the library's own count (gate_degree), not the blob's field.
-    const char *he = getenv("P2GPU_HALF_GATES");  // 0: off (A/B measurements); the knob "half_gates" does the same per handle
     uint64_t half_constraints = 0;
-    if (!(he && *he == '0') && c->d >= 6 && c->rate_bits == 3)
+    // P2GPU_HALF_GATES=0: off (A/B measurements); the knob "half_gates" does the same per handle
+    if (env_flag("P2GPU_HALF_GATES", true) && c->d >= 6 && c->rate_bits == 3)
       for (auto &g : c->gates)
         if (g.kind != G_POSEIDON && g.num_constraints >= 48 && gate_degree(g.kind, g.p) <= 4 && c->half_slots < 64) {
           g.pad |= (++c->half_slots) << 16;
@@ -351,11 +338,10 @@ static int circuit_create_one(const uint8_t *blob, size_t len, int device, p2gpu
       auto cost_main = [&](const GateDesc &g) { return gate_half_slot(g) ? 8u : cost(g); };
       uint32_t rest = 0;
       for (auto &g : c->gates) rest += cost_main(g);
-      const char *gge = getenv("P2GPU_GATE_GROUPS_HALF");  // balance experiments only
-      c->gate_groups_half = gge ? (atoi(gge) == 4 ? 4u : 1u) : (rest > 2 * perm_cost ? 4u : 1u);
+      // (P2GPU_GATE_GROUPS_HALF, P2GPU_SUMS_GROUPS: balance experiments only)
+      c->gate_groups_half = env_uint("P2GPU_GATE_GROUPS_HALF", rest > 2 * perm_cost ? 4u : 1u) == 4 ? 4u : 1u;
       uint32_t lm[4] = {perm_cost, 0, 0, 0}, ls[4] = {0, 0, 0, 0};
-      const char *sge = getenv("P2GPU_SUMS_GROUPS");  // balance experiments only
-      c->sums_groups = sge ? (atoi(sge) == 4 ? 4u : 1u) : (c->half_slots >= 2 ? 4u : 1u);
+      c->sums_groups = env_uint("P2GPU_SUMS_GROUPS", c->half_slots >= 2 ? 4u : 1u) == 4 ? 4u : 1u;
       for (uint32_t gi : order) {
         GateDesc &g = c->gates[gi];
         uint32_t bm = 0, bs = 0;
@@ -642,7 +628,7 @@ static int circuit_create_one(const uint8_t *blob, size_t len, int device, p2gpu
 
 int p2gpu_circuit_set(p2gpu_circuit *c, const char *key, uint64_t value) try {
   if (!c || !key) return P2GPU_E_ARG;
-  if (c->device < 0) { set_err("this is a verifier-only handle (p2gpu_verifier_create): no prover state"); return P2GPU_E_ARG; }
+  if (int rc = prover_handle(c)) return rc;
   for (p2gpu_circuit *m : c->group)  // a device group: every rank gets the same knobs (the ranks must take the same path)
     if (int rc = p2gpu_circuit_set(m, key, value)) return rc;
   HIP_TRY(hipSetDevice(c->device));
@@ -720,7 +706,7 @@ static int shard_args_ok(p2gpu_circuit *c, int rank, int world) {
     set_err("bad shard configuration: rank %d of %d (cosets %u)", rank, world, c ? c->C : 0u);
     return P2GPU_E_ARG;
   }
-  if (c->device < 0) { set_err("this is a verifier-only handle (p2gpu_verifier_create): no prover state"); return P2GPU_E_ARG; }
+  if (int rc = prover_handle(c)) return rc;
   return P2GPU_OK;
 }
 
@@ -767,7 +753,7 @@ int p2gpu_circuit_set_shard_rccl(p2gpu_circuit *c, int rank, int world, const ui
 // entries "name\0" (64 B each) + total ms + launch count; returns the number of entries
 int p2gpu_kernel_stats(p2gpu_circuit *c, char *names, double *ms, double *bytes, uint64_t *launches, int cap) try {
   if (!c) return P2GPU_E_ARG;
-  if (c->device < 0) { set_err("this is a verifier-only handle (p2gpu_verifier_create): no prover state"); return P2GPU_E_ARG; }
+  if (int rc = prover_handle(c)) return rc;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   flush_kstats(c);

@@ -1,6 +1,7 @@
 // internal.hpp -- declarations shared by the HIP translation units of libp2gpu.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstdlib>
 #include <vector>
 #include "gl.hpp"
 #include "keccak.hpp"
@@ -13,6 +14,19 @@ constexpr uint32_t MAX_GATE_CONSTRAINTS = 4096;  // per gate; every supported ki
 constexpr uint32_t MAX_ARITY_BITS = 4;  // FRI reduction arity 2^4 at most: one limit for circuit_parse, prover and verifier
 constexpr int MAX_CHALLENGES = 2;
 constexpr int MAX_ROUTED = 128;
+
+// ---- environment switches: the only readers of the environment in csrc/.  A call site that wants the value read once keeps it
+// in a function-local static ----
+// unset or empty: dflt; otherwise off exactly when the value starts with '0'
+inline bool env_flag(const char *name, bool dflt) {
+  const char *e = getenv(name);
+  return e && *e ? *e != '0' : dflt;
+}
+// unset: dflt; otherwise the decimal number the value starts with (0 when there is none)
+inline uint64_t env_uint(const char *name, uint64_t dflt) {
+  const char *e = getenv(name);
+  return e ? strtoull(e, nullptr, 10) : dflt;
+}
 
 // ---- per-launch profiling hook (HIP events on the launch stream, see prover.hip) ----
 struct Prof {
@@ -33,10 +47,10 @@ struct NttPass {
   uint32_t r[NTT_MAX_ROUNDS], tw_off[NTT_MAX_ROUNDS];
   // DIT passes on full 2^12 tiles whose first round has three layers also have a "direct" form (ntt.hip ntt_dit_*_kernel):
   // the first round straight from global memory (strided passes), the last one straight to it, its twiddles shifts only.
-  // ftw_off: offset in the plan's table of the folded twiddles of the round before the last (see fold_table_kernel)
+  // ftw_off: offset in the plan's table of the folded twiddles of the round before the last (strided passes: fold_table_kernel)
   bool direct = false;
   uint32_t ftw_off = 0;
-  uint32_t ftw2_off = 0;  // head pass: the folded table in ntt_dit_head2_kernel's lane order
+  uint32_t ftw2_off = 0;  // head pass (s = 0) instead: its folded table in ntt_dit_head2_kernel's lane order
 };
 struct NttPlan {
   uint32_t d = 0;
@@ -81,7 +95,7 @@ struct ColHints {
   uint32_t dense_hint = 0;          // profile accounting only: how many of the columns are dense (the handle's previous proof;
                                     // 0 = not known -- the transforms' bytes are then counted for every column)
   bool fill_only = false;           // write the structured columns and return: the dense ones are somebody else's (a rank of a
-                                    // sharded proof transforms only its block of the dense columns, prover.hip shard_intt)
+                                    // sharded proof transforms only its block of the dense columns, commit.hip shard_intt)
 };
 void ntt_batch(hipStream_t st, const NttPlan *plan, const gl_t *src, gl_t *dst, uint32_t cols, uint32_t cosets,
                const gl_t *scale, gl_t post, bool src_per_coset, CosetMap cm = CosetMap(), uint32_t stride_cols = 0,

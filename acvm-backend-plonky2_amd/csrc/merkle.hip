@@ -693,7 +693,7 @@ bool merkle_tail(hipStream_t st, dig_t *lvl, uint32_t cosets, uint32_t m, uint32
 
 // P2GPU_LEAF_LEVELS=0: the leaf kernels leave every tree level to merkle_level / merkle_tail (A/B measurements)
 static bool leaf_levels_on() {
-  static const bool on = [] { const char *e = getenv("P2GPU_LEAF_LEVELS"); return !(e && *e == '0'); }();
+  static const bool on = env_flag("P2GPU_LEAF_LEVELS", true);
   return on;
 }
 // Returns how many tree levels above the leaf digests the launch has ALSO built (0 or 2): lvl1 / lvl2 = storage of the levels with

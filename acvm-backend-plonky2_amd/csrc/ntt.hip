@@ -29,8 +29,6 @@
 // kernel runs, not its limiter.  No MFMA.
 #include "internal.hpp"
 #include <algorithm>
-#include <map>
-#include <mutex>
 #include <type_traits>
 #include <vector>
 
@@ -176,8 +174,8 @@ struct PassArgs {
   uint32_t tw_off[MAX_ROUNDS];  // offset of the round's table in ptw
   const uint32_t *colnz;        // optional [cols]: class of every column (ColHints, internal.hpp); only class 2 (dense)
                                 // columns are transformed here, the others are written by structured_fill_kernel
-  const gl_t *ftw;              // direct DIT passes: folded twiddles of the round before the last (fold_table_kernel)
-  const gl_t *ftw2;             // ntt_dit_head2_kernel: the same values in its lane order (head_fold_table_kernel)
+  const gl_t *ftw;              // direct strided passes: folded twiddles of the round before the last (fold_table_kernel)
+  const gl_t *ftw2;             // direct head / tail pass: the same kind of table in its lane order (head_fold_table_kernel)
 };
 
 __device__ __forceinline__ uint32_t gidx(uint32_t e, uint32_t hi_base, uint32_t lo0, uint32_t s, uint32_t tb) {
@@ -413,9 +411,8 @@ __global__ __launch_bounds__(TBC ? NTT_THREADS : 256, TBC ? NTT_MIN_WAVES : 1) v
 //     it is multiplied into that round's input twiddles (one folded table: fold_table_kernel), and what is left,
 //     w_{2^(r' + r)}^(k * brev(j)), is a power of w_64 = 2^3 -- a SHIFT -- with k uniform over the wave (k sits in bits >= 6 of the
 //     lane's group index): a scalar branch on k, then compile-time shift amounts.
-// 12-layer first pass: 5.25 -> 4.5 general products per element over the 17 layers of a 2^17-point transform together with the
-// 5-layer pass, 8 -> 5 LDS round trips, 6 -> 3 barriers.  Same values (the field result of a butterfly network does not depend on
-// how its twiddles are factored): bit-exact against the oracle and against ntt_pass_kernel (P2GPU_NTT_DIRECT=0).
+// Same values (the field result of a butterfly network does not depend on how its twiddles are factored): bit-exact against the
+// oracle and against ntt_pass_kernel (P2GPU_NTT_DIRECT=0).  The 12-layer first pass goes further (ntt_dit_head2_kernel below).
 template <int E>
 __device__ __forceinline__ gl_t mul_pow2_any(gl_t x) {  // x * 2^E, 0 <= E < 192 (2^96 = -1)
   if constexpr (E == 0) return x;
@@ -531,53 +528,17 @@ __device__ __forceinline__ bool pass_unit(const PassArgs &A, uint32_t &tile, uin
   col = unit / A.tiles;
   return !(A.colnz != nullptr && A.colnz[col] != 2u);
 }
-// The 12-layer first pass of a DIT transform of >= 2^12 points (s = 0, tb = 0: contiguous tiles): coalesced load (+ coset scale)
-// -> LDS | rounds on bits 0-2, 3-5, 6-8 inside each wave (no barrier; the third with the folded table) | last round -> global.
-template <bool INV>
-__global__ __launch_bounds__(NTT_THREADS, NTT_MIN_WAVES) void ntt_dit_head_kernel(PassArgs A) {
-  static_assert(NTT_THREADS == 512 && NTT_TILE_BITS == 12 && NTT_PER == 8, "direct passes: 512 lanes x 8 elements");
-  extern __shared__ gl_t lds[];
-  uint32_t tile, col, coset;
-  if (!pass_unit(A, tile, col, coset)) return;
-  const size_t n = (size_t)1 << A.d;
-  const gl_t *src = A.src + ((size_t)(A.src_single ? 0 : coset) * A.cols + col) * n;
-  gl_t *dst = A.dst + ((size_t)coset * A.cols + col) * n;
-  const gl_t *scale = A.scale ? A.scale + (size_t)(A.coset_first + coset * A.coset_stride) * n : nullptr;
-  const uint32_t tbase = tile << 12;
-  {
-    gl_t x[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) x[i] = src[tbase + threadIdx.x + (uint32_t)i * NTT_THREADS];
-    if (scale) {
-      gl_t sc[8];
-#pragma unroll
-      for (int i = 0; i < 8; i++) sc[i] = scale[tbase + threadIdx.x + (uint32_t)i * NTT_THREADS];
-#pragma unroll
-      for (int i = 0; i < 8; i++) x[i] = gl_mul(x[i], sc[i]);
-    }
-    const uint32_t l0 = pidx(threadIdx.x);  // (the swizzle moves bits below 5 only: + i * 512 commutes with it)
-#pragma unroll
-    for (int i = 0; i < 8; i++) lds[l0 + (uint32_t)i * NTT_THREADS] = x[i];
-  }
-  __syncthreads();
-  // rounds on bits [0, 9): wave w works on the elements whose bits [9, 12) are w in all three, and a wave's LDS operations
-  // execute in order (see wave_private in tile_body)
-  round_regs<1, INV, 3, false>(lds, A, 12, 0, 0, nullptr);
-  asm volatile("" ::: "memory");
-  round_regs<1, INV, 3, true>(lds, A, 12, 3, 0, A.ptw + A.tw_off[1]);
-  asm volatile("" ::: "memory");
-  round_folded<INV, 3>(lds, A, 6, 3, 0, A.ftw);
-  __syncthreads();
-  round_to_global<INV, 3, 3>(lds, dst, A, tbase, 0);
-}
-// The same pass with its FIRST round in registers too, and the second one on shifts (w_64 = 2^3, so the 64-point
-// transform on tile bits 0-5 needs no table): a lane loads 8 CONSECUTIVE words (64 B: the round on bits 0-2 is then its own eight
-// registers; a wave still covers 4 KB contiguous), scales them, runs the twiddle-free 8-point transform and only then stores to LDS.
-// The round on bits 3-5 multiplies input j by w_64^(k1 brev(j)), k1 = element bits 0-2: made WAVE-uniform by giving wave w the
-// groups with k1 = w (lane = bits 6-11), so the eight shift amounts are compile-time behind one scalar branch; the round on bits
-// 6-8 (folded table, laid out in this kernel's lane order: head_fold_table_kernel) keeps wave <-> k1 and therefore needs no barrier
-// in between; then the last round -> global as in ntt_dit_head_kernel.  Against that kernel: 3 instead of 4 LDS round trips, 7 of 8
-// general products per element gone, the same two barriers.  LDS addresses through pidx2 (every access conflict-free).
+static_assert(NTT_THREADS == 512 && NTT_TILE_BITS == 12 && NTT_PER == 8, "direct passes: 512 lanes x 8 elements");
+// The 12-layer first pass of a DIT transform of >= 2^12 points (s = 0, tb = 0: contiguous tiles), three LDS round trips and two
+// barriers.  Its FIRST round runs in registers: a lane loads 8 CONSECUTIVE words (64 B: the round on bits 0-2 is then its own eight
+// registers; a wave still covers 4 KB contiguous), scales them by the coset scale, runs the twiddle-free 8-point transform and only
+// then stores to LDS.  The second round is on shifts (w_64 = 2^3, so the 64-point transform on tile bits 0-5 needs no table): the
+// round on bits 3-5 multiplies input j by w_64^(k1 brev(j)), k1 = element bits 0-2: made WAVE-uniform by giving wave w the groups
+// with k1 = w (lane = bits 6-11), so the eight shift amounts are compile-time behind one scalar branch; the round on bits 6-8
+// (folded table, laid out in this kernel's lane order: head_fold_table_kernel) keeps wave <-> k1 and therefore needs no barrier in
+// between (a wave's LDS operations execute in order, see wave_private in tile_body); then the last round -> global
+// (round_to_global).  One general product per element besides the coset scale.  LDS addresses through pidx2 (every access
+// conflict-free).
 template <bool INV>
 __global__ __launch_bounds__(NTT_THREADS, NTT_MIN_WAVES) void ntt_dit_head2_kernel(PassArgs A) {
   extern __shared__ gl_t lds[];
@@ -932,14 +893,9 @@ __global__ void head_fold_table_kernel(gl_t *out, gl_t root_n, uint32_t d) {
   const uint64_t ex = (((uint64_t)lo * e) << (d - 9)) + (((uint64_t)lo * bitrev32(J, 3)) << (d - 12));
   out[i] = gl_pow(root_n, ex);
 }
-// P2GPU_NTT_HEAD=1: the head pass through ntt_dit_head_kernel (first two rounds in LDS with table twiddles) instead of ntt_dit_head2_kernel
-static bool head2_on() {
-  static const bool on = [] { const char *e = getenv("P2GPU_NTT_HEAD"); return !(e && *e == '1'); }();
-  return on;
-}
 // P2GPU_NTT_DIRECT=0: every pass through ntt_pass_kernel (A/B measurements, and the reference the direct kernels are tested against)
 static bool direct_on() {
-  static const bool on = [] { const char *e = getenv("P2GPU_NTT_DIRECT"); return !(e && *e == '0'); }();
+  static const bool on = env_flag("P2GPU_NTT_DIRECT", true);
   return on;
 }
 
@@ -1014,11 +970,12 @@ NttPlan *ntt_plan_create(hipStream_t st, uint32_t d, int dit, bool inverse) {
         const uint32_t q = np.nrounds - 2, rl = np.r[np.nrounds - 1];  // the round before the last
         uint32_t bq = ps.tb;
         for (uint32_t i = 0; i < q; i++) bq += np.r[i];
-        np.ftw_off = (uint32_t)total;
-        total += (size_t)1 << (np.r[q] + rl + (bq - ps.tb + ps.s));
-        if (ps.s == 0) {  // the head pass: the same 4096 values once more, in ntt_dit_head2_kernel's lane order
+        if (ps.s == 0) {  // the head pass: its 4096 folded twiddles in the lane order of ntt_dit_head2_kernel / ntt_dif_tail2_kernel
           np.ftw2_off = (uint32_t)total;
           total += 4096;
+        } else {
+          np.ftw_off = (uint32_t)total;
+          total += (size_t)1 << (np.r[q] + rl + (bq - ps.tb + ps.s));
         }
       }
     }
@@ -1052,8 +1009,8 @@ NttPlan *ntt_plan_create(hipStream_t st, uint32_t d, int dit, bool inverse) {
         uint32_t bq = np.tb;
         for (uint32_t i = 0; i < q; i++) bq += np.r[i];
         const uint32_t s0 = bq - np.tb + np.s, cnt = 1u << (np.r[q] + rl + s0);
-        hipLaunchKernelGGL(fold_table_kernel, dim3((cnt + 255) / 256), dim3(256), 0, st, p->ptw + np.ftw_off, root, d, s0, np.r[q], rl);
         if (np.s == 0) hipLaunchKernelGGL(head_fold_table_kernel, dim3(16), dim3(256), 0, st, p->ptw + np.ftw2_off, root, d);
+        else hipLaunchKernelGGL(fold_table_kernel, dim3((cnt + 255) / 256), dim3(256), 0, st, p->ptw + np.ftw_off, root, d, s0, np.r[q], rl);
       }
     }
   }
@@ -1104,54 +1061,6 @@ __global__ __launch_bounds__(256) void structured_fill_kernel(gl_t *dst, uint32_
   }
 }
 
-static void ntt_passes(hipStream_t st, const NttPlan *plan, const gl_t *src, gl_t *dst, uint32_t cols, uint32_t cosets,
-                       const gl_t *scale, gl_t post, bool src_per_coset, CosetMap cm, uint32_t stride_all, const uint32_t *colnz,
-                       uint32_t dense = 0);
-void ntt_batch(hipStream_t st, const NttPlan *plan, const gl_t *src, gl_t *dst, uint32_t cols, uint32_t cosets,
-               const gl_t *scale, gl_t post, bool src_per_coset, CosetMap cm, uint32_t stride_cols, const ColHints *hints) {
-  if (cols == 0) return;
-  if (hints) {
-    const size_t n = (size_t)1 << plan->d;
-    const uint32_t bx = (uint32_t)std::max<size_t>(1, n / (256 * 4));
-    // (profile bytes: the structured columns that are actually stored -- those below virt_first; with no dense count from an earlier
-    // proof every column is counted)
-    const uint32_t stored = hints->virt_first < cols ? hints->virt_first : cols;
-    const uint32_t filled = hints->dense_hint && hints->dense_hint <= cols ? (stored > hints->dense_hint ? stored - hints->dense_hint : 0) : cols;
-    ProfScope ps("structured_fill_kernel", 8.0 * filled * cosets * (double)n);
-    // Columns at or above virt_first are stored only when they are dense (the transform kernels) or of class 3, and class 3 exists
-    // only with more than one special row (public-input circuits): otherwise the grid stops at virt_first -- 80 instead of 234
-    // column rows of blocks for a circuit without ECC gates, most of which would only look at their class and leave
-    const uint32_t fill_cols = hints->nrows > 1 ? cols : std::min(cols, hints->virt_first);
-    if (fill_cols)
-      hipLaunchKernelGGL(structured_fill_kernel, dim3(bx, fill_cols), dim3(256), 0, st, dst, plan->d,
-                         stride_cols ? stride_cols : cols, cosets, *hints, cm.first, cm.stride);
-    if (hints->fill_only) return;
-  }
-  const uint32_t d = plan->d;
-  const size_t np = plan->passes.size();
-  // A transform of several passes leaves its intermediate in dst between them.  With every column in one launch per pass
-  // that intermediate (8n words per column for an LDE) is long gone from the 256 MB memory-side cache when the next pass
-  // reads it; in groups of columns whose dst fits, the second pass finds it there and overwrites it in place: the
-  // intermediate's round trip never reaches HBM (P2GPU_NTT_GROUP_MB: group size, 0 = one launch per pass as before)
-  static const size_t group_bytes = [] {
-    const char *e = getenv("P2GPU_NTT_GROUP_MB");
-    return (size_t)(e ? atoi(e) : 0) << 20;
-  }();
-  const uint32_t stride_all = stride_cols ? stride_cols : cols;
-  const uint32_t *colnz = hints ? hints->cls : nullptr;
-  if (np >= 2 && group_bytes) {
-    const size_t per_col = (size_t)cosets * 8 << d;
-    const uint32_t gcols = (uint32_t)std::max<size_t>(1, group_bytes / per_col);
-    if (gcols < cols) {
-      for (uint32_t c0 = 0; c0 < cols; c0 += gcols)
-        ntt_passes(st, plan, src + ((size_t)c0 << d), dst + ((size_t)c0 << d), std::min(gcols, cols - c0), cosets, scale, post,
-                   src_per_coset, cm, stride_all, colnz ? colnz + c0 : nullptr);
-      return;
-    }
-  }
-  ntt_passes(st, plan, src, dst, cols, cosets, scale, post, src_per_coset, cm, stride_all, colnz,
-             hints && hints->dense_hint && hints->dense_hint <= cols ? hints->dense_hint : 0);
-}
 static void fill_pass_args(PassArgs &A, const NttPlan *plan, size_t i, const gl_t *src, gl_t *dst, uint32_t cols, uint32_t cosets,
                            const gl_t *scale, gl_t post, bool src_per_coset, CosetMap cm, uint32_t stride_all, const uint32_t *colnz) {
   const size_t np = plan->passes.size();
@@ -1169,7 +1078,7 @@ static void fill_pass_args(PassArgs &A, const NttPlan *plan, size_t i, const gl_
   A.coset_stride = cm.stride;
   A.nrounds = ps.nrounds;
   A.colnz = colnz;
-  A.ftw = ps.direct ? plan->ptw + ps.ftw_off : nullptr;
+  A.ftw = ps.direct && ps.s != 0 ? plan->ptw + ps.ftw_off : nullptr;
   A.ftw2 = ps.direct && ps.s == 0 ? plan->ptw + ps.ftw2_off : nullptr;
   for (int k = 0; k < MAX_ROUNDS; k++) { A.r[k] = ps.r[k]; A.tw_off[k] = ps.tw_off[k]; }
   A.tiles = 1u << (plan->d - (A.a + A.tb));
@@ -1225,12 +1134,9 @@ static void ntt_passes(hipStream_t st, const NttPlan *plan, const gl_t *src, gl_
           else P2_STRIDED_DIF(3, 3);
 #undef P2_STRIDED_DIF
         }
-      } else if (ps.s == 0 && head2_on()) {
+      } else if (ps.s == 0) {
         ProfScope psd("ntt_dit_head2_kernel<false>", bytes);
         hipLaunchKernelGGL((ntt_dit_head2_kernel<false>), grid, dim3(NTT_THREADS), lb, st, A);
-      } else if (ps.s == 0) {
-        ProfScope psd("ntt_dit_head_kernel<false>", bytes);
-        hipLaunchKernelGGL((ntt_dit_head_kernel<false>), grid, dim3(NTT_THREADS), lb, st, A);
       } else {
 #define P2_STRIDED(RM, RL)                                                                                        \
   do {                                                                                                            \
@@ -1262,6 +1168,30 @@ static void ntt_passes(hipStream_t st, const NttPlan *plan, const gl_t *src, gl_
     }
 #undef P2_LAUNCH
   }
+}
+
+void ntt_batch(hipStream_t st, const NttPlan *plan, const gl_t *src, gl_t *dst, uint32_t cols, uint32_t cosets,
+               const gl_t *scale, gl_t post, bool src_per_coset, CosetMap cm, uint32_t stride_cols, const ColHints *hints) {
+  if (cols == 0) return;
+  if (hints) {
+    const size_t n = (size_t)1 << plan->d;
+    const uint32_t bx = (uint32_t)std::max<size_t>(1, n / (256 * 4));
+    // (profile bytes: the structured columns that are actually stored -- those below virt_first; with no dense count from an earlier
+    // proof every column is counted)
+    const uint32_t stored = hints->virt_first < cols ? hints->virt_first : cols;
+    const uint32_t filled = hints->dense_hint && hints->dense_hint <= cols ? (stored > hints->dense_hint ? stored - hints->dense_hint : 0) : cols;
+    ProfScope ps("structured_fill_kernel", 8.0 * filled * cosets * (double)n);
+    // Columns at or above virt_first are stored only when they are dense (the transform kernels) or of class 3, and class 3 exists
+    // only with more than one special row (public-input circuits): otherwise the grid stops at virt_first -- 80 instead of 234
+    // column rows of blocks for a circuit without ECC gates, most of which would only look at their class and leave
+    const uint32_t fill_cols = hints->nrows > 1 ? cols : std::min(cols, hints->virt_first);
+    if (fill_cols)
+      hipLaunchKernelGGL(structured_fill_kernel, dim3(bx, fill_cols), dim3(256), 0, st, dst, plan->d,
+                         stride_cols ? stride_cols : cols, cosets, *hints, cm.first, cm.stride);
+    if (hints->fill_only) return;
+  }
+  ntt_passes(st, plan, src, dst, cols, cosets, scale, post, src_per_coset, cm, stride_cols ? stride_cols : cols, hints ? hints->cls : nullptr,
+             hints && hints->dense_hint && hints->dense_hint <= cols ? hints->dense_hint : 0);
 }
 
 // ---- zero-column flags --------------------------------------------------------------

@@ -1,22 +1,16 @@
-// prover_internal.hpp -- what prover.hip (the proof) and handle.hip (the circuit handle, the stage-level operators) share.
+// prover_internal.hpp -- what the translation units of the prover share: commit.hip (commitment operators), upload.hip (the
+// host-witness pipeline), prover.hip (the proof and its entry points) and handle.hip (the circuit handle, the stage-level operators).
 #pragma once
 #include "circuit.hpp"
 #include "transport.hpp"
 #include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <cstdarg>
 #include <cstdio>
-#include <cstring>
-#include <map>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 namespace p2 {
-// P2GPU_TRACE=1: synchronise after every phase and report progress on stderr (debugging aid)
-bool trace_on();
-double now_ms();
 #define TRACE(c, label)                                                                     \
   do {                                                                                      \
     if (p2::trace_on()) {                                                                   \
@@ -26,17 +20,63 @@ double now_ms();
     }                                                                                       \
   } while (0)
 
+// the refusal of a verifier-only handle by every entry point that needs prover state (0: c is a prover handle)
+inline int prover_handle(const p2gpu_circuit *c) {
+  if (c->device >= 0) return 0;
+  set_err("this is a verifier-only handle (p2gpu_verifier_create): no prover state");
+  return P2GPU_E_ARG;
+}
+
 // ---- prover.hip ----
+// P2GPU_TRACE=1: synchronise after every phase and report progress on stderr (debugging aid)
+bool trace_on();
+double now_ms();
+// P2GPU_HOSTPROF=1: host-side timestamps at the transcript sync points of one proof (no extra synchronisation), printed
+// at the end of prove: where the host sits between GPU phases.  One per host thread.
+struct HostProf {
+  std::vector<std::pair<const char *, double>> ev;
+  void mark(const char *label);
+  void dump();
+};
+extern thread_local HostProf g_hp;
+// per-launch timing with HIP events on the launch stream (knob "profile")
+struct EventProf : Prof {
+  p2gpu_circuit *c;
+  hipEvent_t a = nullptr, b = nullptr;
+  const char *name = nullptr;
+  double bytes = 0;
+  bool active = false;
+  explicit EventProf(p2gpu_circuit *c_) : c(c_) {}
+  hipEvent_t get();  // from the handle's pool
+  void begin(const char *k, double by) override;
+  void end() override;
+};
+// ... installed as the calling thread's g_prof for the guard's lifetime when the handle's knob asks for it
+struct ProfGuard {
+  EventProf prof;
+  explicit ProfGuard(p2gpu_circuit *c) : prof(c) { g_prof = c->profile ? &prof : nullptr; }
+  ~ProfGuard() { g_prof = nullptr; }
+};
 void flush_kstats(p2gpu_circuit *c);                 // read the pending per-launch event pairs into c->kstats
+int prove_impl(p2gpu_circuit *c, const gl_t *wires_dev, const uint64_t *pis, uint32_t n_pi, uint8_t *proof_out, size_t *proof_len,
+               p2gpu_timings *tm, double h2d_ms);
+// ---- commit.hip ----
 int pin_exhausted();
+const gl_t *hprc(const p2gpu_circuit *c);
+int wait_stream(p2gpu_circuit *c);
 void tree_layout(Batch &b, uint32_t cosets, size_t m0, size_t cap_per);
 int tree_alloc(Batch &b, uint32_t C, size_t m0, size_t cap_per);
-int wait_stream(p2gpu_circuit *c);
 int tree_build(p2gpu_circuit *c, Batch &b, size_t m0, uint32_t levels_done = 0);
+const uint32_t *batch_colnz(const p2gpu_circuit *c, const Batch &b);
+uint32_t virt_first(const p2gpu_circuit *c);
+ColHints wire_hints(const p2gpu_circuit *c, uint32_t col0, bool lde);
+VirtCols batch_virt(const p2gpu_circuit *c, const Batch &b);
 int batch_alloc(p2gpu_circuit *c, Batch &b, uint32_t cols);
 int batch_commit_from_values(p2gpu_circuit *c, Batch &b, const gl_t *vals_dev);
 int batch_commit_from_coeffs(p2gpu_circuit *c, Batch &b);
-const gl_t *hprc(const p2gpu_circuit *c);
+// ---- upload.hip ----
+int prove_host(p2gpu_circuit *c, const uint64_t *wires, uint32_t ncols, const uint64_t *tail, uint32_t row, const uint64_t *pis,
+               uint32_t n_pi, uint8_t *proof_out, size_t *proof_len, p2gpu_timings *tm);
 // ---- handle.hip ----
 int ensure_device();
 extern int g_device;

@@ -74,10 +74,7 @@ static int shard_allgather_impl(p2gpu_circuit *c, const void *send_dev, void *re
     // grouped send / receive per peer -- on xGMI's point-to-point links all seven transfers of a rank run at once,
     // where a ring all-gather is bound by one link; the small ones (caps, PoW minima, query rows)
     // stay with ncclAllGather's latency-optimised protocols.  P2GPU_RCCL_P2P_BYTES moves the threshold (0: never).
-    static const size_t p2p_min = [] {
-      const char *e = getenv("P2GPU_RCCL_P2P_BYTES");
-      return e ? (size_t)strtoull(e, nullptr, 10) : ((size_t)1 << 20);
-    }();
+    static const size_t p2p_min = (size_t)env_uint("P2GPU_RCCL_P2P_BYTES", (size_t)1 << 20);
     if (p2p_min && bytes >= p2p_min && r.Send && r.Recv && r.GroupStart && r.GroupEnd) {
       const int world = c->shard_world, q = c->shard_rank;
       uint8_t *mine = (uint8_t *)recv_dev + (size_t)q * bytes;

@@ -126,7 +126,7 @@ def exchange_bytes(entry_bytes, world_size):
 def exchange_plan(degree_bits, world_size, num_wires=234, num_constants_sigmas=84, num_challenges=2, partial_products=9,
                   quotient_degree_factor=8, rate_bits=3, cap_height=4, num_queries=28, host_witness=False, dense_columns=None,
                   shard_intt=False, dense_list=None, shard_reduce=False, shard_zs=False, num_routed=80):
-    """The exchange steps of ONE coset-sharded proof (csrc/prover.hip shard_allgather call sites), in
+    """The exchange steps of ONE coset-sharded proof (the shard_allgather call sites of csrc/commit.hip, upload.hip and prover.hip), in
     order: [(what, bytes each rank sends)].  Every step is an all-gather over the `world_size` ranks, so a rank receives
     (world_size - 1) x those bytes (a tuple: unequal blocks, bytes per rank -- `exchange_bytes`); nothing else crosses between the GPUs.  Host-side restatement for tests and budgets: the
     GPU tests compare it with what the library counts (`profile` = 2: the exchange[...] pseudo-kernels of p2gpu_kernel_stats)."""

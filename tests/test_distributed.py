@@ -145,7 +145,7 @@ def test_bench_refuses_more_gpus_than_the_box_has():
 def test_exchange_plan_of_a_sharded_proof(pkg, d, world):
     """DESIGN.md section 7's table, walked without a GPU: the exchanges of one coset-sharded proof, their
     number and their bytes, for the BASELINE sizes on 2 / 4 / 8 GPUs.  `exchange_plan` restates the shard_allgather call sites of
-    csrc/prover.hip; the GPU suite checks it against what the library counts (test_exchange_plan_matches_the_library)."""
+    csrc/commit.hip, upload.hip and prover.hip; the GPU suite checks it against what the library counts (test_exchange_plan_matches_the_library)."""
     n, G = 1 << d, world
     plan = pkg.parallel.exchange_plan(d, world)
     names = [p[0] for p in plan]

@@ -116,7 +116,7 @@ def test_two_pass_transforms_ragged_column_counts(gpu):
 
 @pytest.mark.parametrize("d", [12, 15, 17, 18, 19, 20])
 def test_direct_dit_passes_match_oracle(pkg, orc, gpu, d):
-    """The direct DIT passes of round 5 (ntt.hip ntt_dit_head_kernel / ntt_dit_strided_kernel: first round from global memory, last
+    """The direct DIT passes of round 5 (ntt.hip ntt_dit_head2_kernel / ntt_dit_strided_kernel: first round from global memory, last
     round to it with shift twiddles, folded table in between), one size per shape of the strided pass -- 12: head only; 15: [3];
     17: [3,2]; 18: [3,3]; 19: [3,2,2]; 20: [3,3,2] (21 = [3,3,3] and 22 = two strided passes: test_deep_transforms) -- every word of
     the coset LDE against the oracle, three columns (one of edge words, one zero)."""
@@ -132,7 +132,7 @@ def test_direct_dit_passes_match_oracle(pkg, orc, gpu, d):
 
 def test_ab_switches_keep_every_byte(gpu):
     """The A/B switches of round 5, each in a process of its own (they are read once): P2GPU_NTT_DIRECT=0 sends every pass through
-    ntt_pass_kernel (the round 1-4 path), P2GPU_NTT_HEAD=1 takes the head pass with its first two rounds in LDS (ntt_dit_head_kernel),
+    ntt_pass_kernel (the round 1-4 path),
     P2GPU_LEAF_LEVELS=0 leaves every tree level to merkle_level / merkle_tail instead of
     building the first two inside the leaf-hash launch.  Same LDE words, same proof bytes (virtual-column wires tree, plain
     Z / quotient trees, a 231-dense-column witness) as the default build."""
@@ -160,16 +160,16 @@ for d, mix in ((8, "sha"), (11, "sha"), (14, "ecdsa")):
     print("PROOF-novirt", d, mix, hashlib.sha256(cd.prove(wires).to_bytes()).hexdigest())
 """.format(root=root)
     outs = []
-    for env in ({}, {"P2GPU_NTT_DIRECT": "0"}, {"P2GPU_LEAF_LEVELS": "0"}, {"P2GPU_NTT_HEAD": "1"}):
+    for env in ({}, {"P2GPU_NTT_DIRECT": "0"}, {"P2GPU_LEAF_LEVELS": "0"}):
         r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-2000:]
         outs.append([ln for ln in r.stdout.splitlines() if ln.startswith(("LDE", "PROOF"))])
-    assert len(outs[0]) == 16 and outs[0] == outs[1] == outs[2] == outs[3]
+    assert len(outs[0]) == 16 and outs[0] == outs[1] == outs[2]
 
 
 def test_measurement_switches_keep_every_byte(pkg, orc, gpu):
     """Every other environment switch of INTEGRATION.md section 7 (the host-witness pipeline's, the gate-group balance, the staged /
-    unstaged gate sums, the round-4 column groups), each in a process of its own: the proofs of a `sha` circuit through the
+    unstaged gate sums), each in a process of its own: the proofs of a `sha` circuit through the
     host-matrix entry and of an `ecdsa` circuit with the half-domain route forced are the ORACLE's bytes under every one of them."""
     import hashlib
     import os
@@ -197,7 +197,7 @@ for d, mix in ((11, "sha"), (12, "ecdsa")):
     envs = ({}, {"P2GPU_CHUNK_BLOCKS": "1"}, {"P2GPU_CHUNK_BLOCKS": "5"}, {"P2GPU_HOST_PRESCAN": "0"}, {"P2GPU_HALF_GATES": "0"},
             {"P2GPU_SUMS_STAGE": "0"}, {"P2GPU_GATE_GROUPS": "4", "P2GPU_GATE_GROUPS_HALF": "4", "P2GPU_SUMS_GROUPS": "4"},
             {"P2GPU_GATE_GROUPS": "1", "P2GPU_GATE_GROUPS_HALF": "1", "P2GPU_SUMS_GROUPS": "1"}, {"P2GPU_PERM_COST": "100000"},
-            {"P2GPU_PERM_COST": "1", "P2GPU_GATE_GROUPS": "4", "P2GPU_GATE_GROUPS_HALF": "4"}, {"P2GPU_NTT_GROUP_MB": "1"})
+            {"P2GPU_PERM_COST": "1", "P2GPU_GATE_GROUPS": "4", "P2GPU_GATE_GROUPS_HALF": "4"})
     for env in envs:
         r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, (env, r.stderr[-2000:])
