@@ -204,6 +204,7 @@ struct CircuitState {
   uint32_t C;  // cosets = 2^rate_bits
   std::vector<GateDesc> gates;
   std::vector<gl_t> k_is;
+  std::vector<uint8_t> blob_prefix;  // prover handles: the circuit blob up to the constants table (p2gpu_circuit_export_blob)
   uint32_t nterms = 0, max_gate_constraints = 0;
   uint32_t gate_groups = 1;  // quotient kernel: 1, or 4 when the gate set is heavy
   // gates of degree <= 4 evaluated on the even cosets only, their folded sums extended to the odd cosets (plonk.hip gate_sums_kernel)
@@ -319,6 +320,15 @@ const char *gate_validate(uint32_t kind, const uint32_t p[4], uint32_t W, uint32
                           uint32_t *consts_used);
 uint32_t gate_num_constraints(uint32_t kind, const uint32_t p[4]);
 uint32_t gate_degree(uint32_t kind, const uint32_t p[4]);
+// N2 on the host, shared by p2gpu_build_blob and p2gpu_circuit_build (hostcore.hip): what the size of a circuit blob depends
+// on, and the blob prefix (header, gate table with selector groups, k_is) that circuit_parse reads
+struct BuildPlan {
+  size_t n = 0, prefix_len = 0;
+  uint32_t R = 0, num_selectors = 0, ngc = 0, NC = 0;  // ngc: gate-constant columns (max over the gates)
+  std::vector<uint32_t> gstart, gend, gsel, arity;
+};
+int build_plan(const p2gpu_build_params *bp, const p2gpu_gate_decl *gates, uint32_t num_gates, bool have_row_constants, BuildPlan &pl);
+int build_prefix(const BuildPlan &pl, const p2gpu_build_params *bp, const p2gpu_gate_decl *gates, uint32_t hasher, uint8_t *out);
 // the verifier's plonk identity at zeta on the opened values (verify.hip); also the prover's self-check
 bool plonk_identity_holds(const p2gpu_circuit *c, const std::vector<ext_t> &op, const gl_t *betas, const gl_t *gammas,
                           const gl_t *alphas, ext_t zeta, const gl_t pih[4]);

@@ -4,6 +4,7 @@
 // hashing, commitment, field self-test).  The proof itself is prover.hip, the commitment operators commit.hip, the exchanges of a
 // sharded proof transport.hip.
 #include "prover_internal.hpp"
+#include <functional>
 
 using namespace p2;
 
@@ -201,6 +202,14 @@ int p2gpu_device_info(char *name_out, size_t name_cap, int *cu_count, size_t *hb
 static int shard_layout(p2gpu_circuit *c, int rank, int world);
 static int shard_args_ok(p2gpu_circuit *c, int rank, int world);
 static int circuit_create_one(const uint8_t *blob, size_t len, int device, p2gpu_circuit **out_c);
+// where the constants and sigma tables of a new handle come from: a circuit blob in host memory (p2gpu_circuit_create),
+// or the build on the device from gate rows and copy pairs (p2gpu_circuit_build, build.hip)
+struct TableSource {
+  const gl_t *constants = nullptr, *sigmas = nullptr;  // host, [NC][n] and [R][n]
+  const BuildInputs *build = nullptr;
+  bool truncated = false;  // the blob ends before its tables do
+};
+static int circuit_finish(p2gpu_circuit *c, const TableSource &src, const uint8_t *cap_in, p2gpu_circuit **out_c);
 
 
 // A plain (un-sharded) handle on ONE device of the p2gpu_init list, whatever the length of that list: with several ids
@@ -218,10 +227,9 @@ int p2gpu_circuit_create_on(const uint8_t *blob, size_t len, int device_id, p2gp
   return rc;
 } P2GPU_CATCH
 
-int p2gpu_circuit_create(const uint8_t *blob, size_t len, p2gpu_circuit **out_c) try {
-  if (!blob || !out_c) return P2GPU_E_ARG;
-  if (int rc = ensure_device()) return rc;
-  if (g_devices.size() <= 1) return circuit_create_one(blob, len, g_device, out_c);
+// one(device, &handle) makes a full handle on one device: a plain handle after p2gpu_init with one id, a device group otherwise
+static int circuit_make(const std::function<int(int, p2gpu_circuit **)> &one, p2gpu_circuit **out_c) {
+  if (g_devices.size() <= 1) return one(g_device, out_c);
   // a device group: one full handle per device (each commits constants / sigmas for itself: 5 ms), then the coset
   // layout of rank q of n on each and the shared rendezvous
   const int n = (int)g_devices.size();
@@ -232,7 +240,7 @@ int p2gpu_circuit_create(const uint8_t *blob, size_t len, p2gpu_circuit **out_c)
     std::vector<std::thread> th;
     for (int q = 0; q < n; q++)
       th.emplace_back([&, q] {
-        rcs[q] = circuit_create_one(blob, len, g_devices[q], &hs[q]);
+        rcs[q] = one(g_devices[q], &hs[q]);
         if (rcs[q]) errs[q] = p2gpu_last_error();
       });
     for (auto &t : th) t.join();
@@ -281,6 +289,107 @@ int p2gpu_circuit_create(const uint8_t *blob, size_t len, p2gpu_circuit **out_c)
   for (int q = 1; q < n; q++) hs[0]->group.push_back(hs[q]);
   *out_c = hs[0];
   return P2GPU_OK;
+}
+
+int p2gpu_circuit_create(const uint8_t *blob, size_t len, p2gpu_circuit **out_c) try {
+  if (!blob || !out_c) return P2GPU_E_ARG;
+  if (int rc = ensure_device()) return rc;
+  return circuit_make([&](int device, p2gpu_circuit **h) { return circuit_create_one(blob, len, device, h); }, out_c);
+} P2GPU_CATCH
+
+// ---- build() on the device: gate rows + copy pairs -> handle (the tables come from build.hip, not from a blob) ----
+namespace {
+struct BuildCall {
+  const p2gpu_build_params *bp;
+  const p2gpu_gate_decl *gates;
+  uint32_t num_gates;
+  BuildInputs in;
+  std::vector<uint8_t> prefix;
+};
+// the checks that need no device, in p2gpu_build_blob's order, and the blob prefix
+int build_call_prepare(BuildCall &b, const p2gpu_build_params *bp, const p2gpu_gate_decl *gates, uint32_t num_gates, const uint32_t *row_gate,
+                       const uint64_t *row_constants, const uint32_t *copies, size_t num_copies, uint32_t hasher, p2gpu_circuit **out_c) {
+  if (out_c) *out_c = nullptr;
+  if (!bp || !gates || !row_gate || !out_c || (num_copies && !copies)) return P2GPU_E_ARG;
+  if (hasher > 1) { set_err("unsupported hasher (0 = KeccakHash<25>, 1 = PoseidonHash)"); return P2GPU_E_ARG; }
+  BuildPlan pl;
+  if (int rc = build_plan(bp, gates, num_gates, row_constants != nullptr, pl)) return rc;
+  b.prefix.resize(pl.prefix_len);
+  if (int rc = build_prefix(pl, bp, gates, hasher, b.prefix.data())) return rc;
+  b.bp = bp; b.gates = gates; b.num_gates = num_gates;
+  b.in = BuildInputs{row_gate, row_constants, copies, num_copies};
+  return P2GPU_OK;
+}
+int circuit_build_one(const BuildCall &b, int device, p2gpu_circuit **out_c) {
+  p2gpu_circuit *c = new p2gpu_circuit();
+  size_t off = 0;
+  const uint8_t *cap_in = nullptr;
+  if (int rc = circuit_parse(b.prefix.data(), b.prefix.size(), c, &off, &cap_in)) {
+    delete c;
+    return rc == P2GPU_E_BLOB ? P2GPU_E_ARG : rc;  // (no blob here: the parameters themselves are what circuit_parse refused)
+  }
+  c->device = device;
+  c->blob_prefix = b.prefix;
+  TableSource src;
+  src.build = &b.in;
+  return circuit_finish(c, src, nullptr, out_c);
+}
+}  // namespace
+
+int p2gpu_circuit_build_on(const p2gpu_build_params *bp, const p2gpu_gate_decl *gates, uint32_t num_gates, const uint32_t *row_gate,
+                           const uint64_t *row_constants, const uint32_t *copies, size_t num_copies, uint32_t hasher, int device_id,
+                           p2gpu_circuit **out_c) try {
+  BuildCall b;
+  if (int rc = build_call_prepare(b, bp, gates, num_gates, row_gate, row_constants, copies, num_copies, hasher, out_c)) return rc;
+  if (int rc = ensure_device()) return rc;
+  if (std::find(g_devices.begin(), g_devices.end(), device_id) == g_devices.end()) {
+    set_err("p2gpu_circuit_build_on: device %d is not in the list given to p2gpu_init", device_id);
+    return P2GPU_E_ARG;
+  }
+  const int rc = circuit_build_one(b, device_id, out_c);
+  (void)hipSetDevice(g_device);
+  return rc;
+} P2GPU_CATCH
+
+int p2gpu_circuit_build(const p2gpu_build_params *bp, const p2gpu_gate_decl *gates, uint32_t num_gates, const uint32_t *row_gate,
+                        const uint64_t *row_constants, const uint32_t *copies, size_t num_copies, uint32_t hasher, p2gpu_circuit **out_c) try {
+  BuildCall b;
+  if (int rc = build_call_prepare(b, bp, gates, num_gates, row_gate, row_constants, copies, num_copies, hasher, out_c)) return rc;
+  if (int rc = ensure_device()) return rc;
+  return circuit_make([&](int device, p2gpu_circuit **h) { return circuit_build_one(b, device, h); }, out_c);
+} P2GPU_CATCH
+
+// The circuit blob of a prover handle: the prefix it was made from, then the constants (selector columns from row -> gate, the
+// gate constants) and the sigma table as they sit in device memory.
+int p2gpu_circuit_export_blob(const p2gpu_circuit *cc, uint8_t *out, size_t *len) try {
+  if (!cc || !len) return P2GPU_E_ARG;
+  if (int rc = prover_handle(cc)) return rc;
+  p2gpu_circuit *c = const_cast<p2gpu_circuit *>(cc);
+  const size_t n = c->n, nsel = c->num_selectors, ngc = c->NC - c->num_selectors;
+  const size_t need = c->blob_prefix.size() + 8 * ((size_t)c->NC + c->R) * n;
+  if (!out || *len < need) {
+    const bool probe = out == nullptr;
+    *len = need;
+    if (probe) return P2GPU_OK;
+    set_err("blob buffer too small: need %zu bytes", need);
+    return P2GPU_E_BUFFER;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  Scratch S;
+  gl_t *sel = S.alloc<gl_t>(nsel * n);
+  if (!sel) { set_err("hipMalloc failed"); (void)hipSetDevice(g_device); return P2GPU_E_DEVICE; }
+  build_selector_columns(c->stream, c, sel);
+  memcpy(out, c->blob_prefix.data(), c->blob_prefix.size());
+  uint8_t *q = out + c->blob_prefix.size();
+  hipError_t e = hipMemcpyAsync(q, sel, 8 * nsel * n, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && ngc) e = hipMemcpyAsync(q + 8 * nsel * n, c->d_gconsts.p, 8 * ngc * n, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(q + 8 * (size_t)c->NC * n, c->d_sigmas.p, 8 * (size_t)c->R * n, hipMemcpyDeviceToHost, c->stream);
+  const hipError_t e2 = hipStreamSynchronize(c->stream);
+  (void)hipSetDevice(g_device);
+  HIP_TRY(e);
+  HIP_TRY(e2);
+  *len = need;
+  return P2GPU_OK;
 } P2GPU_CATCH
 
 static int circuit_create_one(const uint8_t *blob, size_t len, int device, p2gpu_circuit **out_c) try {
@@ -292,6 +401,16 @@ static int circuit_create_one(const uint8_t *blob, size_t len, int device, p2gpu
     return rc;
   }
   c->device = device;
+  c->blob_prefix.assign(blob, blob + off);
+  TableSource src;
+  src.truncated = len < off + 8 * ((size_t)c->NC * c->n + (size_t)c->R * c->n);  // (reported where it always was: after the gate groups)
+  src.constants = (const gl_t *)(blob + off);
+  src.sigmas = src.constants + (size_t)c->NC * c->n;
+  return circuit_finish(c, src, cap_in, out_c);
+} P2GPU_CATCH
+
+// Takes ownership of c (parsed, device chosen): schedules the gate groups, makes the device state, commits constants and sigmas.
+static int circuit_finish(p2gpu_circuit *c, const TableSource &src, const uint8_t *cap_in, p2gpu_circuit **out_c) try {
   auto fail = [&](int rc, const char *msg) {
     set_err("%s", msg);
     circuit_release(c);
@@ -359,11 +478,9 @@ static int circuit_create_one(const uint8_t *blob, size_t len, int device, p2gpu
     }
   }
   const size_t n = c->n;
-  if (len < off + 8 * ((size_t)c->NC * n + (size_t)c->R * n)) return fail(P2GPU_E_BLOB, "blob truncated (tables)");
+  if (src.truncated) return fail(P2GPU_E_BLOB, "blob truncated (tables)");
   const gl_t *k_is = c->k_is.data();
-  const gl_t *constants = (const gl_t *)(blob + off);
-  off += 8 * (size_t)c->NC * n;
-  const gl_t *sigmas = (const gl_t *)(blob + off);
+  const gl_t *constants = src.constants, *sigmas = src.sigmas;
 
   // ---- device state ----
   auto H = [&](hipError_t e, const char *what) -> int {
@@ -446,37 +563,50 @@ static int circuit_create_one(const uint8_t *blob, size_t len, int device, p2gpu
   }
   mark("root tables + ntt plans");
   CK(hipMemcpyAsync(c->d_kis.p, k_is, 8 * (size_t)c->R, hipMemcpyHostToDevice, st), "copy kis");
-  CK(hipMemcpyAsync(c->d_sigmas.p, sigmas, 8 * (size_t)c->R * n, hipMemcpyHostToDevice, st), "copy sigmas");
+  if (!src.build) CK(hipMemcpyAsync(c->d_sigmas.p, sigmas, 8 * (size_t)c->R * n, hipMemcpyHostToDevice, st), "copy sigmas");
   if (c->num_gates)
     CK(hipMemcpyAsync(c->d_gates.p, c->gates.data(), sizeof(GateDesc) * c->num_gates, hipMemcpyHostToDevice, st), "copy gates");
   {
-    // row -> gate (the one selector column that is not UNUSED holds the index) and the gate
-    // constants, for the row-local witness generators (p2gpu_fill_witness)
-    std::vector<uint8_t> rg(n, 0);
-    for (size_t row = 0; row < n; row++) {
-      uint32_t gi = 0;
-      for (uint32_t s = 0; s < c->num_selectors; s++) {
-        gl_t v = constants[(size_t)s * n + row];
-        if (c->num_selectors == 1 || v != 0xFFFFFFFFULL) gi = (uint32_t)v;
-      }
-      if (gi >= c->num_gates) return fail(P2GPU_E_BLOB, "selector column holds an unknown gate index");
-      rg[row] = (uint8_t)gi;
-      if (c->sparse_row == UINT32_MAX && c->gates[gi].kind == G_PUBLIC_INPUT) c->sparse_row = (uint32_t)row;
-    }
-    // the special rows of the column classification: the PublicInputGate row first, then the PoseidonGate rows
-    c->sparse_rows = SparseRows();
-    if (c->sparse_row != UINT32_MAX) {
-      c->sparse_rows.row[c->sparse_rows.count++] = c->sparse_row;
-      for (size_t row = 0; row < n && c->sparse_rows.count < MAX_SPARSE_ROWS; row++)
-        if (c->gates[rg[row]].kind == G_POSEIDON) c->sparse_rows.row[c->sparse_rows.count++] = (uint32_t)row;
-    }
     const uint32_t ngc = c->NC - c->num_selectors;
     CK(c->d_row_gate.alloc(n), "alloc row_gate");
     CK(c->d_gconsts.alloc((size_t)(ngc ? ngc : 1) * n), "alloc gconsts");
     CK(c->d_prc.alloc(360), "alloc prc");
-    CK(hipMemcpy(c->d_row_gate.p, rg.data(), n, hipMemcpyHostToDevice), "copy row_gate");
-    if (ngc)
-      CK(hipMemcpy(c->d_gconsts.p, constants + (size_t)c->num_selectors * n, 8 * (size_t)ngc * n, hipMemcpyHostToDevice), "copy gconsts");
+    if (src.build) {
+      // build() on the device: row -> gate as given, gate constants, special rows and sigma from kernels (build.hip); its
+      // scratch is gone again before the per-proof buffers below are allocated
+      struct MarkCtx { decltype(mark) *m; } mc{&mark};
+      if (int rc = build_device_tables(c, *src.build, [](void *ctx, const char *label) { (*((MarkCtx *)ctx)->m)(label); }, &mc)) {
+        std::string keep = last_error_copy();
+        circuit_release(c);
+        delete c;
+        last_error_restore(keep);
+        return rc;
+      }
+    } else {
+      // row -> gate (the one selector column that is not UNUSED holds the index) and the gate
+      // constants, for the row-local witness generators (p2gpu_fill_witness)
+      std::vector<uint8_t> rg(n, 0);
+      for (size_t row = 0; row < n; row++) {
+        uint32_t gi = 0;
+        for (uint32_t s = 0; s < c->num_selectors; s++) {
+          gl_t v = constants[(size_t)s * n + row];
+          if (c->num_selectors == 1 || v != 0xFFFFFFFFULL) gi = (uint32_t)v;
+        }
+        if (gi >= c->num_gates) return fail(P2GPU_E_BLOB, "selector column holds an unknown gate index");
+        rg[row] = (uint8_t)gi;
+        if (c->sparse_row == UINT32_MAX && c->gates[gi].kind == G_PUBLIC_INPUT) c->sparse_row = (uint32_t)row;
+      }
+      // the special rows of the column classification: the PublicInputGate row first, then the PoseidonGate rows
+      c->sparse_rows = SparseRows();
+      if (c->sparse_row != UINT32_MAX) {
+        c->sparse_rows.row[c->sparse_rows.count++] = c->sparse_row;
+        for (size_t row = 0; row < n && c->sparse_rows.count < MAX_SPARSE_ROWS; row++)
+          if (c->gates[rg[row]].kind == G_POSEIDON) c->sparse_rows.row[c->sparse_rows.count++] = (uint32_t)row;
+      }
+      CK(hipMemcpy(c->d_row_gate.p, rg.data(), n, hipMemcpyHostToDevice), "copy row_gate");
+      if (ngc)
+        CK(hipMemcpy(c->d_gconsts.p, constants + (size_t)c->num_selectors * n, 8 * (size_t)ngc * n, hipMemcpyHostToDevice), "copy gconsts");
+    }
     CK(hipMemcpy(c->d_prc.p, c->poseidon_rc, sizeof c->poseidon_rc, hipMemcpyHostToDevice), "copy prc");
     {
       gl_t hrc[360];
@@ -581,7 +711,14 @@ static int circuit_create_one(const uint8_t *blob, size_t len, int device, p2gpu
   {
     // stage values [constants | sigmas] in the wires buffer region of the cs LDE (reuse cs.lde as scratch)
     gl_t *stage = c->cs.lde.p;
-    CK(hipMemcpyAsync(stage, constants, 8 * (size_t)c->NC * n, hipMemcpyHostToDevice, st), "copy constants");
+    if (src.build) {
+      build_selector_columns(st, c, stage);
+      if (c->NC > c->num_selectors)
+        CK(hipMemcpyAsync(stage + (size_t)c->num_selectors * n, c->d_gconsts.p, 8 * (size_t)(c->NC - c->num_selectors) * n, hipMemcpyDeviceToDevice, st),
+           "copy constants");
+    } else {
+      CK(hipMemcpyAsync(stage, constants, 8 * (size_t)c->NC * n, hipMemcpyHostToDevice, st), "copy constants");
+    }
     CK(hipMemcpyAsync(stage + (size_t)c->NC * n, c->d_sigmas.p, 8 * (size_t)c->R * n, hipMemcpyDeviceToDevice, st), "copy sigmas");
     {
       gl_t ninv = gl_inv((gl_t)n);

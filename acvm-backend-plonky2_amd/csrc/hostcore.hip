@@ -237,6 +237,89 @@ int circuit_parse(const uint8_t *blob, size_t len, p2gpu_circuit *c, size_t *off
   *off_out = off;
   return P2GPU_OK;
 }
+
+// ---- N2, the part both build paths share (p2gpu_build_blob below; p2gpu_circuit_build, handle.hip / build.hip) ----
+// Parameter checks, selector groups (plonky2 gates/selectors.rs selector_polynomials), constant-column count and FRI
+// arities of ConstantArityBits(4, 5): everything the size of the blob depends on.
+int build_plan(const p2gpu_build_params *bp, const p2gpu_gate_decl *gates, uint32_t num_gates, bool have_row_constants, BuildPlan &pl) {
+  const uint32_t d = bp->degree_bits, W = bp->num_wires, R = bp->num_routed_wires, QF = bp->quotient_degree_factor;
+  if (d < 1 || d > 24 || num_gates == 0 || num_gates > (uint32_t)MAX_GATES || R == 0 || R > (uint32_t)MAX_ROUTED || W < R || W > 4096 ||
+      QF == 0 || bp->rate_bits < 1 || bp->rate_bits > 3 || (1u << bp->rate_bits) != QF || bp->num_challenges < 1 ||
+      bp->num_challenges > 2) {
+    set_err("p2gpu_build_blob: unsupported circuit parameters");
+    return P2GPU_E_ARG;
+  }
+  pl.n = (size_t)1 << d;
+  pl.R = R;
+  for (uint32_t i = 1; i < num_gates; i++)
+    if (gates[i].degree < gates[i - 1].degree) {
+      set_err("p2gpu_build_blob: gates must come sorted by (degree, id) as in CommonCircuitData.gates");
+      return P2GPU_E_ARG;
+    }
+  // selector groups
+  const uint32_t max_degree = QF + 1;
+  std::vector<uint32_t> &gstart = pl.gstart, &gend = pl.gend, &gsel = pl.gsel;
+  gstart.assign(num_gates, 0); gend.assign(num_gates, 0); gsel.assign(num_gates, 0);
+  uint32_t num_selectors = 0;
+  if (gates[num_gates - 1].degree + num_gates - 1 <= max_degree) {
+    num_selectors = 1;
+    for (uint32_t i = 0; i < num_gates; i++) { gstart[i] = 0; gend[i] = num_gates; gsel[i] = 0; }
+  } else {
+    uint32_t start = 0;
+    while (start < num_gates) {
+      uint32_t size = 0;
+      while (start + size < num_gates && size + gates[start + size].degree < max_degree) size++;
+      if (size == 0) { set_err("p2gpu_build_blob: gate degree %u does not fit max_degree %u", gates[start].degree, max_degree); return P2GPU_E_ARG; }
+      for (uint32_t i = start; i < start + size; i++) { gstart[i] = start; gend[i] = start + size; gsel[i] = num_selectors; }
+      start += size;
+      num_selectors++;
+    }
+  }
+  uint32_t ngc = 0;
+  for (uint32_t i = 0; i < num_gates; i++) ngc = std::max(ngc, gates[i].num_constants);
+  if (ngc && !have_row_constants) return P2GPU_E_ARG;
+  pl.num_selectors = num_selectors;
+  pl.ngc = ngc;
+  pl.NC = num_selectors + ngc;
+  pl.arity.clear();
+  for (uint32_t db = d; db > 5 && db + bp->rate_bits - 4 >= bp->cap_height; db -= 4) pl.arity.push_back(4);
+  if (pl.arity.size() > 8) return P2GPU_E_ARG;
+  pl.prefix_len = 256 + 48 * (size_t)num_gates + 8 * (size_t)R;
+  return P2GPU_OK;
+}
+
+// The blob prefix: header (hasher in word 22, flags 0), gate table with the selector groups, k_is[j] = g^j.
+int build_prefix(const BuildPlan &pl, const p2gpu_build_params *bp, const p2gpu_gate_decl *gates, uint32_t hasher, uint8_t *out) {
+  const uint32_t d = bp->degree_bits, W = bp->num_wires, R = pl.R, QF = bp->quotient_degree_factor;
+  const uint32_t num_gates = (uint32_t)pl.gsel.size();
+  // header + gate table
+  uint32_t hd[64];
+  memset(hd, 0, sizeof hd);
+  hd[0] = 0x43473250u; hd[1] = 1; hd[2] = d; hd[3] = W; hd[4] = R; hd[5] = pl.NC; hd[6] = pl.num_selectors; hd[7] = bp->num_challenges;
+  hd[8] = QF; hd[9] = bp->rate_bits; hd[10] = bp->cap_height; hd[11] = bp->proof_of_work_bits; hd[12] = bp->num_query_rounds;
+  hd[13] = (uint32_t)pl.arity.size();
+  for (size_t i = 0; i < pl.arity.size(); i++) hd[14 + i] = pl.arity[i];
+  hd[22] = hasher; hd[23] = num_gates; hd[24] = bp->num_public_inputs; hd[25] = 0; hd[26] = (R + QF - 1) / QF - 1;
+  memcpy(out, hd, sizeof hd);
+  size_t off = sizeof hd;
+  for (uint32_t i = 0; i < num_gates; i++) {
+    uint64_t wu = 0;
+    uint32_t cu = 0;
+    if (gates[i].kind >= G_KIND_COUNT) { set_err("unsupported gate kind in blob"); return P2GPU_E_ARG; }
+    if (const char *why = gate_validate(gates[i].kind, gates[i].p, W, pl.ngc, &wu, &cu)) { set_err("%s", why); return P2GPU_E_ARG; }
+    const uint32_t gw[12] = {gates[i].kind, gates[i].p[0], gates[i].p[1], gates[i].p[2], gates[i].p[3], pl.gsel[i], pl.gstart[i], pl.gend[i],
+                             gate_num_constraints(gates[i].kind, gates[i].p), gates[i].degree, gates[i].num_constants, 0};
+    memcpy(out + off, gw, sizeof gw);
+    off += sizeof gw;
+  }
+  gl_t k = 1;
+  for (uint32_t j = 0; j < R; j++) {
+    memcpy(out + off, &k, 8);
+    off += 8;
+    k = gl_mul(k, GL_GEN);
+  }
+  return P2GPU_OK;
+}
 }  // namespace p2
 
 extern "C" {
@@ -270,45 +353,12 @@ int p2gpu_build_blob(const p2gpu_build_params *bp, const p2gpu_gate_decl *gates,
                      const uint64_t *row_constants, const uint32_t *copies, size_t num_copies, uint8_t *blob_out,
                      size_t *blob_len) try {
   if (!bp || !gates || !row_gate || !blob_len || (num_copies && !copies)) return P2GPU_E_ARG;
-  const uint32_t d = bp->degree_bits, W = bp->num_wires, R = bp->num_routed_wires, QF = bp->quotient_degree_factor;
-  if (d < 1 || d > 24 || num_gates == 0 || num_gates > (uint32_t)MAX_GATES || R == 0 || R > (uint32_t)MAX_ROUTED || W < R || W > 4096 ||
-      QF == 0 || bp->rate_bits < 1 || bp->rate_bits > 3 || (1u << bp->rate_bits) != QF || bp->num_challenges < 1 ||
-      bp->num_challenges > 2) {
-    set_err("p2gpu_build_blob: unsupported circuit parameters");
-    return P2GPU_E_ARG;
-  }
-  const size_t n = (size_t)1 << d;
-  for (uint32_t i = 1; i < num_gates; i++)
-    if (gates[i].degree < gates[i - 1].degree) {
-      set_err("p2gpu_build_blob: gates must come sorted by (degree, id) as in CommonCircuitData.gates");
-      return P2GPU_E_ARG;
-    }
-  // selector groups
-  const uint32_t max_degree = QF + 1;
-  std::vector<uint32_t> gstart(num_gates), gend(num_gates), gsel(num_gates);
-  uint32_t num_selectors = 0;
-  if (gates[num_gates - 1].degree + num_gates - 1 <= max_degree) {
-    num_selectors = 1;
-    for (uint32_t i = 0; i < num_gates; i++) { gstart[i] = 0; gend[i] = num_gates; gsel[i] = 0; }
-  } else {
-    uint32_t start = 0;
-    while (start < num_gates) {
-      uint32_t size = 0;
-      while (start + size < num_gates && size + gates[start + size].degree < max_degree) size++;
-      if (size == 0) { set_err("p2gpu_build_blob: gate degree %u does not fit max_degree %u", gates[start].degree, max_degree); return P2GPU_E_ARG; }
-      for (uint32_t i = start; i < start + size; i++) { gstart[i] = start; gend[i] = start + size; gsel[i] = num_selectors; }
-      start += size;
-      num_selectors++;
-    }
-  }
-  uint32_t ngc = 0;
-  for (uint32_t i = 0; i < num_gates; i++) ngc = std::max(ngc, gates[i].num_constants);
-  if (ngc && !row_constants) return P2GPU_E_ARG;
-  const uint32_t NC = num_selectors + ngc;
-  std::vector<uint32_t> arity;
-  for (uint32_t db = d; db > 5 && db + bp->rate_bits - 4 >= bp->cap_height; db -= 4) arity.push_back(4);
-  if (arity.size() > 8) return P2GPU_E_ARG;
-  const size_t need = 256 + 48 * (size_t)num_gates + 8 * ((size_t)R + (size_t)NC * n + (size_t)R * n);
+  BuildPlan pl;
+  if (int rc = build_plan(bp, gates, num_gates, row_constants != nullptr, pl)) return rc;
+  const uint32_t d = bp->degree_bits, R = pl.R, NC = pl.NC, num_selectors = pl.num_selectors, ngc = pl.ngc;
+  const size_t n = pl.n;
+  const std::vector<uint32_t> &gsel = pl.gsel;
+  const size_t need = pl.prefix_len + 8 * ((size_t)NC * n + (size_t)R * n);
   if (!blob_out || *blob_len < need) {
     const bool probe = blob_out == nullptr;
     *blob_len = need;
@@ -316,37 +366,16 @@ int p2gpu_build_blob(const p2gpu_build_params *bp, const p2gpu_gate_decl *gates,
     set_err("blob buffer too small: need %zu bytes", need);
     return P2GPU_E_BUFFER;
   }
-  // header + gate table
-  uint32_t hd[64];
-  memset(hd, 0, sizeof hd);
-  hd[0] = 0x43473250u; hd[1] = 1; hd[2] = d; hd[3] = W; hd[4] = R; hd[5] = NC; hd[6] = num_selectors; hd[7] = bp->num_challenges;
-  hd[8] = QF; hd[9] = bp->rate_bits; hd[10] = bp->cap_height; hd[11] = bp->proof_of_work_bits; hd[12] = bp->num_query_rounds;
-  hd[13] = (uint32_t)arity.size();
-  for (size_t i = 0; i < arity.size(); i++) hd[14 + i] = arity[i];
-  hd[22] = 0; hd[23] = num_gates; hd[24] = bp->num_public_inputs; hd[25] = 0; hd[26] = (R + QF - 1) / QF - 1;
-  memcpy(blob_out, hd, sizeof hd);
-  size_t off = sizeof hd;
-  for (uint32_t i = 0; i < num_gates; i++) {
-    uint64_t wu = 0;
-    uint32_t cu = 0;
-    if (gates[i].kind >= G_KIND_COUNT) { set_err("unsupported gate kind in blob"); return P2GPU_E_ARG; }
-    if (const char *why = gate_validate(gates[i].kind, gates[i].p, W, ngc, &wu, &cu)) { set_err("%s", why); return P2GPU_E_ARG; }
-    const uint32_t gw[12] = {gates[i].kind, gates[i].p[0], gates[i].p[1], gates[i].p[2], gates[i].p[3], gsel[i], gstart[i], gend[i],
-                             gate_num_constraints(gates[i].kind, gates[i].p), gates[i].degree, gates[i].num_constants, 0};
-    memcpy(blob_out + off, gw, sizeof gw);
-    off += sizeof gw;
-  }
+  if (int rc = build_prefix(pl, bp, gates, 0, blob_out)) return rc;
+  size_t off = pl.prefix_len;
   // k_is and the subgroup
-  std::vector<gl_t> k_is(R), sub(n);
-  k_is[0] = 1;
-  for (uint32_t j = 1; j < R; j++) k_is[j] = gl_mul(k_is[j - 1], GL_GEN);
+  const gl_t *k_is = (const gl_t *)(blob_out + off - 8 * (size_t)R);  // (8-byte aligned: 256 + 48 g)
+  std::vector<gl_t> sub(n);
   {
     const gl_t wn = gl_root(d);
     sub[0] = 1;
     for (size_t i = 1; i < n; i++) sub[i] = gl_mul(sub[i - 1], wn);
   }
-  memcpy(blob_out + off, k_is.data(), 8 * (size_t)R);
-  off += 8 * (size_t)R;
   // constants: selector columns, then the gate constants as given
   gl_t *consts = (gl_t *)(blob_out + off);  // (8-byte aligned: 256 + 48 g + 8 R)
   for (size_t r = 0; r < n; r++) {

@@ -77,6 +77,19 @@ int batch_commit_from_coeffs(p2gpu_circuit *c, Batch &b);
 // ---- upload.hip ----
 int prove_host(p2gpu_circuit *c, const uint64_t *wires, uint32_t ncols, const uint64_t *tail, uint32_t row, const uint64_t *pis,
                uint32_t n_pi, uint8_t *proof_out, size_t *proof_len, p2gpu_timings *tm);
+// ---- build.hip: build() on the device (p2gpu_circuit_build) ----
+// the caller's arrays, still in host memory (validated on the device before anything indexes with them)
+struct BuildInputs {
+  const uint32_t *row_gate;        // [n]
+  const uint64_t *row_constants;   // [NC - num_selectors][n], nullptr when no gate has constants
+  const uint32_t *copies;          // [num_copies][4]
+  size_t num_copies;
+};
+// Fills d_row_gate, d_gconsts, d_sigmas and the special rows of a handle whose root tables, k_is and gate table are
+// enqueued on c->stream; every scratch buffer is gone when it returns.  mark: the P2GPU_TRACE marks of circuit creation.
+int build_device_tables(p2gpu_circuit *c, const BuildInputs &in, void (*mark)(void *, const char *), void *mark_ctx);
+// consts [num_selectors][n] <- the selector columns of d_row_gate (row of a gate outside the column's group: 2^32 - 1)
+void build_selector_columns(hipStream_t st, const p2gpu_circuit *c, gl_t *consts);
 // ---- handle.hip ----
 int ensure_device();
 extern int g_device;

@@ -114,6 +114,9 @@ def load_library():
     lib.p2gpu_device_info.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(sz)]
     lib.p2gpu_peer_access.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int]
     lib.p2gpu_circuit_create_on.argtypes = [u8p, sz, ctypes.c_int, ctypes.POINTER(vp)]
+    lib.p2gpu_circuit_build.argtypes = [vp, vp, ctypes.c_uint32, vp, vp, vp, sz, ctypes.c_uint32, ctypes.POINTER(vp)]
+    lib.p2gpu_circuit_build_on.argtypes = [vp, vp, ctypes.c_uint32, vp, vp, vp, sz, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(vp)]
+    lib.p2gpu_circuit_export_blob.argtypes = [vp, u8p, ctypes.POINTER(sz)]
     lib.p2gpu_peer_access.restype = ctypes.c_int
     lib.p2gpu_host_alloc.argtypes = [sz]
     lib.p2gpu_host_alloc.restype = vp
@@ -251,6 +254,42 @@ class CircuitData:
     @classmethod
     def from_blob(cls, blob):
         return cls(blob)
+
+    @classmethod
+    def build(cls, degree_bits, gates, row_gate, row_constants, copies, num_public_inputs=0, num_wires=234, num_routed_wires=80,
+              num_challenges=2, quotient_degree_factor=8, rate_bits=3, cap_height=4, proof_of_work_bits=16, num_query_rounds=28,
+              hasher=0, device=None):
+        """``builder.build::<C>()`` on the device (``p2gpu_circuit_build``): the arguments of ``build_blob`` plus the hasher
+        (0 KeccakHash<25>, 1 PoseidonHash), straight to a prover handle -- selector columns, row -> gate and the sigma
+        polynomials are made by kernels from the uploaded gate rows and copy pairs, no blob passes through host memory.
+        The handle is the one ``CircuitData(build_blob(...))`` gives; ``to_blob()`` reads the blob back to cache it.
+        device: as for the constructor."""
+        lib = load_library()
+        bp, gd, rg, rc, cp = _build_args(degree_bits, gates, row_gate, row_constants, copies, num_public_inputs, num_wires, num_routed_wires,
+                                         num_challenges, quotient_degree_factor, rate_bits, cap_height, proof_of_work_bits, num_query_rounds)
+        self = cls.__new__(cls)
+        self._lib = lib
+        self._blob = None
+        self.degree_bits, self.num_wires, self.num_routed_wires = int(degree_bits), int(num_wires), int(num_routed_wires)
+        self.rate_bits, self.cap_height, self.num_public_inputs = int(rate_bits), int(cap_height), int(num_public_inputs)
+        self._h = ctypes.c_void_p()
+        args = [ctypes.byref(bp), gd, len(gates), rg.ctypes.data, rc.ctypes.data if rc.size else None, cp.ctypes.data if cp.size else None,
+                len(cp), int(hasher)]
+        if device is None:
+            _check(lib.p2gpu_circuit_build(*args, ctypes.byref(self._h)))
+        else:
+            _check(lib.p2gpu_circuit_build_on(*args, int(device), ctypes.byref(self._h)))
+        self._bound = lib.p2gpu_proof_size_bound(self._h)
+        return self
+
+    def to_blob(self):
+        """The circuit blob of this handle, read back from the device (``p2gpu_circuit_export_blob``): for a handle from
+        ``build`` exactly what ``build_blob`` returns for the same arguments, with the hasher in header word 22."""
+        ln = ctypes.c_size_t(0)
+        _check(self._lib.p2gpu_circuit_export_blob(self._h, None, ctypes.byref(ln)))
+        out = np.zeros(ln.value, dtype=np.uint8)
+        _check(self._lib.p2gpu_circuit_export_blob(self._h, out.ctypes.data, ctypes.byref(ln)))
+        return out[:ln.value]
 
     @property
     def degree(self):
@@ -577,16 +616,9 @@ class _GateDecl(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_uint32), ("p", ctypes.c_uint32 * 4), ("degree", ctypes.c_uint32), ("num_constants", ctypes.c_uint32)]
 
 
-def build_blob(degree_bits, gates, row_gate, row_constants, copies, num_public_inputs=0, num_wires=234, num_routed_wires=80,
-               num_challenges=2, quotient_degree_factor=8, rate_bits=3, cap_height=4, proof_of_work_bits=16, num_query_rounds=28):
-    """``builder.build::<C>()`` minus the GPU part (circuit_translation/mod.rs:80-82): selector columns and groups,
-    sigma polynomials from the copy constraints, k_is, FRI arities -> circuit blob (p2gpu_build_blob).
-    gates: [(kind, (p0, p1, p2, p3), degree, num_constants)] sorted by (degree, id) like CommonCircuitData.gates;
-    row_gate[n]; row_constants[max num_constants][n]; copies[m][4] = (row_a, col_a, row_b, col_b).
-    ``CircuitData(build_blob(...))`` then commits constants and sigmas on the GPU and derives the digest."""
-    lib = load_library()
-    lib.p2gpu_build_blob.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                     ctypes.c_size_t, ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t)]
+def _build_args(degree_bits, gates, row_gate, row_constants, copies, num_public_inputs, num_wires, num_routed_wires, num_challenges,
+                quotient_degree_factor, rate_bits, cap_height, proof_of_work_bits, num_query_rounds):
+    """The ctypes / numpy forms of what ``build_blob`` and ``CircuitData.build`` hand to the library."""
     bp = _BuildParams(degree_bits, num_wires, num_routed_wires, num_challenges, quotient_degree_factor, rate_bits, cap_height,
                       proof_of_work_bits, num_query_rounds, num_public_inputs)
     gd = (_GateDecl * len(gates))()
@@ -599,6 +631,21 @@ def build_blob(degree_bits, gates, row_gate, row_constants, copies, num_public_i
     cp = np.ascontiguousarray(copies, dtype=np.uint32).reshape(-1, 4)
     if rg.size != 1 << degree_bits:
         raise P2GpuError(-7, "row_gate must have 2^degree_bits entries")
+    return bp, gd, rg, rc, cp
+
+
+def build_blob(degree_bits, gates, row_gate, row_constants, copies, num_public_inputs=0, num_wires=234, num_routed_wires=80,
+               num_challenges=2, quotient_degree_factor=8, rate_bits=3, cap_height=4, proof_of_work_bits=16, num_query_rounds=28):
+    """``builder.build::<C>()`` minus the GPU part (circuit_translation/mod.rs:80-82): selector columns and groups,
+    sigma polynomials from the copy constraints, k_is, FRI arities -> circuit blob (p2gpu_build_blob).
+    gates: [(kind, (p0, p1, p2, p3), degree, num_constants)] sorted by (degree, id) like CommonCircuitData.gates;
+    row_gate[n]; row_constants[max num_constants][n]; copies[m][4] = (row_a, col_a, row_b, col_b).
+    ``CircuitData(build_blob(...))`` then commits constants and sigmas on the GPU and derives the digest."""
+    lib = load_library()
+    lib.p2gpu_build_blob.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_size_t, ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t)]
+    bp, gd, rg, rc, cp = _build_args(degree_bits, gates, row_gate, row_constants, copies, num_public_inputs, num_wires, num_routed_wires,
+                                     num_challenges, quotient_degree_factor, rate_bits, cap_height, proof_of_work_bits, num_query_rounds)
     ln = ctypes.c_size_t(0)
     args = [ctypes.byref(bp), gd, len(gates), rg.ctypes.data, rc.ctypes.data if rc.size else None, cp.ctypes.data if cp.size else None, len(cp)]
     _check(lib.p2gpu_build_blob(*args, None, ctypes.byref(ln)))

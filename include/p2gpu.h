@@ -178,6 +178,26 @@ int p2gpu_build_blob(const p2gpu_build_params *params, const p2gpu_gate_decl *ga
                      const uint64_t *row_constants, const uint32_t *copies, size_t num_copies, uint8_t *blob_out,
                      size_t *blob_len);
 
+/* build() on the device: the arguments of p2gpu_build_blob, plus the hasher of header word 22 (0 = KeccakHash<25>,
+ * 1 = PoseidonHash), to a prover handle.  The arrays are uploaded as they are; selector columns, row -> gate and the sigma
+ * polynomials (connected components of the copy pairs, then one cycle per class) are made by kernels, and no blob passes
+ * through host memory.  The handle equals, in every byte it can report or prove, p2gpu_circuit_create(p2gpu_build_blob(...)).
+ * Follows the rules of p2gpu_circuit_create: after p2gpu_init with several ids the result is a device group and each device
+ * runs the build itself; _on makes a plain handle on one named device.  A row_gate entry >= num_gates, a constant >= p or a
+ * copy pair outside [n] x [num_routed_wires] is found on the device before anything indexes with it: P2GPU_E_ARG, *out = NULL.
+ * Without a HIP device: P2GPU_E_DEVICE (argument errors that need no device are still P2GPU_E_ARG). */
+int p2gpu_circuit_build(const p2gpu_build_params *params, const p2gpu_gate_decl *gates, uint32_t num_gates, const uint32_t *row_gate,
+                        const uint64_t *row_constants, const uint32_t *copies, size_t num_copies, uint32_t hasher, p2gpu_circuit **out);
+int p2gpu_circuit_build_on(const p2gpu_build_params *params, const p2gpu_gate_decl *gates, uint32_t num_gates, const uint32_t *row_gate,
+                           const uint64_t *row_constants, const uint32_t *copies, size_t num_copies, uint32_t hasher, int device_id,
+                           p2gpu_circuit **out);
+/* The circuit blob of a prover handle, read back from the device (to cache a circuit that was built once).  out == NULL: only
+ * report the size in *len.  For a handle made by p2gpu_circuit_build: exactly the bytes p2gpu_build_blob writes (flags 0, the
+ * hasher in word 22).  For one made from a blob: that blob's prefix, the selector columns in their canonical form.
+ * The read-back runs on the handle's own stream: like every call on a handle it must not run while another thread proves
+ * on the same handle.  A device group answers from its first device (every device holds the same tables). */
+int p2gpu_circuit_export_blob(const p2gpu_circuit *c, uint8_t *out, size_t *len);
+
 /* ---- verification (host code only; needs no GPU) ------------------------------------------------
  * The counterpart of the reference's `verify` action (plonky2-backend/src/actions/verify_action.rs:11-17)
  * and of the `circuit_data.verify(proof)` assertion its tests end with (tests/factories/utils.rs:26-27),
