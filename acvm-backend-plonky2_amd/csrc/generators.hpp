@@ -1,0 +1,183 @@
+// generators.hpp -- the gates' witness generators, one body each, shared by the two kernels that run them:
+//   fill_witness_kernel (witness.hip)  one lane per row, straight on the wire matrix;
+//   genwit_walk_kernel  (genwit.hip)   one lane per scheduled op, on the per-proof class values.
+// A body sees its row through an accessor A:
+//   gl_t get(col)            the wire's value
+//   void set(col, gl_t v)    a derived wire (the level walk compares instead when the wire's class already has a value)
+//   gl_t lc(i)               gate constant i of the row
+//   void reject(col)         the inputs admit no value for `col` (fill_witness: nothing -- it derives, it does not judge)
+// Restated generators: witness.hip's header lists their sources.  gen_base_sum_join is the one le_sum adds
+// (gadgets/split_join.rs: the sum is computed from the bits), every other body is what fill_witness_kernel always ran.
+#pragma once
+#include "internal.hpp"
+#include "poseidon.hpp"
+
+namespace p2 {
+
+template <class A>
+__device__ __forceinline__ void gen_constant(A &a, const GateDesc &g) {
+  for (uint32_t i = 0; i < g.p[0]; i++) a.set(i, a.lc(i));
+}
+
+template <class A>
+__device__ __forceinline__ void gen_arithmetic_op(A &a, uint32_t i, gl_t c0, gl_t c1) {
+  a.set(4 * i + 3, gl_add(gl_mul(gl_mul(a.get(4 * i), a.get(4 * i + 1)), c0), gl_mul(a.get(4 * i + 2), c1)));
+}
+
+// BaseSplitGenerator: sum -> limbs
+template <class A>
+__device__ __forceinline__ void gen_base_sum_split(A &a, const GateDesc &g) {
+  uint64_t v = a.get(0);
+  const uint32_t B = g.p[0];
+  for (uint32_t i = 0; i < g.p[1]; i++) {
+    a.set(1 + i, v % B);
+    v /= B;
+  }
+  if (v) a.reject(0);  // the sum does not fit the limbs
+}
+
+// limbs -> sum (Horner from the top limb)
+template <class A>
+__device__ __forceinline__ void gen_base_sum_join(A &a, const GateDesc &g) {
+  const uint32_t B = g.p[0];
+  gl_t s = 0;
+  for (uint32_t i = g.p[1]; i-- > 0;) {
+    const gl_t l = a.get(1 + i);
+    if (l >= B) a.reject(1 + i);
+    s = gl_add(gl_mul(s, B), l);
+  }
+  a.set(0, s);
+}
+
+template <class A>
+__device__ __forceinline__ void gen_random_access_copy(A &a, const GateDesc &g, uint32_t cp) {
+  const uint32_t bits = g.p[0], copies = g.p[1], extra = g.p[2], vec = 1u << bits;
+  const uint32_t routed = (2 + vec) * copies + extra, base = (2 + vec) * cp;
+  const uint64_t idx = a.get(base);
+  a.set(base + 1, a.get(base + 2 + (uint32_t)(idx & (vec - 1))));
+  for (uint32_t k = 0; k < bits; k++) a.set(routed + cp * bits + k, (idx >> k) & 1);
+}
+
+template <class A>
+__device__ __forceinline__ void gen_random_access_consts(A &a, const GateDesc &g) {
+  const uint32_t copies = g.p[1], extra = g.p[2], vec = 1u << g.p[0];
+  for (uint32_t i = 0; i < extra; i++) a.set((2 + vec) * copies + i, a.lc(i));
+}
+
+// prc: the 360 round constants (wave-uniform index -> scalar loads)
+template <class A>
+__device__ __forceinline__ void gen_poseidon(A &a, const gl_t *prc) {
+  gl_t st[12];
+  const gl_t swap = a.get(24);
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const gl_t l = a.get(i), r = a.get(i + 4);
+    const gl_t dl = gl_mul(swap, gl_sub(r, l));
+    a.set(25 + i, dl);
+    st[i] = gl_add(l, dl);
+    st[i + 4] = gl_sub(r, dl);
+  }
+#pragma unroll
+  for (int i = 8; i < 12; i++) st[i] = a.get(i);
+#pragma unroll 1
+  for (int r = 0; r < 30; r++) {
+#pragma unroll
+    for (int i = 0; i < 12; i++) st[i] = gl_add(st[i], prc[12 * r + i]);
+    const bool full = r < 4 || r >= 26;
+    if (full) {
+      if (r != 0) {
+        const uint32_t base = r < 4 ? 29 + 12 * (r - 1) : 87 + 12 * (r - 26);
+#pragma unroll
+        for (int i = 0; i < 12; i++) a.set(base + i, st[i]);
+      }
+#pragma unroll
+      for (int i = 0; i < 12; i++) st[i] = poseidon_sbox(st[i]);
+    } else {
+      a.set(65 + (r - 4), st[0]);
+      st[0] = poseidon_sbox(st[0]);
+    }
+    poseidon_mds(st);
+  }
+#pragma unroll
+  for (int i = 0; i < 12; i++) a.set(12 + i, st[i]);
+}
+
+template <class A>
+__device__ __forceinline__ void gen_u32_arithmetic_op(A &a, const GateDesc &g, uint32_t i) {
+  const uint32_t ops = g.p[0];
+  uint64_t o = gl_add(gl_mul(a.get(6 * i), a.get(6 * i + 1)), a.get(6 * i + 2));
+  const uint64_t hi = o >> 32, lo = o & 0xFFFFFFFFULL;
+  a.set(6 * i + 3, lo);
+  a.set(6 * i + 4, hi);
+  const uint64_t diff = 0xFFFFFFFFULL - hi;
+  a.set(6 * i + 5, diff ? gl_inv(diff) : 0);
+  for (uint32_t j = 0; j < 32; j++) {
+    a.set(6 * ops + 32 * i + j, o & 3);
+    o >>= 2;
+  }
+}
+
+template <class A>
+__device__ __forceinline__ void gen_u32_add_many_op(A &a, const GateDesc &g, uint32_t i) {
+  const uint32_t na = g.p[0], ops = g.p[1];
+  const uint32_t b = (na + 3) * i;
+  gl_t sum = 0;
+  for (uint32_t j = 0; j <= na; j++) sum = gl_add(sum, a.get(b + j));
+  const uint64_t res = sum & 0xFFFFFFFFULL, carry = sum >> 32;
+  a.set(b + na + 1, res);
+  a.set(b + na + 2, carry);
+  for (uint32_t j = 0; j < 16; j++) a.set((na + 3) * ops + 18 * i + j, (res >> (2 * j)) & 3);
+  for (uint32_t j = 0; j < 2; j++) a.set((na + 3) * ops + 18 * i + 16 + j, (carry >> (2 * j)) & 3);
+}
+
+template <class A>
+__device__ __forceinline__ void gen_u32_subtraction_op(A &a, const GateDesc &g, uint32_t i) {
+  const uint32_t ops = g.p[0];
+  const gl_t init = gl_sub(gl_sub(a.get(5 * i), a.get(5 * i + 1)), a.get(5 * i + 2));
+  const gl_t bout = init > (1ULL << 32) ? 1 : 0;
+  const gl_t res = gl_add(init, gl_mul(bout, 1ULL << 32));
+  a.set(5 * i + 3, res);
+  a.set(5 * i + 4, bout);
+  for (uint32_t j = 0; j < 16; j++) a.set(5 * ops + 16 * i + j, (res >> (2 * j)) & 3);
+}
+
+template <class A>
+__device__ __forceinline__ void gen_u32_range_check(A &a, const GateDesc &g) {
+  const uint32_t nl = g.p[0];
+  for (uint32_t i = 0; i < nl; i++) {
+    const uint32_t v = (uint32_t)a.get(i);
+    for (uint32_t j = 0; j < 16; j++) a.set(nl + 16 * i + j, (v >> (2 * j)) & 3);
+  }
+}
+
+template <class A>
+__device__ __forceinline__ void gen_comparison(A &a, const GateDesc &g) {
+  const uint32_t nb = g.p[0], nc = g.p[1], cb = (nb + nc - 1) / nc;
+  const uint64_t a0 = a.get(0), b0 = a.get(1), cs = 1ULL << cb;
+  uint64_t ta = a0, tb = b0;
+  a.set(2, a0 <= b0 ? 1 : 0);
+  gl_t msd = 0;
+  for (uint32_t i = 0; i < nc; i++) {
+    const gl_t f = ta % cs, s = tb % cs;
+    ta /= cs;
+    tb /= cs;
+    a.set(4 + i, f);
+    a.set(4 + nc + i, s);
+    a.set(4 + 2 * nc + i, (f == s) ? 1 : gl_inv(gl_sub(s, f)));
+    a.set(4 + 3 * nc + i, (f == s) ? 1 : 0);
+    if (f != s) {
+      msd = gl_sub(s, f);
+      a.set(4 + 4 * nc + i, 0);
+    } else {
+      a.set(4 + 4 * nc + i, msd);
+    }
+  }
+  a.set(3, msd);
+  uint64_t v = gl_add(cs, msd);
+  for (uint32_t i = 0; i < cb + 1; i++) {
+    a.set(4 + 5 * nc + i, v & 1);
+    v >>= 1;
+  }
+}
+
+}  // namespace p2

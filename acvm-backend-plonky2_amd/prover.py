@@ -92,6 +92,12 @@ def load_library():
     a = lib.p2gpu_prove.argtypes
     lib.p2gpu_prove_sparse.argtypes = [a[0], a[1], ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32] + list(a[2:])
     lib.p2gpu_fill_witness.argtypes = [vp, vp]
+    lib.p2gpu_witness_plan_create.argtypes = [vp, vp, sz, ctypes.POINTER(vp)]
+    lib.p2gpu_witness_plan_destroy.argtypes = [vp]
+    lib.p2gpu_witness_plan_destroy.restype = None
+    lib.p2gpu_witness_plan_info.argtypes = [vp, vp, vp]
+    lib.p2gpu_generate_witness.argtypes = [vp, vp, vp]
+    lib.p2gpu_prove_seeds.argtypes = [vp, vp, vp, ctypes.c_uint32, u8p, ctypes.POINTER(sz), ctypes.POINTER(_Timings)]
     lib.p2gpu_verify.argtypes = [vp, u8p, sz]
     lib.p2gpu_circuit_export_vk.argtypes = [vp, u8p, ctypes.POINTER(sz)]
     lib.p2gpu_circuit_export_vk_plonky2.argtypes = [vp, u8p, ctypes.POINTER(sz)]
@@ -421,6 +427,11 @@ class CircuitData:
         _check(self._lib.p2gpu_fill_witness(self._h, ctypes.c_void_p(wires_dev.data_ptr())))
         return wires_dev
 
+    def witness_plan(self, seed_cells):
+        """``p2gpu_witness_plan_create``: the plan that turns the values of `seed_cells` ([(row, col)]: the cells the
+        caller assigns per proof, ``pw.set_target`` on the Rust side) into the whole witness on the GPU."""
+        return WitnessPlan(self, seed_cells)
+
     def prove_routed(self, routed, public_inputs=()):
         """Prove from the routed columns only ([num_routed_wires][degree], host): gate-internal
         columns are derived on the GPU by the row-local generators."""
@@ -484,6 +495,67 @@ class CircuitData:
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             self._lib.p2gpu_circuit_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class WitnessPlan:
+    """Witness generation on the GPU for one circuit and one set of seed cells (``p2gpu_witness_plan``).  Close it before
+    the circuit."""
+
+    def __init__(self, circuit, seed_cells):
+        self._cd, self._lib = circuit, circuit._lib
+        cells = np.ascontiguousarray(np.array(list(seed_cells), dtype=np.int64).reshape(-1, 2))
+        if cells.size and (cells.min() < 0 or cells.max() >= 1 << 32):
+            raise P2GpuError(-7, "seed cells are (row, col) pairs of unsigned 32-bit numbers")
+        cells = cells.astype(np.uint32)
+        self.num_seeds = len(cells)
+        self._h = ctypes.c_void_p()
+        _check(self._lib.p2gpu_witness_plan_create(circuit._h, cells.ctypes.data if cells.size else None, len(cells), ctypes.byref(self._h)))
+
+    def _values(self, values):
+        v = _u64(np.array([int(x) for x in values], dtype=np.uint64))
+        if v.size != self.num_seeds:
+            raise P2GpuError(-7, f"{self.num_seeds} seed values expected, {v.size} given")
+        return v
+
+    def info(self):
+        """Shape of the schedule, the host time of the plan's compilation and the device time of the last level walk."""
+        counts, ms = np.zeros(5, dtype=np.uint64), np.zeros(2, dtype=np.float64)
+        _check(self._lib.p2gpu_witness_plan_info(self._h, counts.ctypes.data, ms.ctypes.data))
+        out = dict(zip(("ops", "levels", "widest_level", "slots", "seeds"), (int(x) for x in counts)))
+        out.update(compile_ms=float(ms[0]), walk_ms=float(ms[1]))
+        return out
+
+    def generate(self, values):
+        """``p2gpu_generate_witness``: the wire matrix [num_wires][degree] as an int64 tensor on the circuit's GPU."""
+        import torch
+
+        v = self._values(values)
+        cd = self._cd
+        out = torch.empty((cd.num_wires, cd.degree), dtype=torch.int64, device=f"cuda:{cd.device_index()}")
+        _check(self._lib.p2gpu_generate_witness(self._h, v.ctypes.data if v.size else None, ctypes.c_void_p(out.data_ptr())))
+        return out
+
+    def prove(self, values, public_inputs=()):
+        """``p2gpu_prove_seeds``: generate into the handle's own buffer, then the resident proof path."""
+        v = self._values(values)
+        pis = _u64(np.array(list(public_inputs), dtype=np.uint64))
+        out = np.zeros(self._cd._bound, dtype=np.uint8)
+        plen = ctypes.c_size_t(out.nbytes)
+        tm = _Timings()
+        _check(self._lib.p2gpu_prove_seeds(self._h, v.ctypes.data if v.size else None, pis.ctypes.data, len(pis), out.ctypes.data,
+                                           ctypes.byref(plen), ctypes.byref(tm)))
+        return ProofWithPublicInputs(out[:plen.value].tobytes(), {f: getattr(tm, f) for f, _ in _Timings._fields_})
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.p2gpu_witness_plan_destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

@@ -50,6 +50,7 @@ class CircuitBuilder:
         self.arith_results = {}   # (c0, c1, m0, m1, addend) -> output target of the identical earlier operation
         self.events = []          # witness generators in creation order
         self.rng = np.random.default_rng(seed)
+        self._lay = None          # what _layout() made
 
     # -- targets, copy constraints --------------------------------------------------------------
     def add_virtual_target(self):
@@ -222,8 +223,11 @@ class CircuitBuilder:
         return row["sum"]
 
     # -- build(): rows -> blob (library) + witness ----------------------------------------------------
-    def build(self, witness_values):
-        """witness_values: {target: value}.  Returns (blob, wires) for CircuitData(blob).prove(wires)."""
+    def _layout(self):
+        """The circuit half of build(): rows -> blob, and the cells of every copy class.  Runs once; build(), seed_cells() and
+        seed_values() share its result."""
+        if self._lay is not None:
+            return self._lay
         zero = self.zero()
         # circuit_builder.rs build(): the public inputs are hashed IN CIRCUIT -- hash_n_to_hash_no_pad::<PoseidonHash>, an
         # overwrite-mode sponge: one PoseidonGate row per 8 inputs, swap wire tied to zero, the state starts as twelve copies of
@@ -309,6 +313,13 @@ class CircuitBuilder:
                 copies.append((r0, c0, r1, c1))
         blob = build_blob(d, gates, row_gate, row_consts, np.array(copies, dtype=np.uint32).reshape(-1, 4),
                           num_public_inputs=len(self.public_inputs), num_wires=self.num_wires)
+        self.pi_row = pi_row
+        self._lay = (blob, rows, pi_row, const_list, cells, n)
+        return self._lay
+
+    def build(self, witness_values):
+        """witness_values: {target: value}.  Returns (blob, wires) for CircuitData(blob).prove(wires)."""
+        blob, rows, pi_row, const_list, cells, n = self._layout()
         # witness: the generators, in creation order, until nothing changes
         val = {}
         for c, t in const_list:
@@ -377,9 +388,50 @@ class CircuitBuilder:
         wires[4:NUM_ROUTED, pi_row] = self.rng.integers(0, P, size=NUM_ROUTED - 4, dtype=np.uint64)
         wires[NUM_ROUTED:, pi_row] = self.rng.integers(0, P, size=W - NUM_ROUTED, dtype=np.uint64)
         self.public_input_values = [val[self.find(t)] for t in self.public_inputs]
-        self.pi_row = pi_row
         self.values = val
         return blob, wires
+
+    # -- the witness on the GPU: what the caller still has to supply ------------------------------------
+    def _seed_classes(self):
+        """(cells, roots) of the seeds that carry a value of the program: one cell per copy class that holds no constant and
+        no generator's output -- the targets `pw.set_target` is called on -- in the order of the classes' first targets."""
+        _, _, _, _, cells, _ = self._layout()
+        derived = {self.find(t) for t in self.const_of}
+        for ev in self.events:
+            if ev[0] == "arith":
+                derived.add(self.find(ev[6]))
+            elif ev[0] == "poseidon":
+                derived.update(self.find(t) for t in ev[1]["out"])
+            elif ev[0] == "split":
+                assert len(ev[2]) == 1, "a split over several BaseSum rows spans rows: not a gate-local generator"
+                derived.update(self.find(t) for t in ev[2][0]["limbs"])
+            else:
+                derived.add(self.find(ev[1]["sum"]))
+        roots = sorted(rt for rt in cells if rt not in derived)
+        return [cells[rt][0] for rt in roots], roots
+
+    def seed_cells(self):
+        """[(row, col)] for CircuitData.witness_plan: the input classes, then every wire of the PublicInputGate row behind
+        the public-input hash (build() fills those with random values: they are the caller's, not a generator's)."""
+        cl, _ = self._seed_classes()
+        return cl + [(self.pi_row, c) for c in range(4, self.num_wires)]
+
+    def seed_values(self, witness_values):
+        """The values of seed_cells(), without running build()'s event loop: witness_values {target: value} must name one
+        target of every input class; the PublicInputGate row is drawn from the builder's generator as build() draws it."""
+        _, roots = self._seed_classes()
+        given = {}
+        for t, v in witness_values.items():
+            rt, v = self.find(t), v % P
+            if given.setdefault(rt, v) != v:
+                raise ValueError("witness value contradicts the circuit")
+        missing = [rt for rt in roots if rt not in given]
+        if missing:
+            raise ValueError("witness generation is stuck: some inputs were not assigned")
+        out = [given[rt] for rt in roots]
+        out += [int(x) for x in self.rng.integers(0, P, size=NUM_ROUTED - 4, dtype=np.uint64)]
+        out += [int(x) for x in self.rng.integers(0, P, size=self.num_wires - NUM_ROUTED, dtype=np.uint64)]
+        return out
 
     def _set(self, val, t, v):
         rt = self.find(t)
@@ -575,6 +627,20 @@ class CircuitBuilderFromAcirToPlonky2:
         inputs; outputs given are checked against what the circuit forces).  Returns (blob, wires)."""
         vals = {self.witness_target_map[w]: v for w, v in acir_witness.items() if w in self.witness_target_map}
         return self.builder.build(vals)
+
+    def witness_seeds(self, acir_witness):
+        """(seed cells, seed values) for CircuitData.witness_plan(cells).prove(values): the inputs of `acir_witness`
+        ({witness index: value}) without build()'s event loop.  Outputs the solver also knows may be given; only the
+        circuit's inputs are read."""
+        b = self.builder
+        vals = {self.witness_target_map[w]: v for w, v in acir_witness.items() if w in self.witness_target_map}
+        _, roots = b._seed_classes()
+        roots = set(roots)
+        return b.seed_cells(), b.seed_values({t: v for t, v in vals.items() if b.find(t) in roots})
+
+    def blob(self):
+        """The circuit blob alone (build() without the witness)."""
+        return self.builder._layout()[0]
 
     def public_inputs(self):
         """Values of the registered public inputs, in order (after build): what p2gpu_prove takes beside the wires."""

@@ -17,6 +17,9 @@
  *   p2gpu_fill_witness / p2gpu_prove_routed
  *                          <- the row-local tail of `generate_partial_witness`: the gates' own
  *                             SimpleGenerators (e.g. arithmetic_u32.rs:376-426)
+ *   p2gpu_witness_plan_create / p2gpu_generate_witness / p2gpu_prove_seeds
+ *                          <- all of `generate_partial_witness` (plonky2 iop/generator.rs, called by `prove`): the caller
+ *                             hands over the `pw.set_target` values only, generators and copy constraints run on the GPU
  *   p2gpu_last_error       <- the `anyhow::Error` text the reference unwraps
  *   p2gpu_ifft_batch / p2gpu_lde_batch / p2gpu_commit_values
  *                          <- plonky2 PolynomialValues::ifft,
@@ -157,6 +160,32 @@ int p2gpu_prove_routed(p2gpu_circuit *c, const uint64_t *routed, const uint64_t 
 int p2gpu_prove_sparse(p2gpu_circuit *c, const uint64_t *wires, uint32_t ncols, const uint64_t *tail, uint32_t row,
                        const uint64_t *public_inputs, uint32_t n_pi, uint8_t *proof_out, size_t *proof_len,
                        p2gpu_timings *opt_timings);
+
+/* ---- the witness from the solver's values (`generate_partial_witness`, iop/generator.rs) ----
+ * A plan is made once per circuit and seed set.  Seeds are the cells whose values the caller supplies per proof -- what the
+ * Rust side passes to `pw.set_target` -- as (row, col) with col < num_wires; a seed on a gate-internal column or on a cell
+ * outside every copy class is simply written (the PublicInputGate row's random wires arrive that way).  From the handle's sigma
+ * polynomials the plan takes the copy classes of the routed cells, from its gate rows the generators (the closed registry
+ * p2gpu_fill_witness runs, per ArithmeticGate / U32 operation, per RandomAccess copy, per row otherwise; BaseSum in the
+ * direction the schedule reaches first), and sorts them into dependency levels.  P2GPU_E_ARG, with a cell in
+ * p2gpu_last_error: a seed outside the matrix, a cell seeded twice, a copy class that no seed, constant or generator
+ * reaches, a dependency cycle; also a verifier-only handle or a device group.  A plan must be destroyed before its circuit;
+ * one call at a time per circuit handle, as for every entry point. */
+typedef struct p2gpu_witness_plan p2gpu_witness_plan;
+int p2gpu_witness_plan_create(p2gpu_circuit *c, const uint32_t *seed_cells /* [n_seeds][2] = (row, col) */, size_t n_seeds,
+                              p2gpu_witness_plan **out);
+void p2gpu_witness_plan_destroy(p2gpu_witness_plan *p);
+/* counts: ops, levels, widest level, value slots, seeds; ms: plan compilation (host), level walk of the last witness (device) */
+int p2gpu_witness_plan_info(const p2gpu_witness_plan *p, uint64_t counts[5], double ms[2]);
+/* seed_values: host, [n_seeds] in the plan's order.  wires_dev_out: device, [num_wires][n], written completely.  One workgroup
+ * walks the levels, a kernel copies the class values to the routed cells, p2gpu_fill_witness's kernel derives the rest.  A
+ * generator whose output already has another value, or a seed >= p: P2GPU_E_UNSATISFIED, the first offender's cell in
+ * p2gpu_last_error (the matrix is then not a witness). */
+int p2gpu_generate_witness(p2gpu_witness_plan *p, const uint64_t *seed_values, uint64_t *wires_dev_out);
+/* p2gpu_generate_witness into the handle's own buffer, then p2gpu_prove_dev on it: the same proof bytes.  h2d_ms of the timings
+ * holds the time the witness took. */
+int p2gpu_prove_seeds(p2gpu_witness_plan *p, const uint64_t *seed_values, const uint64_t *public_inputs, uint32_t n_pi,
+                      uint8_t *proof_out, size_t *proof_len, p2gpu_timings *opt_timings);
 
 /* ---- N2: prover-side precompute of `builder.build::<C>()` (host code; circuit_translation/mod.rs:80-82) ----
  * From the gate instances and the copy constraints: selector columns + groups (gates/selectors.rs), the
