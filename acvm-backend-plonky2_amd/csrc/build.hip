@@ -205,7 +205,7 @@ void build_selector_columns(hipStream_t st, const p2gpu_circuit *c, gl_t *consts
                      c->num_selectors, c->n, consts);
 }
 
-int build_device_tables(p2gpu_circuit *c, const BuildInputs &in, void (*mark)(void *, const char *), void *mark_ctx) {
+int build_device_tables(p2gpu_circuit *c, const BuildInputs &in, const CreateTrace &tr) {
   hipStream_t st = c->stream;
   const size_t n = c->n, E = in.num_copies;
   const uint32_t R = c->R, d = c->d, ngc = c->NC - c->num_selectors;
@@ -242,7 +242,7 @@ int build_device_tables(p2gpu_circuit *c, const BuildInputs &in, void (*mark)(vo
   unsigned long long h[8];
   BT(hipMemcpyAsync(h, words, 24, hipMemcpyDeviceToHost, st), "read validation");
   BT(hipStreamSynchronize(st), "validation");
-  mark(mark_ctx, "build: upload + validation");
+  tr.mark("build: upload + validation");
   // (the order and the words of p2gpu_build_blob's refusals)
   if (h[0] != UINT64_MAX) {
     set_err("row %zu holds gate index %u of %u", (size_t)h[0], in.row_gate[h[0]], c->num_gates);
@@ -279,7 +279,7 @@ int build_device_tables(p2gpu_circuit *c, const BuildInputs &in, void (*mark)(vo
     BT(hipStreamSynchronize(st), "touch");
     T = (size_t)h[3];
     if (T > list_cap) { set_err("p2gpu_circuit_build: internal error (touched cells)"); return P2GPU_E_DEVICE; }
-    mark(mark_ctx, "build: touched cells");
+    tr.mark("build: touched cells");
     // classes: while a pair is left to hook, every round removes at least one root; in practice a handful of rounds.  The
     // bounds are backstops against a defect, not part of the algorithm
     uint32_t hc = 0;
@@ -299,7 +299,7 @@ int build_device_tables(p2gpu_circuit *c, const BuildInputs &in, void (*mark)(vo
         if (!hc) break;
       }
     }
-    mark(mark_ctx, "build: copy classes");
+    tr.mark("build: copy classes");
     // cycles
     unsigned long long *sorted = S.alloc<unsigned long long>(T);
     if (!sorted) return dev_fail("scratch (sort)", hipErrorOutOfMemory);
@@ -311,7 +311,7 @@ int build_device_tables(p2gpu_circuit *c, const BuildInputs &in, void (*mark)(vo
     BT(rocprim::radix_sort_keys(tmp, tmp_bytes, list, sorted, T, 0u, 2 * key_bits, st), "sort");
     if (trace_on()) {
       (void)hipStreamSynchronize(st);
-      mark(mark_ctx, "build: sort by (root, key)");
+      tr.mark("build: sort by (root, key)");
     }
     hipLaunchKernelGGL(build_sigma_cycles_kernel, dim3(grid_for(T)), dim3(TPB), 0, st, sorted, T, key_bits, R, d, c->d_kis.p, c->tw_fwd.p,
                        c->d_sigmas.p);
@@ -330,7 +330,7 @@ int build_device_tables(p2gpu_circuit *c, const BuildInputs &in, void (*mark)(vo
     c->sparse_rows.row[c->sparse_rows.count++] = c->sparse_row;
     for (uint32_t s = 1; s < MAX_SPARSE_ROWS && hr[s] != UINT32_MAX; s++) c->sparse_rows.row[c->sparse_rows.count++] = hr[s];
   }
-  mark(mark_ctx, "build: sigma fill, rows");
+  tr.mark("build: sigma fill, rows");
   return P2GPU_OK;
 }
 

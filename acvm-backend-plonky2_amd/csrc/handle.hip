@@ -1,8 +1,10 @@
-// handle.hip -- the circuit handle behind include/p2gpu.h: device selection, `p2gpu_circuit_create` (the prover-side half of
-// `build()`: tables, plans, the constants / sigmas commitment; plonky2-backend/src/circuit_translation/mod.rs:80-82), knobs,
-// sharding configuration, release -- and the stage-level operators the parity tests drive (inverse transform, LDE, row
-// hashing, commitment, field self-test).  The proof itself is prover.hip, the commitment operators commit.hip, the exchanges of a
-// sharded proof transport.hip.
+// handle.hip -- the circuit handle behind include/p2gpu.h: device selection, `p2gpu_circuit_create` / `p2gpu_circuit_build` (the
+// prover-side half of `build()`; plonky2-backend/src/circuit_translation/mod.rs:80-82), knobs, sharding configuration, release --
+// and the stage-level operators the parity tests drive (inverse transform, LDE, row hashing, commitment, field self-test).
+// Creation is circuit_finish: a list of phases (schedule_gates, make_streams, make_root_tables, the tables from a blob or from
+// build.hip, alloc_proof_buffers, commit_constants_sigmas, check_cap_and_digest) on a handle that a HalfBuilt owns until it is
+// handed to the caller.  The proof itself is prover.hip, the commitment operators commit.hip, the exchanges of a sharded proof
+// transport.hip.
 #include "prover_internal.hpp"
 #include <functional>
 
@@ -62,7 +64,7 @@ std::vector<int> g_devices;  // p2gpu_init's list; more than one entry: circuit 
 void circuit_release(p2gpu_circuit *c) {
   c->tw_fwd.release(); c->tw_inv.release(); c->scale.release(); c->inv_scale.release(); c->d_kis.release();
   c->d_sigmas.release(); c->fri_scale.release(); c->d_gates.release(); c->qconst.release(); c->l0_lde.release();
-  c->d_row_gate.release(); c->d_gconsts.release(); c->d_prc.release(); c->d_prc_hash.release(); c->qconst.release();
+  c->d_row_gate.release(); c->d_gconsts.release(); c->d_prc.release(); c->d_prc_hash.release();
   c->hsum.release(); c->htmp_a.release(); c->htmp_b.release();
   c->cs.release(); c->wires.release(); c->zp.release(); c->quot.release();
   c->wires_vals.release(); c->zp_vals.release(); c->cp.release(); c->scan_tmp.release();
@@ -112,6 +114,409 @@ int ensure_device() {
 }
 
 }  // namespace p2
+
+
+// ---- circuit creation: the phases of circuit_finish, in its order ----
+namespace {
+
+// a failed HIP call of a creation phase: "<what>: <hip error string>", P2GPU_E_DEVICE (the HalfBuilt of the caller gives the handle back)
+#define CK(e, what)                                       \
+  do {                                                    \
+    const hipError_t e_ = (e);                            \
+    if (e_ != hipSuccess) {                               \
+      set_err("%s: %s", what, hipGetErrorString(e_));     \
+      return P2GPU_E_DEVICE;                              \
+    }                                                     \
+  } while (0)
+
+// Host only, cannot fail: nterms, the gate groups of the quotient kernels, the half-domain slots and every GateDesc.pad.
+void schedule_gates(p2gpu_circuit *c) {
+  c->nterms = c->K + c->K * c->nchunks + c->max_gate_constraints;
+  // heavy gate mixes: split the gates over 4 waves that share a row tile (plonk.hip); greedy
+  // balance by an estimate of modmuls per row, group 0 starts with the permutation argument
+  // (a PoseidonGate is not part of this: it has its own kernel, plonk.hip poseidon_gate_kernel)
+  auto cost = [](const GateDesc &g) { return g.kind == G_POSEIDON ? 0u : 4u * g.num_constraints + 8u; };
+  const uint32_t perm_cost = (uint32_t)env_uint("P2GPU_PERM_COST", 8u * c->R + 100u);  // balance experiments only
+  uint32_t total = 0;
+  for (auto &g : c->gates) total += cost(g);
+  c->gate_groups = env_uint("P2GPU_GATE_GROUPS", total > 2 * perm_cost ? 4u : 1u) == 4 ? 4u : 1u;
+  uint32_t load[4] = {perm_cost, 0, 0, 0};
+  std::vector<uint32_t> order(c->gates.size());
+  for (size_t i = 0; i < order.size(); i++) order[i] = (uint32_t)i;
+  std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return cost(c->gates[x]) > cost(c->gates[y]); });
+  for (uint32_t gi : order) {
+    uint32_t best = 0;
+    for (uint32_t q = 1; q < 4; q++)
+      if (load[q] < load[best]) best = q;
+    c->gates[gi].pad = c->gate_groups == 4 ? best : 0;
+    load[best] += cost(c->gates[gi]);
+  }
+  // Gates of degree <= 4 with enough constraints to pay for two transforms per challenge: evaluated on the even cosets only
+  // (plonk.hip gate_sums_kernel).  The degree is the library's own count (gate_degree), not the blob's field.
+  uint64_t half_constraints = 0;
+  // P2GPU_HALF_GATES=0: off (A/B measurements); the knob "half_gates" does the same per handle
+  if (env_flag("P2GPU_HALF_GATES", true) && c->d >= 6 && c->rate_bits == 3)
+    for (auto &g : c->gates)
+      if (g.kind != G_POSEIDON && g.num_constraints >= 48 && gate_degree(g.kind, g.p) <= 4 && c->half_slots < 64) {
+        g.pad |= (++c->half_slots) << 16;
+        half_constraints += g.num_constraints;
+      }
+  // Worth it by default only where it saves more than its five extra launches cost a lone proof: ~77 lane-instructions per
+  // constraint on 4n rows at 37.7 T/s against ~100 us -- constraints x n >= 12 M (the heavy mix: from 2^14 gates on).  The knob
+  // "half_gates" = 2 takes the route whatever the size (tests).
+  c->half_auto = (half_constraints << c->d) >= ((uint64_t)12 << 20);
+  if (c->half_slots) {
+    // the main kernel without them: a look-up and two products per gate and challenge
+    auto cost_main = [&](const GateDesc &g) { return gate_half_slot(g) ? 8u : cost(g); };
+    uint32_t rest = 0;
+    for (auto &g : c->gates) rest += cost_main(g);
+    // (P2GPU_GATE_GROUPS_HALF, P2GPU_SUMS_GROUPS: balance experiments only)
+    c->gate_groups_half = env_uint("P2GPU_GATE_GROUPS_HALF", rest > 2 * perm_cost ? 4u : 1u) == 4 ? 4u : 1u;
+    uint32_t lm[4] = {perm_cost, 0, 0, 0}, ls[4] = {0, 0, 0, 0};
+    c->sums_groups = env_uint("P2GPU_SUMS_GROUPS", c->half_slots >= 2 ? 4u : 1u) == 4 ? 4u : 1u;
+    for (uint32_t gi : order) {
+      GateDesc &g = c->gates[gi];
+      uint32_t bm = 0, bs = 0;
+      for (uint32_t q = 1; q < 4; q++) {
+        if (lm[q] < lm[bm]) bm = q;
+        if (ls[q] < ls[bs]) bs = q;
+      }
+      if (c->gate_groups_half == 4) g.pad |= bm << 4;
+      lm[bm] += cost_main(g);
+      if (gate_half_slot(g)) {
+        if (c->sums_groups == 4) g.pad |= bs << 8;
+        ls[bs] += cost(g);
+      }
+    }
+  }
+}
+
+int make_streams(p2gpu_circuit *c) {
+  if (poseidon_upload_constants()) { set_err("uploading Poseidon constants failed"); return P2GPU_E_DEVICE; }
+  CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking), "hipStreamCreate");
+  CK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking), "hipStreamCreate");
+  return P2GPU_OK;
+}
+
+// twiddles, coset scales, transform plans, the half-domain buffers and matrix, the quotient constants and the L0 table (and the
+// buffers of k_is, sigma and the gate table, which the table phase fills)
+int make_root_tables(p2gpu_circuit *c) {
+  hipStream_t st = c->stream;
+  const size_t n = c->n;
+  const uint32_t d = c->d, K = c->K, C = c->C;
+  const size_t half = n >= 2 ? n / 2 : 1;
+  CK(c->tw_fwd.alloc(half), "alloc tw");
+  CK(c->tw_inv.alloc(half), "alloc tw");
+  CK(c->scale.alloc((size_t)C * n), "alloc scale");
+  CK(c->inv_scale.alloc((size_t)C * n), "alloc scale");
+  CK(c->fri_scale.alloc((size_t)C * n), "alloc scale");
+  CK(c->d_kis.alloc(c->R), "alloc kis");
+  CK(c->d_sigmas.alloc((size_t)c->R * n), "alloc sigmas");
+  CK(c->d_gates.alloc(c->num_gates ? c->num_gates : 1), "alloc gates");
+  gl_t wn = gl_root(d), wN = gl_root(d + c->rate_bits);
+  c->plan_inv = ntt_plan_create(st, d, 0, true);
+  c->plan_fwd = ntt_plan_create(st, d, 1, false);
+  if (!c->plan_inv || !c->plan_fwd) { set_err("ntt plan allocation failed"); return P2GPU_E_DEVICE; }
+  fill_powers(st, c->tw_fwd.p, wn, (uint32_t)half);
+  fill_powers(st, c->tw_inv.p, gl_inv(wn), (uint32_t)half);
+  fill_coset_scale(st, c->scale.p, GL_GEN, wN, d, C, 1);
+  fill_coset_scale(st, c->inv_scale.p, gl_inv(GL_GEN), gl_inv(wN), d, C, 1);
+  if (c->half_slots) {
+    const size_t per = (size_t)4 * c->half_slots * K * n;
+    CK(c->hsum.alloc(2 * per), "alloc gate sums");
+    CK(c->htmp_a.alloc(per), "alloc gate sums");
+    CK(c->htmp_b.alloc(per), "alloc gate sums");
+    // F[m'][m] = 1/4 sum_j w_8^((2 m' + 1 - 2 m) j): even cosets' interpolants -> odd cosets' coefficient arrays
+    const gl_t w8 = gl_root(3), quarter = gl_inv(4);
+    for (int mo = 0; mo < 4; mo++)
+      for (int m = 0; m < 4; m++) {
+        const gl_t base = gl_pow(w8, (uint64_t)((2 * mo + 1 - 2 * m + 16) % 8));
+        gl_t acc = 0, pw = 1;
+        for (int j = 0; j < 4; j++) {
+          acc = gl_add(acc, pw);
+          pw = gl_mul(pw, base);
+        }
+        c->half_cross[4 * mo + m] = gl_mul(acc, quarter);
+      }
+  }
+  CK(c->qconst.alloc(24), "alloc qconst");
+  {
+    // ZeroPolyOnCoset: Z_H on the LDE coset has period 2^rate_bits
+    gl_t qc[24];
+    memset(qc, 0, sizeof qc);
+    gl_t wC = gl_root(c->rate_bits), gn = gl_pow(GL_GEN, n);
+    for (uint32_t r = 0; r < C; r++) {
+      qc[r] = gl_mul(GL_GEN, gl_pow(wN, r));
+      qc[8 + r] = gl_sub(gl_mul(gn, gl_pow(wC, r)), 1);
+      qc[16 + r] = gl_inv(qc[8 + r]);
+    }
+    CK(hipMemcpy(c->qconst.p, qc, sizeof qc, hipMemcpyHostToDevice), "copy qconst");
+    CK(c->l0_lde.alloc((size_t)C * n), "alloc L0 table");
+    fill_l0_table(st, c->qconst.p, c->tw_fwd.p, 0, d, C, gl_inv((gl_t)n), c->l0_lde.p);
+  }
+  return P2GPU_OK;
+}
+
+// The blob form of the table phase (the device form: build_device_tables): row -> gate from the selector columns, the special
+// rows, and the gate constants and sigma as the blob holds them.
+int tables_from_blob(p2gpu_circuit *c, const gl_t *constants, const gl_t *sigmas) {
+  const size_t n = c->n;
+  const uint32_t ngc = c->NC - c->num_selectors;
+  CK(hipMemcpyAsync(c->d_sigmas.p, sigmas, 8 * (size_t)c->R * n, hipMemcpyHostToDevice, c->stream), "copy sigmas");
+  // row -> gate (the one selector column that is not UNUSED holds the index) and the gate
+  // constants, for the row-local witness generators (p2gpu_fill_witness)
+  std::vector<uint8_t> rg(n, 0);
+  for (size_t row = 0; row < n; row++) {
+    uint32_t gi = 0;
+    for (uint32_t s = 0; s < c->num_selectors; s++) {
+      gl_t v = constants[(size_t)s * n + row];
+      if (c->num_selectors == 1 || v != 0xFFFFFFFFULL) gi = (uint32_t)v;
+    }
+    if (gi >= c->num_gates) { set_err("selector column holds an unknown gate index"); return P2GPU_E_BLOB; }
+    rg[row] = (uint8_t)gi;
+    if (c->sparse_row == UINT32_MAX && c->gates[gi].kind == G_PUBLIC_INPUT) c->sparse_row = (uint32_t)row;
+  }
+  // the special rows of the column classification: the PublicInputGate row first, then the PoseidonGate rows
+  c->sparse_rows = SparseRows();
+  if (c->sparse_row != UINT32_MAX) {
+    c->sparse_rows.row[c->sparse_rows.count++] = c->sparse_row;
+    for (size_t row = 0; row < n && c->sparse_rows.count < MAX_SPARSE_ROWS; row++)
+      if (c->gates[rg[row]].kind == G_POSEIDON) c->sparse_rows.row[c->sparse_rows.count++] = (uint32_t)row;
+  }
+  CK(hipMemcpy(c->d_row_gate.p, rg.data(), n, hipMemcpyHostToDevice), "copy row_gate");
+  if (ngc)
+    CK(hipMemcpy(c->d_gconsts.p, constants + (size_t)c->num_selectors * n, 8 * (size_t)ngc * n, hipMemcpyHostToDevice), "copy gconsts");
+  return P2GPU_OK;
+}
+
+// Everything a proof writes: the four batches, the wire classes and the sparse basis, the work buffers, the FRI plans, buffers
+// and trees, the query gather and the pinned arena.
+int alloc_proof_buffers(p2gpu_circuit *c) {
+  hipStream_t st = c->stream;
+  const size_t n = c->n;
+  const uint32_t d = c->d, K = c->K, C = c->C;
+  const uint32_t ncs = c->NC + c->R, nzp = K * (1 + c->PP), nq = K * c->QF;
+  const uint32_t nall = ncs + c->W + nzp + nq;
+  if (batch_alloc(c, c->cs, ncs) || batch_alloc(c, c->wires, c->W) || batch_alloc(c, c->zp, nzp) || batch_alloc(c, c->quot, nq)) return P2GPU_E_DEVICE;
+  CK(c->wires_vals.alloc((size_t)c->W * n), "alloc wires");
+  CK(c->wire_nz.alloc(c->W), "alloc wire flags");
+  CK(c->wire_nzlist.alloc(c->W + 1), "alloc wire flags");
+  CK(c->wire_clean.alloc(c->W), "alloc wire flags");
+  CK(hipMemsetAsync(c->wire_clean.p, 0, sizeof(uint32_t) * c->W, c->stream), "clear wire flags");
+  CK(c->wire_scalar.alloc((size_t)MAX_SPARSE_ROWS * c->W), "alloc wire flags");
+  if (c->sparse_row != UINT32_MAX) {
+    // inverse transform and LDE (all cosets) of the unit column of the PublicInputGate row: what a wire that is
+    // zero everywhere but there transforms to, up to its scalar -- and the same for the PoseidonGate rows
+    // (sparse_rows: columns that are zero outside these rows are their linear combination, class 3)
+    const uint32_t nr = c->sparse_rows.count;
+    CK(c->sparse_coeffs.alloc((size_t)nr * n), "alloc sparse basis");
+    CK(c->sparse_lde.alloc((size_t)nr * C * n), "alloc sparse basis");
+    CK(c->sparse_partial.alloc(16 * 2 + 2), "alloc sparse basis");
+    const gl_t one = 1;
+    CK(hipMemsetAsync(c->sparse_coeffs.p, 0, 8 * (size_t)nr * n, st), "sparse basis");
+    for (uint32_t s = 0; s < nr; s++)
+      CK(hipMemcpyAsync(c->sparse_coeffs.p + (size_t)s * n + c->sparse_rows.row[s], &one, 8, hipMemcpyHostToDevice, st), "sparse basis");
+    CK(hipStreamSynchronize(st), "sparse basis");  // `one` lives on this stack frame
+    ntt_batch(st, c->plan_inv, c->sparse_coeffs.p, c->sparse_coeffs.p, nr, 1, nullptr, gl_inv((gl_t)n), false);
+    for (uint32_t s = 0; s < nr; s++)  // [rows][C][n]: one column per launch keeps every row's cosets together
+      ntt_batch(st, c->plan_fwd, c->sparse_coeffs.p + (size_t)s * n, c->sparse_lde.p + (size_t)s * C * n, 1, C, c->scale.p, 1, false);
+  }
+  CK(c->zp_vals.alloc((size_t)nzp * n), "alloc zp");
+  CK(c->cp.alloc((size_t)K * (c->nchunks + 1) * n), "alloc cp");  // chunk quotients + the row products behind them (ZsArgs::cp)
+  CK(c->scan_tmp.alloc((size_t)K * (n + (n + 255) / 256 + 8)), "alloc scan");
+  CK(c->apow.alloc((size_t)2 * c->nterms), "alloc apow");
+  CK(c->qvals.alloc((size_t)K * C * n), "alloc qvals");
+  CK(c->qtmp.alloc((size_t)K * C * n), "alloc qtmp");
+  CK(c->pw.alloc((size_t)4 * n), "alloc pw");
+  CK(c->partial.alloc(((size_t)(nall + K) + 8) * 16 * 2), "alloc partial");  // (+8 columns: a sharded proof gathers equal blocks per rank)
+  CK(c->ext_apow.alloc((size_t)2 * nall), "alloc ext_apow");
+  CK(c->f01.alloc((size_t)4 * n), "alloc f01");
+  CK(c->f01v.alloc((size_t)4 * n), "alloc f01v");
+  CK(c->fv.alloc((size_t)2 * n), "alloc fv");
+  c->fri_coef.resize(c->n_steps + 1);
+  c->fri_vals.resize(c->n_steps + 1);
+  c->fri_trees.resize(c->n_steps);
+  size_t gather_words = 0;
+  {
+    uint32_t ds = d;
+    const size_t cap_per = ((size_t)1 << c->cap_h) >> c->rate_bits;
+    for (uint32_t s = 0; s <= c->n_steps; s++) {
+      c->fri_plans.push_back(s == 0 ? c->plan_fwd : ntt_plan_create(st, ds, 1, false));
+      if (!c->fri_plans.back()) { set_err("ntt plan allocation failed"); return P2GPU_E_DEVICE; }
+      CK(c->fri_coef[s].alloc((size_t)2 << ds), "alloc fri coef");
+      if (s < c->n_steps) {
+        CK(c->fri_vals[s].alloc((size_t)2 * C << ds), "alloc fri vals");
+        uint32_t ab = c->arity[s];
+        if (ab < 1 || ab > 4 || ds < ab || (((size_t)1 << ds) >> ab) < cap_per) { set_err("unsupported FRI reduction arity"); return P2GPU_E_BLOB; }
+        if (tree_alloc(c->fri_trees[s], C, ((size_t)1 << ds) >> ab, cap_per)) return P2GPU_E_DEVICE;
+        gather_words += (2u << ab) + 4 * (size_t)(ds + c->rate_bits);
+        ds -= ab;
+      }
+    }
+  }
+  gather_words += nall + 4 * 4 * (size_t)(d + c->rate_bits);
+  c->gather_cap = gather_words * c->num_queries + 64;
+  CK(c->gather_ptrs.alloc(c->gather_cap), "alloc gather");
+  CK(c->gather_out.alloc(c->gather_cap), "alloc gather");
+  CK(c->pow_result.alloc(1), "alloc pow");
+  // pinned host arena for every small transcript transfer of a proof (caps, opening partials, challenge
+  // powers, final polynomial, PoW result, query gather): with pageable memory each of those
+  // hipMemcpyAsync calls blocks in a staging copy and the following stream sync costs another ~10 us
+  {
+    size_t n_final = n;
+    for (uint32_t s = 0; s < c->n_steps; s++) n_final >>= c->arity[s];
+    // per proof: 3 + n_steps trees stage their caps (2^cap_h digests each, twice when sharded: local roots + gathered),
+    // the alpha powers of the openings (2 * nall words), the opening partials, the final polynomial, the query gather
+    const size_t caps = (size_t)2 * (4 + c->n_steps) * (sizeof(dig_t) << c->cap_h);
+    CK(c->pin.alloc(16 * c->gather_cap + 32 * n_final + 16 * (size_t)(nall + K) * 16 + 16 * (size_t)nall + 16 * (size_t)c->nterms +
+                    20 * (size_t)c->W + caps + ((size_t)1 << 18)),  // (4 W more: the column classes read back early by shard_intt)
+       "alloc pinned staging");
+  }
+  return P2GPU_OK;
+}
+
+// where the constants and sigma tables of a new handle come from: a circuit blob in host memory (p2gpu_circuit_create),
+// or the build on the device from gate rows and copy pairs (p2gpu_circuit_build, build.hip)
+struct TableSource {
+  const gl_t *constants = nullptr, *sigmas = nullptr;  // host, [NC][n] and [R][n]
+  const BuildInputs *build = nullptr;
+};
+
+// the constants_sigmas commitment (the prover-side part of `build()`).  A blob commits to its own constant columns, canonical
+// selector values or not; a device build to the selector columns of d_row_gate.
+int commit_constants_sigmas(p2gpu_circuit *c, const TableSource &src) {
+  hipStream_t st = c->stream;
+  const size_t n = c->n;
+  const uint32_t ncs = c->NC + c->R;
+  // stage values [constants | sigmas] in the wires buffer region of the cs LDE (reuse cs.lde as scratch)
+  gl_t *stage = c->cs.lde.p;
+  if (src.build) {
+    build_selector_columns(st, c, stage);
+    if (c->NC > c->num_selectors)
+      CK(hipMemcpyAsync(stage + (size_t)c->num_selectors * n, c->d_gconsts.p, 8 * (size_t)(c->NC - c->num_selectors) * n, hipMemcpyDeviceToDevice, st),
+         "copy constants");
+  } else {
+    CK(hipMemcpyAsync(stage, src.constants, 8 * (size_t)c->NC * n, hipMemcpyHostToDevice, st), "copy constants");
+  }
+  CK(hipMemcpyAsync(stage + (size_t)c->NC * n, c->d_sigmas.p, 8 * (size_t)c->R * n, hipMemcpyDeviceToDevice, st), "copy sigmas");
+  ntt_batch(st, c->plan_inv, stage, c->cs.coeffs.p, ncs, 1, nullptr, gl_inv((gl_t)n), false);
+  return batch_commit_from_coeffs(c, c->cs);
+}
+
+int check_cap_and_digest(p2gpu_circuit *c, const uint8_t *cap_in) {
+  if (cap_in) {
+    for (size_t i = 0; i < c->cs.cap.size(); i++)
+      if (memcmp(cap_in + 32 * i, c->cs.cap[i].w, c->hasher ? 32 : 25)) { set_err("constants_sigmas cap mismatch"); return P2GPU_E_CAP_MISMATCH; }
+  }
+  if (!(c->flags & 1)) {
+    // circuit_builder.rs build(): H::hash_no_pad(cap.flatten() || hash_pad([]).to_vec() || [degree_bits])  (pinned: tests/test_reference_proofs.py)
+    std::vector<gl_t> parts;
+    for (auto &dg : c->cs.cap) {
+      gl_t e[4];
+      digest_elems(dg, e);
+      parts.insert(parts.end(), e, e + 4);
+    }
+    std::vector<gl_t> pad(8, 0);  // hash_pad([]): pad10*1 to the sponge rate
+    pad[0] = 1;
+    pad[7] = 1;
+    dig_t ds = host_hash_no_pad(pad);
+    gl_t e[4];
+    digest_elems(ds, e);
+    parts.insert(parts.end(), e, e + 4);
+    parts.push_back(c->d);
+    c->circuit_digest = host_hash_no_pad(parts);
+  }
+  return P2GPU_OK;
+}
+
+// c is parsed and has its device: schedules the gate groups, makes the device state, commits constants and sigmas.  The caller owns
+// c (HalfBuilt): every refusal here is set_err and a return.
+int circuit_finish(p2gpu_circuit *c, const TableSource &src, const uint8_t *cap_in) {
+  schedule_gates(c);
+  CK(hipSetDevice(c->device), "hipSetDevice");
+  const CreateTrace tr{c, now_ms()};
+  if (int rc = make_streams(c)) return rc;
+  tr.mark("streams + poseidon constants");
+  if (int rc = make_root_tables(c)) return rc;
+  tr.mark("root tables + ntt plans");
+  // common to both forms of the table phase: k_is and the gate table before it, the Poseidon round constants after it
+  const uint32_t ngc = c->NC - c->num_selectors;
+  CK(hipMemcpyAsync(c->d_kis.p, c->k_is.data(), 8 * (size_t)c->R, hipMemcpyHostToDevice, c->stream), "copy kis");
+  if (c->num_gates)
+    CK(hipMemcpyAsync(c->d_gates.p, c->gates.data(), sizeof(GateDesc) * c->num_gates, hipMemcpyHostToDevice, c->stream), "copy gates");
+  CK(c->d_row_gate.alloc(c->n), "alloc row_gate");
+  CK(c->d_gconsts.alloc((size_t)(ngc ? ngc : 1) * c->n), "alloc gconsts");
+  CK(c->d_prc.alloc(360), "alloc prc");
+  if (int rc = src.build ? build_device_tables(c, *src.build, tr) : tables_from_blob(c, src.constants, src.sigmas)) return rc;
+  CK(hipMemcpy(c->d_prc.p, c->poseidon_rc, sizeof c->poseidon_rc, hipMemcpyHostToDevice), "copy prc");
+  gl_t hrc[360];
+  poseidon_device_constants(c->poseidon_rc, hrc);
+  CK(c->d_prc_hash.alloc(360), "alloc prc (hash form)");
+  CK(hipMemcpy(c->d_prc_hash.p, hrc, sizeof hrc, hipMemcpyHostToDevice), "copy prc (hash form)");
+  tr.mark("sigma/constant uploads, row->gate");
+  if (int rc = alloc_proof_buffers(c)) return rc;
+  tr.mark("batch + work buffer allocation");
+  if (int rc = commit_constants_sigmas(c, src)) return rc;
+  if (int rc = check_cap_and_digest(c, cap_in)) return rc;
+  CK(hipStreamSynchronize(c->stream), "sync");
+  tr.mark("constants_sigmas commitment");
+  return P2GPU_OK;
+}
+#undef CK
+
+int circuit_create_one(const uint8_t *blob, size_t len, int device, p2gpu_circuit **out_c) try {
+  HalfBuilt c(new p2gpu_circuit());
+  size_t off = 0;
+  const uint8_t *cap_in = nullptr;
+  c->device = device;
+  if (int rc = circuit_parse(blob, len, c.get(), &off, &cap_in)) return rc;
+  c->blob_prefix.assign(blob, blob + off);
+  if (len < off + 8 * ((size_t)c->NC * c->n + (size_t)c->R * c->n)) { set_err("blob truncated (tables)"); return P2GPU_E_BLOB; }
+  TableSource src;
+  src.constants = (const gl_t *)(blob + off);
+  src.sigmas = src.constants + (size_t)c->NC * c->n;
+  if (int rc = circuit_finish(c.get(), src, cap_in)) return rc;
+  *out_c = c.release();
+  return P2GPU_OK;
+} P2GPU_CATCH
+
+// ---- build() on the device: gate rows + copy pairs -> handle (the tables come from build.hip, not from a blob) ----
+struct BuildCall {
+  const p2gpu_build_params *bp;
+  const p2gpu_gate_decl *gates;
+  uint32_t num_gates;
+  BuildInputs in;
+  std::vector<uint8_t> prefix;
+};
+// the checks that need no device, in p2gpu_build_blob's order, and the blob prefix
+int build_call_prepare(BuildCall &b, const p2gpu_build_params *bp, const p2gpu_gate_decl *gates, uint32_t num_gates, const uint32_t *row_gate,
+                       const uint64_t *row_constants, const uint32_t *copies, size_t num_copies, uint32_t hasher, p2gpu_circuit **out_c) {
+  if (out_c) *out_c = nullptr;
+  if (!bp || !gates || !row_gate || !out_c || (num_copies && !copies)) return P2GPU_E_ARG;
+  if (hasher > 1) { set_err("unsupported hasher (0 = KeccakHash<25>, 1 = PoseidonHash)"); return P2GPU_E_ARG; }
+  BuildPlan pl;
+  if (int rc = build_plan(bp, gates, num_gates, row_constants != nullptr, pl)) return rc;
+  b.prefix.resize(pl.prefix_len);
+  if (int rc = build_prefix(pl, bp, gates, hasher, b.prefix.data())) return rc;
+  b.bp = bp; b.gates = gates; b.num_gates = num_gates;
+  b.in = BuildInputs{row_gate, row_constants, copies, num_copies};
+  return P2GPU_OK;
+}
+int circuit_build_one(const BuildCall &b, int device, p2gpu_circuit **out_c) try {
+  HalfBuilt c(new p2gpu_circuit());
+  c->device = device;
+  size_t off = 0;
+  const uint8_t *cap_in = nullptr;
+  if (int rc = circuit_parse(b.prefix.data(), b.prefix.size(), c.get(), &off, &cap_in))
+    return rc == P2GPU_E_BLOB ? P2GPU_E_ARG : rc;  // (no blob here: the parameters themselves are what circuit_parse refused)
+  c->blob_prefix = b.prefix;
+  TableSource src;
+  src.build = &b.in;
+  if (int rc = circuit_finish(c.get(), src, nullptr)) return rc;
+  *out_c = c.release();
+  return P2GPU_OK;
+} P2GPU_CATCH
+}  // namespace
 
 extern "C" {
 
@@ -201,15 +606,6 @@ int p2gpu_device_info(char *name_out, size_t name_cap, int *cu_count, size_t *hb
 
 static int shard_layout(p2gpu_circuit *c, int rank, int world);
 static int shard_args_ok(p2gpu_circuit *c, int rank, int world);
-static int circuit_create_one(const uint8_t *blob, size_t len, int device, p2gpu_circuit **out_c);
-// where the constants and sigma tables of a new handle come from: a circuit blob in host memory (p2gpu_circuit_create),
-// or the build on the device from gate rows and copy pairs (p2gpu_circuit_build, build.hip)
-struct TableSource {
-  const gl_t *constants = nullptr, *sigmas = nullptr;  // host, [NC][n] and [R][n]
-  const BuildInputs *build = nullptr;
-  bool truncated = false;  // the blob ends before its tables do
-};
-static int circuit_finish(p2gpu_circuit *c, const TableSource &src, const uint8_t *cap_in, p2gpu_circuit **out_c);
 
 
 // A plain (un-sharded) handle on ONE device of the p2gpu_init list, whatever the length of that list: with several ids
@@ -297,44 +693,6 @@ int p2gpu_circuit_create(const uint8_t *blob, size_t len, p2gpu_circuit **out_c)
   return circuit_make([&](int device, p2gpu_circuit **h) { return circuit_create_one(blob, len, device, h); }, out_c);
 } P2GPU_CATCH
 
-// ---- build() on the device: gate rows + copy pairs -> handle (the tables come from build.hip, not from a blob) ----
-namespace {
-struct BuildCall {
-  const p2gpu_build_params *bp;
-  const p2gpu_gate_decl *gates;
-  uint32_t num_gates;
-  BuildInputs in;
-  std::vector<uint8_t> prefix;
-};
-// the checks that need no device, in p2gpu_build_blob's order, and the blob prefix
-int build_call_prepare(BuildCall &b, const p2gpu_build_params *bp, const p2gpu_gate_decl *gates, uint32_t num_gates, const uint32_t *row_gate,
-                       const uint64_t *row_constants, const uint32_t *copies, size_t num_copies, uint32_t hasher, p2gpu_circuit **out_c) {
-  if (out_c) *out_c = nullptr;
-  if (!bp || !gates || !row_gate || !out_c || (num_copies && !copies)) return P2GPU_E_ARG;
-  if (hasher > 1) { set_err("unsupported hasher (0 = KeccakHash<25>, 1 = PoseidonHash)"); return P2GPU_E_ARG; }
-  BuildPlan pl;
-  if (int rc = build_plan(bp, gates, num_gates, row_constants != nullptr, pl)) return rc;
-  b.prefix.resize(pl.prefix_len);
-  if (int rc = build_prefix(pl, bp, gates, hasher, b.prefix.data())) return rc;
-  b.bp = bp; b.gates = gates; b.num_gates = num_gates;
-  b.in = BuildInputs{row_gate, row_constants, copies, num_copies};
-  return P2GPU_OK;
-}
-int circuit_build_one(const BuildCall &b, int device, p2gpu_circuit **out_c) {
-  p2gpu_circuit *c = new p2gpu_circuit();
-  size_t off = 0;
-  const uint8_t *cap_in = nullptr;
-  if (int rc = circuit_parse(b.prefix.data(), b.prefix.size(), c, &off, &cap_in)) {
-    delete c;
-    return rc == P2GPU_E_BLOB ? P2GPU_E_ARG : rc;  // (no blob here: the parameters themselves are what circuit_parse refused)
-  }
-  c->device = device;
-  c->blob_prefix = b.prefix;
-  TableSource src;
-  src.build = &b.in;
-  return circuit_finish(c, src, nullptr, out_c);
-}
-}  // namespace
 
 int p2gpu_circuit_build_on(const p2gpu_build_params *bp, const p2gpu_gate_decl *gates, uint32_t num_gates, const uint32_t *row_gate,
                            const uint64_t *row_constants, const uint32_t *copies, size_t num_copies, uint32_t hasher, int device_id,
@@ -392,374 +750,6 @@ int p2gpu_circuit_export_blob(const p2gpu_circuit *cc, uint8_t *out, size_t *len
   return P2GPU_OK;
 } P2GPU_CATCH
 
-static int circuit_create_one(const uint8_t *blob, size_t len, int device, p2gpu_circuit **out_c) try {
-  p2gpu_circuit *c = new p2gpu_circuit();
-  size_t off = 0;
-  const uint8_t *cap_in = nullptr;
-  if (int rc = circuit_parse(blob, len, c, &off, &cap_in)) {
-    delete c;
-    return rc;
-  }
-  c->device = device;
-  c->blob_prefix.assign(blob, blob + off);
-  TableSource src;
-  src.truncated = len < off + 8 * ((size_t)c->NC * c->n + (size_t)c->R * c->n);  // (reported where it always was: after the gate groups)
-  src.constants = (const gl_t *)(blob + off);
-  src.sigmas = src.constants + (size_t)c->NC * c->n;
-  return circuit_finish(c, src, cap_in, out_c);
-} P2GPU_CATCH
-
-// Takes ownership of c (parsed, device chosen): schedules the gate groups, makes the device state, commits constants and sigmas.
-static int circuit_finish(p2gpu_circuit *c, const TableSource &src, const uint8_t *cap_in, p2gpu_circuit **out_c) try {
-  auto fail = [&](int rc, const char *msg) {
-    set_err("%s", msg);
-    circuit_release(c);
-    delete c;
-    return rc;
-  };
-  c->nterms = c->K + c->K * c->nchunks + c->max_gate_constraints;
-  {
-    // heavy gate mixes: split the gates over 4 waves that share a row tile (plonk.hip); greedy
-    // balance by an estimate of modmuls per row, group 0 starts with the permutation argument
-    // (a PoseidonGate is not part of this: it has its own kernel, plonk.hip poseidon_gate_kernel)
-    auto cost = [](const GateDesc &g) { return g.kind == G_POSEIDON ? 0u : 4u * g.num_constraints + 8u; };
-    const uint32_t perm_cost = (uint32_t)env_uint("P2GPU_PERM_COST", 8u * c->R + 100u);  // balance experiments only
-    uint32_t total = 0;
-    for (auto &g : c->gates) total += cost(g);
-    c->gate_groups = env_uint("P2GPU_GATE_GROUPS", total > 2 * perm_cost ? 4u : 1u) == 4 ? 4u : 1u;
-    uint32_t load[4] = {perm_cost, 0, 0, 0};
-    std::vector<uint32_t> order(c->gates.size());
-    for (size_t i = 0; i < order.size(); i++) order[i] = (uint32_t)i;
-    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return cost(c->gates[x]) > cost(c->gates[y]); });
-    for (uint32_t gi : order) {
-      uint32_t best = 0;
-      for (uint32_t q = 1; q < 4; q++)
-        if (load[q] < load[best]) best = q;
-      c->gates[gi].pad = c->gate_groups == 4 ? best : 0;
-      load[best] += cost(c->gates[gi]);
-    }
-    // Gates of degree <= 4 with enough constraints to pay for two transforms per challenge: evaluated on the even cosets only
-    // (plonk.hip gate_sums_kernel).  The degree is the library's own count (gate_degree), not the blob's field.
-    uint64_t half_constraints = 0;
-    // P2GPU_HALF_GATES=0: off (A/B measurements); the knob "half_gates" does the same per handle
-    if (env_flag("P2GPU_HALF_GATES", true) && c->d >= 6 && c->rate_bits == 3)
-      for (auto &g : c->gates)
-        if (g.kind != G_POSEIDON && g.num_constraints >= 48 && gate_degree(g.kind, g.p) <= 4 && c->half_slots < 64) {
-          g.pad |= (++c->half_slots) << 16;
-          half_constraints += g.num_constraints;
-        }
-    // Worth it by default only where it saves more than its five extra launches cost a lone proof: ~77 lane-instructions per
-    // constraint on 4n rows at 37.7 T/s against ~100 us -- constraints x n >= 12 M (the heavy mix: from 2^14 gates on).  The knob
-    // "half_gates" = 2 takes the route whatever the size (tests).
-    c->half_auto = (half_constraints << c->d) >= ((uint64_t)12 << 20);
-    if (c->half_slots) {
-      // the main kernel without them: a look-up and two products per gate and challenge
-      auto cost_main = [&](const GateDesc &g) { return gate_half_slot(g) ? 8u : cost(g); };
-      uint32_t rest = 0;
-      for (auto &g : c->gates) rest += cost_main(g);
-      // (P2GPU_GATE_GROUPS_HALF, P2GPU_SUMS_GROUPS: balance experiments only)
-      c->gate_groups_half = env_uint("P2GPU_GATE_GROUPS_HALF", rest > 2 * perm_cost ? 4u : 1u) == 4 ? 4u : 1u;
-      uint32_t lm[4] = {perm_cost, 0, 0, 0}, ls[4] = {0, 0, 0, 0};
-      c->sums_groups = env_uint("P2GPU_SUMS_GROUPS", c->half_slots >= 2 ? 4u : 1u) == 4 ? 4u : 1u;
-      for (uint32_t gi : order) {
-        GateDesc &g = c->gates[gi];
-        uint32_t bm = 0, bs = 0;
-        for (uint32_t q = 1; q < 4; q++) {
-          if (lm[q] < lm[bm]) bm = q;
-          if (ls[q] < ls[bs]) bs = q;
-        }
-        if (c->gate_groups_half == 4) g.pad |= bm << 4;
-        lm[bm] += cost_main(g);
-        if (gate_half_slot(g)) {
-          if (c->sums_groups == 4) g.pad |= bs << 8;
-          ls[bs] += cost(g);
-        }
-      }
-    }
-  }
-  const size_t n = c->n;
-  if (src.truncated) return fail(P2GPU_E_BLOB, "blob truncated (tables)");
-  const gl_t *k_is = c->k_is.data();
-  const gl_t *constants = src.constants, *sigmas = src.sigmas;
-
-  // ---- device state ----
-  auto H = [&](hipError_t e, const char *what) -> int {
-    if (e == hipSuccess) return 0;
-    set_err("%s: %s", what, hipGetErrorString(e));
-    return P2GPU_E_DEVICE;
-  };
-#define CK(e, what)                                   \
-  if (H((e), what)) {                                 \
-    std::string keep = last_error_copy();                         \
-    circuit_release(c);                               \
-    delete c;                                         \
-    last_error_restore(keep);                                     \
-    return P2GPU_E_DEVICE;                            \
-  }
-  CK(hipSetDevice(c->device), "hipSetDevice");
-  const double t_create0 = now_ms();
-  auto mark = [&](const char *label) {  // P2GPU_TRACE=1: where circuit creation spends its time
-    if (!trace_on()) return;
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    fprintf(stderr, "[p2gpu] create %-28s +%.2f ms\n", label, now_ms() - t_create0);
-  };
-  if (poseidon_upload_constants()) return fail(P2GPU_E_DEVICE, "uploading Poseidon constants failed");
-  CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking), "hipStreamCreate");
-  CK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking), "hipStreamCreate");
-  mark("streams + poseidon constants");
-  hipStream_t st = c->stream;
-  const uint32_t d = c->d, K = c->K, C = c->C;
-  const uint32_t ncs = c->NC + c->R, nzp = K * (1 + c->PP), nq = K * c->QF;
-  const uint32_t nall = ncs + c->W + nzp + nq;
-  const size_t half = n >= 2 ? n / 2 : 1;
-  CK(c->tw_fwd.alloc(half), "alloc tw");
-  CK(c->tw_inv.alloc(half), "alloc tw");
-  CK(c->scale.alloc((size_t)C * n), "alloc scale");
-  CK(c->inv_scale.alloc((size_t)C * n), "alloc scale");
-  CK(c->fri_scale.alloc((size_t)C * n), "alloc scale");
-  CK(c->d_kis.alloc(c->R), "alloc kis");
-  CK(c->d_sigmas.alloc((size_t)c->R * n), "alloc sigmas");
-  CK(c->d_gates.alloc(c->num_gates ? c->num_gates : 1), "alloc gates");
-  gl_t wn = gl_root(d), wN = gl_root(d + c->rate_bits);
-  c->plan_inv = ntt_plan_create(st, d, 0, true);
-  c->plan_fwd = ntt_plan_create(st, d, 1, false);
-  if (!c->plan_inv || !c->plan_fwd) return fail(P2GPU_E_DEVICE, "ntt plan allocation failed");
-  fill_powers(st, c->tw_fwd.p, wn, (uint32_t)half);
-  fill_powers(st, c->tw_inv.p, gl_inv(wn), (uint32_t)half);
-  fill_coset_scale(st, c->scale.p, GL_GEN, wN, d, C, 1);
-  fill_coset_scale(st, c->inv_scale.p, gl_inv(GL_GEN), gl_inv(wN), d, C, 1);
-  if (c->half_slots) {
-    const size_t per = (size_t)4 * c->half_slots * K * n;
-    CK(c->hsum.alloc(2 * per), "alloc gate sums");
-    CK(c->htmp_a.alloc(per), "alloc gate sums");
-    CK(c->htmp_b.alloc(per), "alloc gate sums");
-    // F[m'][m] = 1/4 sum_j w_8^((2 m' + 1 - 2 m) j): even cosets' interpolants -> odd cosets' coefficient arrays
-    const gl_t w8 = gl_root(3), quarter = gl_inv(4);
-    for (int mo = 0; mo < 4; mo++)
-      for (int m = 0; m < 4; m++) {
-        const gl_t base = gl_pow(w8, (uint64_t)((2 * mo + 1 - 2 * m + 16) % 8));
-        gl_t acc = 0, pw = 1;
-        for (int j = 0; j < 4; j++) {
-          acc = gl_add(acc, pw);
-          pw = gl_mul(pw, base);
-        }
-        c->half_cross[4 * mo + m] = gl_mul(acc, quarter);
-      }
-  }
-  CK(c->qconst.alloc(24), "alloc qconst");
-  {
-    // ZeroPolyOnCoset: Z_H on the LDE coset has period 2^rate_bits
-    gl_t qc[24];
-    memset(qc, 0, sizeof qc);
-    gl_t wC = gl_root(c->rate_bits), gn = gl_pow(GL_GEN, n);
-    for (uint32_t r = 0; r < C; r++) {
-      qc[r] = gl_mul(GL_GEN, gl_pow(wN, r));
-      qc[8 + r] = gl_sub(gl_mul(gn, gl_pow(wC, r)), 1);
-      qc[16 + r] = gl_inv(qc[8 + r]);
-    }
-    CK(hipMemcpy(c->qconst.p, qc, sizeof qc, hipMemcpyHostToDevice), "copy qconst");
-    CK(c->l0_lde.alloc((size_t)C * n), "alloc L0 table");
-    fill_l0_table(st, c->qconst.p, c->tw_fwd.p, 0, d, C, gl_inv((gl_t)n), c->l0_lde.p);
-  }
-  mark("root tables + ntt plans");
-  CK(hipMemcpyAsync(c->d_kis.p, k_is, 8 * (size_t)c->R, hipMemcpyHostToDevice, st), "copy kis");
-  if (!src.build) CK(hipMemcpyAsync(c->d_sigmas.p, sigmas, 8 * (size_t)c->R * n, hipMemcpyHostToDevice, st), "copy sigmas");
-  if (c->num_gates)
-    CK(hipMemcpyAsync(c->d_gates.p, c->gates.data(), sizeof(GateDesc) * c->num_gates, hipMemcpyHostToDevice, st), "copy gates");
-  {
-    const uint32_t ngc = c->NC - c->num_selectors;
-    CK(c->d_row_gate.alloc(n), "alloc row_gate");
-    CK(c->d_gconsts.alloc((size_t)(ngc ? ngc : 1) * n), "alloc gconsts");
-    CK(c->d_prc.alloc(360), "alloc prc");
-    if (src.build) {
-      // build() on the device: row -> gate as given, gate constants, special rows and sigma from kernels (build.hip); its
-      // scratch is gone again before the per-proof buffers below are allocated
-      struct MarkCtx { decltype(mark) *m; } mc{&mark};
-      if (int rc = build_device_tables(c, *src.build, [](void *ctx, const char *label) { (*((MarkCtx *)ctx)->m)(label); }, &mc)) {
-        std::string keep = last_error_copy();
-        circuit_release(c);
-        delete c;
-        last_error_restore(keep);
-        return rc;
-      }
-    } else {
-      // row -> gate (the one selector column that is not UNUSED holds the index) and the gate
-      // constants, for the row-local witness generators (p2gpu_fill_witness)
-      std::vector<uint8_t> rg(n, 0);
-      for (size_t row = 0; row < n; row++) {
-        uint32_t gi = 0;
-        for (uint32_t s = 0; s < c->num_selectors; s++) {
-          gl_t v = constants[(size_t)s * n + row];
-          if (c->num_selectors == 1 || v != 0xFFFFFFFFULL) gi = (uint32_t)v;
-        }
-        if (gi >= c->num_gates) return fail(P2GPU_E_BLOB, "selector column holds an unknown gate index");
-        rg[row] = (uint8_t)gi;
-        if (c->sparse_row == UINT32_MAX && c->gates[gi].kind == G_PUBLIC_INPUT) c->sparse_row = (uint32_t)row;
-      }
-      // the special rows of the column classification: the PublicInputGate row first, then the PoseidonGate rows
-      c->sparse_rows = SparseRows();
-      if (c->sparse_row != UINT32_MAX) {
-        c->sparse_rows.row[c->sparse_rows.count++] = c->sparse_row;
-        for (size_t row = 0; row < n && c->sparse_rows.count < MAX_SPARSE_ROWS; row++)
-          if (c->gates[rg[row]].kind == G_POSEIDON) c->sparse_rows.row[c->sparse_rows.count++] = (uint32_t)row;
-      }
-      CK(hipMemcpy(c->d_row_gate.p, rg.data(), n, hipMemcpyHostToDevice), "copy row_gate");
-      if (ngc)
-        CK(hipMemcpy(c->d_gconsts.p, constants + (size_t)c->num_selectors * n, 8 * (size_t)ngc * n, hipMemcpyHostToDevice), "copy gconsts");
-    }
-    CK(hipMemcpy(c->d_prc.p, c->poseidon_rc, sizeof c->poseidon_rc, hipMemcpyHostToDevice), "copy prc");
-    {
-      gl_t hrc[360];
-      poseidon_device_constants(c->poseidon_rc, hrc);
-      CK(c->d_prc_hash.alloc(360), "alloc prc (hash form)");
-      CK(hipMemcpy(c->d_prc_hash.p, hrc, sizeof hrc, hipMemcpyHostToDevice), "copy prc (hash form)");
-    }
-  }
-  mark("sigma/constant uploads, row->gate");
-  if (batch_alloc(c, c->cs, ncs) || batch_alloc(c, c->wires, c->W) || batch_alloc(c, c->zp, nzp) || batch_alloc(c, c->quot, nq)) {
-    std::string keep = last_error_copy();
-    circuit_release(c);
-    delete c;
-    last_error_restore(keep);
-    return P2GPU_E_DEVICE;
-  }
-  CK(c->wires_vals.alloc((size_t)c->W * n), "alloc wires");
-  CK(c->wire_nz.alloc(c->W), "alloc wire flags");
-  CK(c->wire_nzlist.alloc(c->W + 1), "alloc wire flags");
-  CK(c->wire_clean.alloc(c->W), "alloc wire flags");
-  CK(hipMemsetAsync(c->wire_clean.p, 0, sizeof(uint32_t) * c->W, c->stream), "clear wire flags");
-  CK(c->wire_scalar.alloc((size_t)MAX_SPARSE_ROWS * c->W), "alloc wire flags");
-  if (c->sparse_row != UINT32_MAX) {
-    // inverse transform and LDE (all cosets) of the unit column of the PublicInputGate row: what a wire that is
-    // zero everywhere but there transforms to, up to its scalar -- and the same for the PoseidonGate rows
-    // (sparse_rows: columns that are zero outside these rows are their linear combination, class 3)
-    const uint32_t nr = c->sparse_rows.count;
-    CK(c->sparse_coeffs.alloc((size_t)nr * n), "alloc sparse basis");
-    CK(c->sparse_lde.alloc((size_t)nr * C * n), "alloc sparse basis");
-    CK(c->sparse_partial.alloc(16 * 2 + 2), "alloc sparse basis");
-    const gl_t one = 1;
-    CK(hipMemsetAsync(c->sparse_coeffs.p, 0, 8 * (size_t)nr * n, st), "sparse basis");
-    for (uint32_t s = 0; s < nr; s++)
-      CK(hipMemcpyAsync(c->sparse_coeffs.p + (size_t)s * n + c->sparse_rows.row[s], &one, 8, hipMemcpyHostToDevice, st), "sparse basis");
-    CK(hipStreamSynchronize(st), "sparse basis");  // `one` lives on this stack frame
-    ntt_batch(st, c->plan_inv, c->sparse_coeffs.p, c->sparse_coeffs.p, nr, 1, nullptr, gl_inv((gl_t)n), false);
-    for (uint32_t s = 0; s < nr; s++)  // [rows][C][n]: one column per launch keeps every row's cosets together
-      ntt_batch(st, c->plan_fwd, c->sparse_coeffs.p + (size_t)s * n, c->sparse_lde.p + (size_t)s * C * n, 1, C, c->scale.p, 1, false);
-  }
-  CK(c->zp_vals.alloc((size_t)nzp * n), "alloc zp");
-  CK(c->cp.alloc((size_t)K * (c->nchunks + 1) * n), "alloc cp");  // chunk quotients + the row products behind them (ZsArgs::cp)
-  CK(c->scan_tmp.alloc((size_t)K * (n + (n + 255) / 256 + 8)), "alloc scan");
-  CK(c->apow.alloc((size_t)2 * c->nterms), "alloc apow");
-  CK(c->qvals.alloc((size_t)K * C * n), "alloc qvals");
-  CK(c->qtmp.alloc((size_t)K * C * n), "alloc qtmp");
-  CK(c->pw.alloc((size_t)4 * n), "alloc pw");
-  CK(c->partial.alloc(((size_t)(nall + K) + 8) * 16 * 2), "alloc partial");  // (+8 columns: a sharded proof gathers equal blocks per rank)
-  CK(c->ext_apow.alloc((size_t)2 * nall), "alloc ext_apow");
-  CK(c->f01.alloc((size_t)4 * n), "alloc f01");
-  CK(c->f01v.alloc((size_t)4 * n), "alloc f01v");
-  CK(c->fv.alloc((size_t)2 * n), "alloc fv");
-  c->fri_coef.resize(c->n_steps + 1);
-  c->fri_vals.resize(c->n_steps + 1);
-  c->fri_trees.resize(c->n_steps);
-  size_t gather_words = 0;
-  {
-    uint32_t ds = d;
-    const size_t cap_per = ((size_t)1 << c->cap_h) >> c->rate_bits;
-    for (uint32_t s = 0; s <= c->n_steps; s++) {
-      c->fri_plans.push_back(s == 0 ? c->plan_fwd : ntt_plan_create(st, ds, 1, false));
-      if (!c->fri_plans.back()) return fail(P2GPU_E_DEVICE, "ntt plan allocation failed");
-      CK(c->fri_coef[s].alloc((size_t)2 << ds), "alloc fri coef");
-      if (s < c->n_steps) {
-        CK(c->fri_vals[s].alloc((size_t)2 * C << ds), "alloc fri vals");
-        uint32_t ab = c->arity[s];
-        if (ab < 1 || ab > 4 || ds < ab || (((size_t)1 << ds) >> ab) < cap_per) {
-          return fail(P2GPU_E_BLOB, "unsupported FRI reduction arity");
-        }
-        if (tree_alloc(c->fri_trees[s], C, ((size_t)1 << ds) >> ab, cap_per)) {
-          std::string keep = last_error_copy();
-          circuit_release(c);
-          delete c;
-          last_error_restore(keep);
-          return P2GPU_E_DEVICE;
-        }
-        gather_words += (2u << ab) + 4 * (size_t)(ds + c->rate_bits);
-        ds -= ab;
-      }
-    }
-  }
-  gather_words += nall + 4 * 4 * (size_t)(d + c->rate_bits);
-  c->gather_cap = gather_words * c->num_queries + 64;
-  CK(c->gather_ptrs.alloc(c->gather_cap), "alloc gather");
-  CK(c->gather_out.alloc(c->gather_cap), "alloc gather");
-  CK(c->pow_result.alloc(1), "alloc pow");
-  // pinned host arena for every small transcript transfer of a proof (caps, opening partials, challenge
-  // powers, final polynomial, PoW result, query gather): with pageable memory each of those
-  // hipMemcpyAsync calls blocks in a staging copy and the following stream sync costs another ~10 us
-  {
-    size_t n_final = n;
-    for (uint32_t s = 0; s < c->n_steps; s++) n_final >>= c->arity[s];
-    // per proof: 3 + n_steps trees stage their caps (2^cap_h digests each, twice when sharded: local roots + gathered),
-    // the alpha powers of the openings (2 * nall words), the opening partials, the final polynomial, the query gather
-    const size_t caps = (size_t)2 * (4 + c->n_steps) * (sizeof(dig_t) << c->cap_h);
-    CK(c->pin.alloc(16 * c->gather_cap + 32 * n_final + 16 * (size_t)(nall + K) * 16 + 16 * (size_t)nall + 16 * (size_t)c->nterms +
-                    20 * (size_t)c->W + caps + ((size_t)1 << 18)),  // (4 W more: the column classes read back early by shard_intt)
-       "alloc pinned staging");
-  }
-
-  mark("batch + work buffer allocation");
-  // ---- constants_sigmas commitment (the prover-side part of `build()`) ----
-  {
-    // stage values [constants | sigmas] in the wires buffer region of the cs LDE (reuse cs.lde as scratch)
-    gl_t *stage = c->cs.lde.p;
-    if (src.build) {
-      build_selector_columns(st, c, stage);
-      if (c->NC > c->num_selectors)
-        CK(hipMemcpyAsync(stage + (size_t)c->num_selectors * n, c->d_gconsts.p, 8 * (size_t)(c->NC - c->num_selectors) * n, hipMemcpyDeviceToDevice, st),
-           "copy constants");
-    } else {
-      CK(hipMemcpyAsync(stage, constants, 8 * (size_t)c->NC * n, hipMemcpyHostToDevice, st), "copy constants");
-    }
-    CK(hipMemcpyAsync(stage + (size_t)c->NC * n, c->d_sigmas.p, 8 * (size_t)c->R * n, hipMemcpyDeviceToDevice, st), "copy sigmas");
-    {
-      gl_t ninv = gl_inv((gl_t)n);
-      ntt_batch(st, c->plan_inv, stage, c->cs.coeffs.p, ncs, 1, nullptr, ninv, false);
-    }
-    if (int rc = batch_commit_from_coeffs(c, c->cs)) {
-      std::string keep = last_error_copy();
-      circuit_release(c);
-      delete c;
-      last_error_restore(keep);
-      return rc;
-    }
-  }
-  if (cap_in) {
-    for (size_t i = 0; i < c->cs.cap.size(); i++)
-      if (memcmp(cap_in + 32 * i, c->cs.cap[i].w, c->hasher ? 32 : 25)) return fail(P2GPU_E_CAP_MISMATCH, "constants_sigmas cap mismatch");
-  }
-  if (!(c->flags & 1)) {
-    // circuit_builder.rs build(): H::hash_no_pad(cap.flatten() || hash_pad([]).to_vec() || [degree_bits])  (pinned: tests/test_reference_proofs.py)
-    std::vector<gl_t> parts;
-    for (auto &dg : c->cs.cap) {
-      gl_t e[4];
-      digest_elems(dg, e);
-      parts.insert(parts.end(), e, e + 4);
-    }
-    std::vector<gl_t> pad(8, 0);  // hash_pad([]): pad10*1 to the sponge rate
-    pad[0] = 1;
-    pad[7] = 1;
-    dig_t ds = host_hash_no_pad(pad);
-    gl_t e[4];
-    digest_elems(ds, e);
-    parts.insert(parts.end(), e, e + 4);
-    parts.push_back(d);
-    c->circuit_digest = host_hash_no_pad(parts);
-  }
-  CK(hipStreamSynchronize(st), "sync");
-  mark("constants_sigmas commitment");
-#undef CK
-  *out_c = c;
-  return P2GPU_OK;
-} P2GPU_CATCH
 
 
 
@@ -1000,7 +990,8 @@ int p2gpu_commit_values(const uint64_t *vals, size_t ncols, unsigned d, unsigned
   if (int rc = ensure_device()) return rc;
   if (!vals || !cap_out || d > 24 || rate_bits > 3 || cap_h < rate_bits || cap_h > rate_bits + d) return P2GPU_E_ARG;
   // a throw-away circuit-like context with just the tables and one batch
-  p2gpu_circuit *c = new p2gpu_circuit();
+  HalfBuilt own(new p2gpu_circuit());
+  p2gpu_circuit *c = own.get();
   c->d = d; c->rate_bits = rate_bits; c->cap_h = cap_h; c->n = (size_t)1 << d; c->N = c->n << rate_bits;
   c->C = 1u << rate_bits; c->device = g_device; c->n_steps = 0;
   int rc = P2GPU_OK;
@@ -1030,8 +1021,6 @@ int p2gpu_commit_values(const uint64_t *vals, size_t ncols, unsigned d, unsigned
     if ((rc = batch_commit_from_values(c, c->wires, c->wires_vals.p))) break;
     for (size_t i = 0; i < c->wires.cap.size(); i++) memcpy(cap_out + 25 * i, c->wires.cap[i].w, 25);
   } while (0);
-  circuit_release(c);
-  delete c;
   return rc;
 } P2GPU_CATCH
 

@@ -5,6 +5,7 @@
 #include "transport.hpp"
 #include <algorithm>
 #include <cstdio>
+#include <memory>
 #include <string>
 #include <thread>
 #include <utility>
@@ -85,9 +86,21 @@ struct BuildInputs {
   const uint32_t *copies;          // [num_copies][4]
   size_t num_copies;
 };
-// Fills d_row_gate, d_gconsts, d_sigmas and the special rows of a handle whose root tables, k_is and gate table are
-// enqueued on c->stream; every scratch buffer is gone when it returns.  mark: the P2GPU_TRACE marks of circuit creation.
-int build_device_tables(p2gpu_circuit *c, const BuildInputs &in, void (*mark)(void *, const char *), void *mark_ctx);
+// P2GPU_TRACE=1: where circuit creation spends its time.  t0 is taken once the device is selected; every mark waits for the
+// handle's stream first, so its figure covers the device work enqueued so far.
+struct CreateTrace {
+  p2gpu_circuit *c;
+  double t0;
+  void mark(const char *label) const {
+    if (!trace_on()) return;
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    fprintf(stderr, "[p2gpu] create %-28s +%.2f ms\n", label, now_ms() - t0);
+  }
+};
+// The device form of the table phase of circuit creation (handle.hip circuit_finish; the blob form is tables_from_blob there).
+// On entry the root tables exist and k_is and the gate table are enqueued on c->stream; both forms leave d_row_gate, d_gconsts,
+// d_sigmas, sparse_row and sparse_rows behind.  Every scratch buffer is gone when it returns.
+int build_device_tables(p2gpu_circuit *c, const BuildInputs &in, const CreateTrace &tr);
 // consts [num_selectors][n] <- the selector columns of d_row_gate (row of a gate outside the column's group: 2^32 - 1)
 void build_selector_columns(hipStream_t st, const p2gpu_circuit *c, gl_t *consts);
 // ---- handle.hip ----
@@ -95,6 +108,17 @@ int ensure_device();
 extern int g_device;
 extern std::vector<int> g_devices, g_peer_access;
 void circuit_release(p2gpu_circuit *c);
+// Owner of a handle from `new` until it is handed to the caller.  Whatever leaves creation early -- a refusal, a device error,
+// an exception on its way to P2GPU_CATCH -- destroys the handle the way the caller would have (p2gpu_circuit_destroy: the device
+// state through circuit_release; none, and no device call, for a verifier-only handle); the thread's error message survives.
+struct HalfBuiltDelete {
+  void operator()(p2gpu_circuit *c) const {
+    const std::string keep = last_error_copy();
+    p2gpu_circuit_destroy(c);
+    last_error_restore(keep);
+  }
+};
+using HalfBuilt = std::unique_ptr<p2gpu_circuit, HalfBuiltDelete>;
 
 // run f(rank handle, rank) on one host thread per rank of a device group (rank 0 on the caller's thread); a rank
 // that fails releases the others from their rendezvous.  Returns the first failing rank's code with its message.

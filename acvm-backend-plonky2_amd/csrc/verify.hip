@@ -15,6 +15,7 @@
 // final polynomial.  Proof layout: SURVEY.md C.11; it accepts the reference's own proofs
 // (tests/test_reference_proofs.py::test_product_verifier_accepts_reference_proof).
 #include "hostproof.hpp"
+#include "prover_internal.hpp"
 #include <cstdarg>
 #include <cstdio>
 
@@ -105,15 +106,12 @@ extern "C" {
 
 int p2gpu_verifier_create(const uint8_t *blob, size_t len, p2gpu_circuit **out) try {
   if (!blob || !out) return P2GPU_E_ARG;
-  p2gpu_circuit *c = new p2gpu_circuit();
+  HalfBuilt c(new p2gpu_circuit());
+  c->device = -1;  // no device state: only p2gpu_verify and the getters accept this handle
   size_t off = 0;
   const uint8_t *cap_in = nullptr;
-  if (int rc = circuit_parse(blob, len, c, &off, &cap_in)) {
-    delete c;
-    return rc;
-  }
+  if (int rc = circuit_parse(blob, len, c.get(), &off, &cap_in)) return rc;
   if ((c->flags & 3) != 3 || !cap_in) {
-    delete c;
     set_err("a verifier handle needs the circuit digest and the constants_sigmas cap in the blob (flags 0b11)");
     return P2GPU_E_BLOB;
   }
@@ -128,13 +126,11 @@ int p2gpu_verifier_create(const uint8_t *blob, size_t len, p2gpu_circuit **out) 
       for (int i = 0; i < 4; i++) canon &= dg.w[i] < GL_P;
     for (int i = 0; i < 4; i++) canon &= c->circuit_digest.w[i] < GL_P;
     if (!canon) {
-      delete c;
       set_err("verifier key holds a non-canonical Poseidon digest word");
       return P2GPU_E_BLOB;
     }
   }
-  c->device = -1;  // no device state: only p2gpu_verify and the getters accept this handle
-  *out = c;
+  *out = c.release();
   return P2GPU_OK;
 } P2GPU_CATCH
 

@@ -512,6 +512,67 @@ def test_error_paths(pkg, gpu):
     assert len(cd.prove(wires)) > 0
 
 
+def test_refused_creation_returns_its_memory(pkg, orc, gpu):
+    """A creation refused on the host side -- before the device is touched, after the root tables exist, after everything
+    exists, inside the device build -- gives back every byte of device memory and leaves a working library behind.
+    (2^9 ecdsa: the half-domain buffers are among those to return.)  The refusal for an unsupported FRI arity has no case:
+    circuit_parse refuses the same arities first, so no blob reaches it."""
+    import torch
+
+    import device_build_inputs as dbi
+
+    def refused(code, fragment, make):
+        with pytest.raises(pkg.P2GpuError) as ei:
+            make()
+        assert ei.value.code == code and fragment in str(ei.value), ei.value
+        torch.cuda.synchronize()
+        assert torch.cuda.mem_get_info()[0] == free0, fragment
+
+    E_BLOB, E_CAP_MISMATCH, E_ARG = -1, -6, -7
+    for d, mix in ((5, "arith"), (9, "ecdsa")):
+        blob, wires = pkg.make_circuit(d, mix, 1)[:2]
+        want = orc.OracleCircuit(blob).prove(wires)[0]
+        kw = dbi.decompose(pkg, blob)
+        hdr = blob[:256].view(np.uint32)
+        n, R, NC, nsel, ngates = 1 << int(hdr[2]), int(hdr[4]), int(hdr[5]), int(hdr[6]), int(hdr[23])
+        tables = len(blob) - 8 * (NC + R) * n
+        for _ in range(2):          # (first round: whatever the runtime allocates once per process, a proof's share included)
+            pkg.CircuitData.build(**kw).close()
+            warm = pkg.CircuitData(blob)
+            assert warm.prove(wires).to_bytes() == want
+            warm.close()
+        torch.cuda.synchronize()
+        free0 = torch.cuda.mem_get_info()[0]
+
+        refused(E_BLOB, "blob truncated (tables)", lambda: pkg.CircuitData(blob[:-8]))
+
+        bad = blob.copy()           # refused after the root tables exist
+        sel = bad[tables:].view(np.uint64)[:nsel * n].reshape(nsel, n)
+        active = [s for s in range(nsel) if nsel == 1 or sel[s, 3] != 0xFFFFFFFF]
+        assert len(active) == 1
+        sel[active[0], 3] = ngates
+        refused(E_BLOB, "unknown gate index", lambda: pkg.CircuitData(bad))
+
+        good = pkg.CircuitData(blob)   # refused after everything exists: the cap in the blob is not the one committed to
+        with_cap = np.concatenate([np.frombuffer(good.verifier_blob(), dtype=np.uint8), blob[tables:]])
+        good.close()
+        checked = pkg.CircuitData(with_cap)
+        assert checked.prove(wires).to_bytes() == want
+        checked.close()
+        torch.cuda.synchronize()
+        assert torch.cuda.mem_get_info()[0] == free0
+        with_cap[256 + 48 * ngates] ^= 1
+        refused(E_CAP_MISMATCH, "cap mismatch", lambda: pkg.CircuitData(with_cap))
+
+        rg = kw["row_gate"].copy()     # refused by the device build, between its upload and its tables
+        rg[3] = 99
+        refused(E_ARG, "row 3 holds gate index 99", lambda: pkg.CircuitData.build(**dict(kw, row_gate=rg)))
+
+        cd = pkg.CircuitData(blob)
+        assert cd.prove(wires).to_bytes() == want
+        cd.close()
+
+
 @pytest.mark.parametrize("d,mix", [(19, "ecdsa"), (21, "arith"), (21, "grammar")])
 def test_larger_configs_are_accepted(pkg, orc, gpu, d, mix):
     """BASELINE configs[3] / configs[4] sizes on ONE GPU: 2^22 LDE rows with every gate kind,
