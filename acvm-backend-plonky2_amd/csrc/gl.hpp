@@ -15,6 +15,7 @@
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #define P2_HD __host__ __device__ __forceinline__
 #else
 #define P2_HD inline
@@ -393,6 +394,73 @@ P2_HD uint32_t bitrev32(uint32_t x, unsigned bits) {
   return r;
 #endif
 }
+
+#if defined(__HIPCC__)
+// ---- compile-time loops and shift products (device) -------------------------------------------------------
+// f(integral_constant<int, I>) for I in [I, N): a loop whose index is a compile-time constant inside the body
+template <int I, int N, class F>
+__device__ __forceinline__ void static_for(F &&f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    static_for<I + 1, N>(f);
+  }
+}
+
+// x * 2^E mod p for a compile-time 0 <= E < 96 (canonical in, canonical out)
+#if P2_GL_DEV_ASM
+// x = x0 + x1 * 2^32, E = 32 q + r: the shifted words go straight into the carry-chain reductions of gl.hpp
+// (2^64 = eps, 2^96 = -1): 11-14 VALU for every E, where the portable form below costs 15 (E < 32), 20
+// (E < 64) or 35 (two steps).
+template <int E>
+__device__ __forceinline__ gl_t mul_pow2(gl_t x) {
+  if constexpr (E == 0) {
+    return x;
+  } else if constexpr (E < 32) {
+    const uint64_t lo = x << E;
+    return gl_reduce_add_eps((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)(x >> (64 - E)));
+  } else if constexpr (E == 32) {
+    return gl_reduce_words(0u, (uint32_t)x, (uint32_t)(x >> 32), 0u);
+  } else if constexpr (E < 64) {
+    const uint64_t y = x << (E - 32);
+    return gl_reduce_words(0u, (uint32_t)y, (uint32_t)(y >> 32), (uint32_t)(x >> (96 - E)));
+  } else if constexpr (E == 64) {
+    // x * 2^64 = -x * 2^-32 = x0 * eps - x1
+    return gl_reduce_eps_sub((uint32_t)x, (uint32_t)(x >> 32), 0u);
+  } else {
+    // x * 2^E = -x * 2^-s, s = 96 - E in (0, 32): x 2^-s = (x >> s) - z eps, z = low s bits of x at the top of a word
+    constexpr int S = 96 - E;
+    const uint64_t h = x >> S;
+    return gl_reduce_eps_sub((uint32_t)x << (32 - S), (uint32_t)h, (uint32_t)(h >> 32));
+  }
+}
+#else
+template <int E>
+__device__ __forceinline__ gl_t mul_pow2(gl_t x) {
+  if constexpr (E == 0) {
+    return x;
+  } else if constexpr (E < 32) {
+    const uint64_t lo = x << E;
+    const uint32_t hi = (uint32_t)(x >> (64 - E));  // < 2^E
+    const uint64_t t1 = ((uint64_t)hi << 32) - hi;  // hi * (2^32 - 1)
+    uint64_t t2 = lo + t1;
+    if (t2 < t1) t2 += GL_EPS;
+    return gl_canon(t2);
+  } else if constexpr (E < 64) {
+    return gl_reduce128(x << E, x >> (64 - E));
+  } else {
+    return mul_pow2<32>(mul_pow2<E - 32>(x));
+  }
+}
+#endif
+// the same for 0 <= E < 192 (2^96 = -1)
+template <int E>
+__device__ __forceinline__ gl_t mul_pow2_any(gl_t x) {  // x * 2^E, 0 <= E < 192 (2^96 = -1)
+  if constexpr (E == 0) return x;
+  else if constexpr (E < 96) return mul_pow2<E>(x);
+  else if constexpr (E == 96) return gl_sub((gl_t)0, x);
+  else return gl_sub((gl_t)0, mul_pow2<E - 96>(x));
+}
+#endif
 
 struct ext_t {
   gl_t c0, c1;

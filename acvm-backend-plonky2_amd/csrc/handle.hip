@@ -214,8 +214,8 @@ int make_root_tables(p2gpu_circuit *c) {
   CK(c->d_sigmas.alloc((size_t)c->R * n), "alloc sigmas");
   CK(c->d_gates.alloc(c->num_gates ? c->num_gates : 1), "alloc gates");
   gl_t wn = gl_root(d), wN = gl_root(d + c->rate_bits);
-  c->plan_inv = ntt_plan_create(st, d, 0, true);
-  c->plan_fwd = ntt_plan_create(st, d, 1, false);
+  c->plan_inv = ntt_plan_create(st, d, NttDir::ToCoeffs);
+  c->plan_fwd = ntt_plan_create(st, d, NttDir::ToValues);
   if (!c->plan_inv || !c->plan_fwd) { set_err("ntt plan allocation failed"); return P2GPU_E_DEVICE; }
   fill_powers(st, c->tw_fwd.p, wn, (uint32_t)half);
   fill_powers(st, c->tw_inv.p, gl_inv(wn), (uint32_t)half);
@@ -341,7 +341,7 @@ int alloc_proof_buffers(p2gpu_circuit *c) {
     uint32_t ds = d;
     const size_t cap_per = ((size_t)1 << c->cap_h) >> c->rate_bits;
     for (uint32_t s = 0; s <= c->n_steps; s++) {
-      c->fri_plans.push_back(s == 0 ? c->plan_fwd : ntt_plan_create(st, ds, 1, false));
+      c->fri_plans.push_back(s == 0 ? c->plan_fwd : ntt_plan_create(st, ds, NttDir::ToValues));
       if (!c->fri_plans.back()) { set_err("ntt plan allocation failed"); return P2GPU_E_DEVICE; }
       CK(c->fri_coef[s].alloc((size_t)2 << ds), "alloc fri coef");
       if (s < c->n_steps) {
@@ -906,7 +906,7 @@ int p2gpu_ifft_batch(const uint64_t *vals, size_t ncols, unsigned d, uint64_t *c
   gl_t *a = S.alloc<gl_t>(ncols * n), *b = S.alloc<gl_t>(ncols * n), *tw = S.alloc<gl_t>(half);
   if (!a || !b || !tw) { set_err("hipMalloc failed"); return P2GPU_E_DEVICE; }
   HIP_TRY(hipMemcpyAsync(a, vals, 8 * ncols * n, hipMemcpyHostToDevice, S.st));
-  NttPlan *plan = ntt_plan_create(S.st, d, 0, true);
+  NttPlan *plan = ntt_plan_create(S.st, d, NttDir::ToCoeffs);
   if (!plan) { set_err("hipMalloc failed"); return P2GPU_E_DEVICE; }
   ntt_batch(S.st, plan, a, b, (uint32_t)ncols, 1, nullptr, gl_inv((gl_t)n), false);
   bitrev_cols(S.st, b, a, d, (uint32_t)ncols);  // natural-order coefficients for the caller
@@ -930,7 +930,7 @@ int p2gpu_lde_batch(const uint64_t *coeffs, size_t ncols, unsigned d, unsigned r
   if (!a || !b || !tw || !scale || !lde) { set_err("hipMalloc failed"); return P2GPU_E_DEVICE; }
   HIP_TRY(hipMemcpyAsync(a, coeffs, 8 * ncols * n, hipMemcpyHostToDevice, S.st));
   bitrev_cols(S.st, a, b, d, (uint32_t)ncols);
-  NttPlan *plan = ntt_plan_create(S.st, d, 1, false);
+  NttPlan *plan = ntt_plan_create(S.st, d, NttDir::ToValues);
   if (!plan) { set_err("hipMalloc failed"); return P2GPU_E_DEVICE; }
   fill_coset_scale(S.st, scale, GL_GEN, gl_root(d + rate_bits), d, C, 1);
   ntt_batch(S.st, plan, b, lde, (uint32_t)ncols, C, scale, 1, false);
@@ -1005,8 +1005,8 @@ int p2gpu_commit_values(const uint64_t *vals, size_t ncols, unsigned d, unsigned
       break;
     }
     if ((rc = batch_alloc(c, c->wires, (uint32_t)ncols))) break;
-    c->plan_inv = ntt_plan_create(c->stream, d, 0, true);
-    c->plan_fwd = ntt_plan_create(c->stream, d, 1, false);
+    c->plan_inv = ntt_plan_create(c->stream, d, NttDir::ToCoeffs);
+    c->plan_fwd = ntt_plan_create(c->stream, d, NttDir::ToValues);
     if (!c->plan_inv || !c->plan_fwd) {
       set_err("hipMalloc failed");
       rc = P2GPU_E_DEVICE;

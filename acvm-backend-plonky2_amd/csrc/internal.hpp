@@ -40,35 +40,7 @@ struct ProfScope {
   ~ProfScope() { if (g_prof) g_prof->end(); }
 };
 
-// ---- ntt.hip ----
-constexpr int NTT_MAX_ROUNDS = 6;  // rounds of <= 3 layers in one pass: 12 layers are 4, a 2^13 tile's 13 layers are 5
-struct NttPass {
-  uint32_t s, a, tb, nrounds;
-  uint32_t r[NTT_MAX_ROUNDS], tw_off[NTT_MAX_ROUNDS];
-  // DIT passes on full 2^12 tiles whose first round has three layers also have a "direct" form (ntt.hip ntt_dit_*_kernel):
-  // the first round straight from global memory (strided passes), the last one straight to it, its twiddles shifts only.
-  // ftw_off: offset in the plan's table of the folded twiddles of the round before the last (strided passes: fold_table_kernel)
-  bool direct = false;
-  uint32_t ftw_off = 0;
-  uint32_t ftw2_off = 0;  // head pass (s = 0) instead: its folded table in ntt_dit_head2_kernel's lane order
-};
-struct NttPlan {
-  uint32_t d = 0;
-  int dit = 0;           // 0: DIF natural in -> bit-reversed out; 1: DIT bit-reversed in -> natural out
-  bool inverse = false;  // roots w^-1 (the 1/n factor is the caller's `post`)
-  std::vector<NttPass> passes;
-  gl_t *ptw = nullptr;   // device: packed per-round twiddle tables
-  size_t table_len = 0;
-};
-// which global cosets a sharded launch covers: local index z <-> global coset first + z * stride
-struct CosetMap {
-  uint32_t first = 0, stride = 1;
-};
-NttPlan *ntt_plan_create(hipStream_t st, uint32_t d, int dit, bool inverse);
-void ntt_plan_destroy(NttPlan *p);
-// src [cols][n] (or [cosets][cols][n] when src_per_coset), dst [cosets][cols][n]; stride_cols != 0: the
-// launch covers `cols` columns of a batch that has stride_cols columns per coset (chunked pipelines).
-// scale (DIT only): [cosets][n] multiplied into the input; post: multiplied into the output.
+// ---- columns.hip ----
 // Structured columns of a batch (the unused wires of a witness): a transform is linear, so the zero column maps to
 // zeros and v * (unit column of a fixed row) maps to v * (the transform of that unit column, kept by the handle).
 constexpr uint32_t MAX_SPARSE_ROWS = 4;  // the PublicInputGate row + up to three PoseidonGate rows
@@ -97,9 +69,6 @@ struct ColHints {
   bool fill_only = false;           // write the structured columns and return: the dense ones are somebody else's (a rank of a
                                     // sharded proof transforms only its block of the dense columns, commit.hip shard_intt)
 };
-void ntt_batch(hipStream_t st, const NttPlan *plan, const gl_t *src, gl_t *dst, uint32_t cols, uint32_t cosets,
-               const gl_t *scale, gl_t post, bool src_per_coset, CosetMap cm = CosetMap(), uint32_t stride_cols = 0,
-               const ColHints *hints = nullptr);
 // clean[c] = 1: dst already holds the zeros of zero column c.  `after` = false, enqueued before the transforms:
 // non-zero columns lose the mark; `after` = true, enqueued behind them: zero columns gain it.
 void column_clean_update(hipStream_t st, const uint32_t *cls, uint32_t cols, uint32_t *clean, bool after);
@@ -107,10 +76,55 @@ void column_clean_update(hipStream_t st, const uint32_t *cls, uint32_t cols, uin
 // the column's value in special row s
 void column_flags(hipStream_t st, const gl_t *vals, uint32_t cols, uint32_t d, const SparseRows &rows, uint32_t *flags,
                   gl_t *scalar, uint32_t sstride);
+
+// ---- ntt.hip ----
+constexpr int NTT_MAX_ROUNDS = 6;  // rounds of <= 3 layers in one pass: the 12 layers of a full tile are 4 (6 keeps PassArgs' layout)
+// values -> coefficients: DIF with the inverse roots, natural in -> bit-reversed out (the 1/n factor is the caller's `post`);
+// coefficients -> values: DIT with the forward roots, bit-reversed in -> natural out
+enum class NttDir { ToCoeffs, ToValues };
+struct NttPass {
+  uint32_t s, a, tb, nrounds;
+  uint32_t r[NTT_MAX_ROUNDS], tw_off[NTT_MAX_ROUNDS];
+  // Passes on full 2^12 tiles whose first round has three layers also have a "direct" form (ntt.hip ntt_dit_* / ntt_dif_*):
+  // the first round straight from global memory (strided passes), the last one straight to it, its twiddles shifts only; the
+  // round before the last (fold_r layers at stride 2^fold_s0) takes the rest from a folded table at ftw_off in the plan's table
+  // (fold_table_kernel; the 12-layer pass s = 0: head_fold_table_kernel's lane order).  rm / rl: layers of the middle and the
+  // last round of a strided pass (0: none), which select its kernel.
+  bool direct = false;
+  uint32_t rm = 0, rl = 0, fold_r = 0, fold_s0 = 0;
+  uint32_t ftw_off = 0;
+};
+struct NttPlan {
+  uint32_t d = 0;
+  NttDir dir = NttDir::ToCoeffs;
+  std::vector<NttPass> passes;
+  gl_t *ptw = nullptr;   // device: packed per-round twiddle tables
+  size_t table_len = 0;
+};
+// which global cosets a sharded launch covers: local index z <-> global coset first + z * stride
+struct CosetMap {
+  uint32_t first = 0, stride = 1;
+};
+NttPlan *ntt_plan_create(hipStream_t st, uint32_t d, NttDir dir);
+void ntt_plan_destroy(NttPlan *p);
+// src [cols][n] (or [cosets][cols][n] when src_per_coset), dst [cosets][cols][n]; stride_cols != 0: the
+// launch covers `cols` columns of a batch that has stride_cols columns per coset (chunked pipelines).
+// scale (ToValues only): [cosets][n] multiplied into the input; post: multiplied into the output.
+// hints: the structured columns are written by structured_fill_kernel, only the dense ones go through the passes.
+void ntt_batch(hipStream_t st, const NttPlan *plan, const gl_t *src, gl_t *dst, uint32_t cols, uint32_t cosets,
+               const gl_t *scale, gl_t post, bool src_per_coset, CosetMap cm = CosetMap(), uint32_t stride_cols = 0,
+               const ColHints *hints = nullptr);
+
+// ---- tables.hip ----
+// out[i] = root^i, i < count
 void fill_powers(hipStream_t st, gl_t *out, gl_t root, uint32_t count);
+// out[c][p] = (shift * wN^c)^(bitrev_d(p)) * mult: the input scale of coset c's ToValues transform
 void fill_coset_scale(hipStream_t st, gl_t *out, gl_t shift, gl_t wN, uint32_t d, uint32_t cosets, gl_t mult);
+
+// ---- selftest.hip (stage-level test operators only) ----
+// bit-reversal permutation of every column: plonky2's natural-order coefficients <-> this library's storage
 void bitrev_cols(hipStream_t st, const gl_t *in, gl_t *out, uint32_t d, uint32_t cols);
-// the device forms of the field primitives against the portable code; bad[8] mismatch counters
+// the device forms of the field primitives against the portable code; bad[16] mismatch counters
 void field_selftest(hipStream_t st, const uint64_t *a, const uint64_t *b, uint32_t n, unsigned long long *bad);
 
 // ---- merkle.hip ----

@@ -160,15 +160,8 @@ __global__ __launch_bounds__(256, V ? P2_LEAFV_WAVES : P2_LEAF_WAVES) void hash_
 }
 
 // ---- Keccak leaf hashing with the sponge state in fixed registers (keccak.hpp P2_KF_*) ----------------------------------
-template <int I, int N, class F>
-__device__ __forceinline__ void kf_for(F &&f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    kf_for<I + 1, N>(f);
-  }
-}
 __device__ __forceinline__ void kf_zero() {
-  kf_for<0, 25>([&](auto ic) { P2_KF_SET(decltype(ic)::value, 0u, 0u); });
+  static_for<0, 25>([&](auto ic) { P2_KF_SET(decltype(ic)::value, 0u, 0u); });
 }
 // One sponge step: absorb the next rate block -- 17 full words, or (the last step) the ragged tail of rem < 17 words with the
 // original Keccak padding -- and permute.  ONE call site of the 34 KB permutation per kernel: two would not fit the
@@ -181,7 +174,7 @@ __device__ __forceinline__ void kf_absorb_group(uint32_t off, F get) {
   uint64_t x[W1 - W0];
 #pragma unroll
   for (int w = W0; w < W1; w++) x[w - W0] = get(off + w);
-  kf_for<W0, W1>([&](auto wc) {
+  static_for<W0, W1>([&](auto wc) {
     constexpr int w = decltype(wc)::value;
     const uint64_t xw = x[w - W0];  // (an asm operand may not name a captured variable)
     const uint32_t lo = (uint32_t)xw, hi = (uint32_t)(xw >> 32);
@@ -199,7 +192,7 @@ __device__ __forceinline__ void kf_absorb(uint32_t off, uint32_t rem, F get) {
       kf_absorb_group<0, 17>(off, get);
     }
   } else {
-    kf_for<0, 17>([&](auto wc) {  // once per leaf: word by word
+    static_for<0, 17>([&](auto wc) {  // once per leaf: word by word
       constexpr int w = decltype(wc)::value;
       if ((uint32_t)w <= rem) {
         const uint64_t xw = (uint32_t)w < rem ? get(off + w) : (uint64_t)1;  // ... | 0x01 pad
@@ -234,13 +227,13 @@ __device__ __forceinline__ void kf_set_two_to_one(const dig_t &l, const dig_t &r
   w[4] = (r.w[0] >> 56) | (r.w[1] << 8);
   w[5] = (r.w[1] >> 56) | (r.w[2] << 8);
   w[6] = (r.w[2] >> 56) | ((r.w[3] & 0xFFULL) << 8) | (0x01ULL << 16);
-  kf_for<0, 7>([&](auto ic) {
+  static_for<0, 7>([&](auto ic) {
     constexpr int i = decltype(ic)::value;
     const uint64_t x = w[i];
     const uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
     P2_KF_SET(i, lo, hi);
   });
-  kf_for<7, 25>([&](auto ic) {
+  static_for<7, 25>([&](auto ic) {
     constexpr int i = decltype(ic)::value;
     P2_KF_SET(i, 0u, (i == 16 ? 0x80000000u : 0u));
   });
@@ -298,7 +291,7 @@ __global__ __launch_bounds__(256) P2_KF_KERNEL_ATTR void hash_lde_leaves_kf_kern
       const uint32_t rem = cols - off;
       complete = rem < 17;
       if constexpr (!V) {
-        kf_for<0, 17>([&](auto wc) {
+        static_for<0, 17>([&](auto wc) {
           constexpr int w = decltype(wc)::value;
           const uint64_t xw = x[w];
           const uint32_t lo = (uint32_t)xw, hi = (uint32_t)(xw >> 32);
@@ -465,7 +458,7 @@ __global__ __launch_bounds__(256) P2_KF_KERNEL_ATTR void hash_lde_absorb_kf_kern
   };
   if (first) kf_zero();
   else
-    kf_for<0, 25>([&](auto ic) {
+    static_for<0, 25>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
       const uint64_t x = sp[(size_t)i * n];
       P2_KF_SET(i, (uint32_t)x, (uint32_t)(x >> 32));
@@ -480,7 +473,7 @@ __global__ __launch_bounds__(256) P2_KF_KERNEL_ATTR void hash_lde_absorb_kf_kern
   if (last) {
     dig[(size_t)c * n + k] = kf_digest();
   } else {
-    kf_for<0, 25>([&](auto ic) {
+    static_for<0, 25>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
       uint32_t lo, hi;  // (locals of the lambda: an asm output may not name a captured variable)
       P2_KF_GET(i, lo, hi);

@@ -29,65 +29,10 @@
 // kernel runs, not its limiter.  No MFMA.
 #include "internal.hpp"
 #include <algorithm>
-#include <type_traits>
+#include <memory>
 #include <vector>
 
 namespace p2 {
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-
-// x * 2^E mod p for a compile-time 0 <= E < 96 (canonical in, canonical out)
-#if P2_GL_DEV_ASM
-// x = x0 + x1 * 2^32, E = 32 q + r: the shifted words go straight into the carry-chain reductions of gl.hpp
-// (2^64 = eps, 2^96 = -1): 11-14 VALU for every E, where the portable form below costs 15 (E < 32), 20
-// (E < 64) or 35 (two steps).
-template <int E>
-__device__ __forceinline__ gl_t mul_pow2(gl_t x) {
-  if constexpr (E == 0) {
-    return x;
-  } else if constexpr (E < 32) {
-    const uint64_t lo = x << E;
-    return gl_reduce_add_eps((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)(x >> (64 - E)));
-  } else if constexpr (E == 32) {
-    return gl_reduce_words(0u, (uint32_t)x, (uint32_t)(x >> 32), 0u);
-  } else if constexpr (E < 64) {
-    const uint64_t y = x << (E - 32);
-    return gl_reduce_words(0u, (uint32_t)y, (uint32_t)(y >> 32), (uint32_t)(x >> (96 - E)));
-  } else if constexpr (E == 64) {
-    // x * 2^64 = -x * 2^-32 = x0 * eps - x1
-    return gl_reduce_eps_sub((uint32_t)x, (uint32_t)(x >> 32), 0u);
-  } else {
-    // x * 2^E = -x * 2^-s, s = 96 - E in (0, 32): x 2^-s = (x >> s) - z eps, z = low s bits of x at the top of a word
-    constexpr int S = 96 - E;
-    const uint64_t h = x >> S;
-    return gl_reduce_eps_sub((uint32_t)x << (32 - S), (uint32_t)h, (uint32_t)(h >> 32));
-  }
-}
-#else
-template <int E>
-__device__ __forceinline__ gl_t mul_pow2(gl_t x) {
-  if constexpr (E == 0) {
-    return x;
-  } else if constexpr (E < 32) {
-    const uint64_t lo = x << E;
-    const uint32_t hi = (uint32_t)(x >> (64 - E));  // < 2^E
-    const uint64_t t1 = ((uint64_t)hi << 32) - hi;  // hi * (2^32 - 1)
-    uint64_t t2 = lo + t1;
-    if (t2 < t1) t2 += GL_EPS;
-    return gl_canon(t2);
-  } else if constexpr (E < 64) {
-    return gl_reduce128(x << E, x >> (64 - E));
-  } else {
-    return mul_pow2<32>(mul_pow2<E - 32>(x));
-  }
-}
-#endif
 
 // exponent of 2 for the constant twiddle w_{2^(lam+1)}^q (w_64 = 2^3), mod 192
 __host__ __device__ constexpr int tw_exp(int lam, int q, bool inv) {
@@ -133,8 +78,7 @@ __device__ __forceinline__ void dft_regs(gl_t (&v)[1 << LOGR]) {
   });
 }
 
-// LDS index swizzle (round 3; replaces the "one pad slot per 16" of rounds 1-2, which left 61 % of the kernel's LDS cycles
-// as bank conflicts: SQ_LDS_BANK_CONFLICT / SQ_ACTIVE_INST_LDS of profiles/r02i_sq_summary.json).  ds_read_b64 serves a
+// LDS index swizzle.  ds_read_b64 serves a
 // wave in two groups of 32 lanes over 32 eight-byte slots, ds_write_b64 in four groups of 16 lanes over 16 slots
 // (MI355X_MICROARCH.md, LDS).  In a round on tile bits [beta0, beta0 + 3) the lanes of a group differ in element bits
 // {3..7} (beta0 = 0), {0,1,2,6,7} (beta0 = 3) or {0..4} (beta0 >= 5, and the load / store phases): the slot bits
@@ -144,17 +88,19 @@ __device__ __forceinline__ void dft_regs(gl_t (&v)[1 << LOGR]) {
 // swz(a ^ b) = swz(a) ^ swz(b): a lane's eight addresses are swz(base) ^ swz(j << beta0), the second term wave-uniform.
 __device__ __forceinline__ uint32_t pidx(uint32_t e) { return e ^ ((e >> 4) & 7u) ^ ((e >> 3) & 0x18u); }
 
+// A full tile is 2^12 elements (32 KB of LDS) on 512 lanes that hold 8 elements each, so the largest round is radix 8; smaller
+// transforms run on one smaller tile.  (Radix-16 rounds on 256 lanes and a 2^13 tile were built and measured slower; the
+// wave-private rounds and the direct kernels below are written for exactly this shape.)
+constexpr int NTT_TILE_BITS = 12;
+constexpr int NTT_PER = 8;
+constexpr int NTT_THREADS = (1 << NTT_TILE_BITS) / NTT_PER;
+// waves per SIMD the full-tile kernels are compiled for: 8 = four 512-lane workgroups per CU, i.e. <= 64 VGPRs.  hipcc reaches
+// 59-60 on its own; saying so makes it schedule for that bound (LDE 1.22-1.24 -> 1.205-1.21 ms at 2^20 rows) and
+// keeps an edit that would silently cost a quarter of the occupancy (every variant above 64 VGPRs measured 20-30 % slower)
+// from compiling into one
+constexpr int NTT_MIN_WAVES = 8;
+static_assert(NTT_THREADS == 512, "wave-private rounds and direct passes: 512 lanes x 8 elements");
 constexpr int MAX_ROUNDS = NTT_MAX_ROUNDS;
-#ifndef NTT_TILE_BITS
-#define NTT_TILE_BITS 12
-#endif
-// elements a lane holds in the full-tile kernel = largest round radix.  16: radix-16 rounds, 256 lanes per tile,
-// ~100 VGPRs, 4 tiles (16 waves) per CU because of the 34 KB of LDS a tile needs.  8: radix-8 rounds, 512 lanes
-// per tile, the same LDS but twice the waves per CU to cover barriers and HBM latency
-#ifndef NTT_PER
-#define NTT_PER 8
-#endif
-#define NTT_THREADS ((1 << NTT_TILE_BITS) / NTT_PER)
 struct PassArgs {
   const gl_t *src;    // [cols][n] (or [cosets][cols][n])
   gl_t *dst;          // [cosets][cols][n]
@@ -180,6 +126,64 @@ struct PassArgs {
 
 __device__ __forceinline__ uint32_t gidx(uint32_t e, uint32_t hi_base, uint32_t lo0, uint32_t s, uint32_t tb) {
   return hi_base + ((e >> tb) << s) + lo0 + (e & ((1u << tb) - 1));
+}
+
+// block -> (tile, column, coset), false when the block has nothing to do.  1-D grid decoded XCD-aware: the hardware deals
+// consecutive block ids round-robin over the 8 XCDs, each with its own L2.  The 2^rate_bits coset transforms of one (tile, column)
+// read the SAME coefficients (and neighbouring rows of the scale table): they get consecutive slots of ONE XCD, so the tile comes
+// from HBM once and from that XCD's L2 afterwards (a speed choice only: any placement gives the same result).
+__device__ __forceinline__ bool pass_unit(const PassArgs &A, uint32_t &tile, uint32_t &col, uint32_t &coset) {
+  const uint32_t units = A.tiles * A.cols_grid;
+  const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
+  coset = slot % A.cosets;
+  const uint32_t unit = (slot / A.cosets) * 8u + xcd;
+  if (unit >= units) return false;
+  tile = unit % A.tiles;
+  col = unit / A.tiles;
+  // Structured columns (internal.hpp ColHints): a transform is linear, so a zero column maps to zeros and
+  // v * (unit column of the fixed row) to v * (that unit column's transform): structured_fill_kernel wrote them,
+  // nothing to do here (block-uniform scalar branch).
+  return !(A.colnz != nullptr && A.colnz[col] != 2u);
+}
+// the column of (col, coset) in src and dst, and the coset's row of the scale table (nullptr: none)
+struct ColPtrs {
+  const gl_t *src;
+  gl_t *dst;
+  const gl_t *scale;
+};
+__device__ __forceinline__ ColPtrs col_ptrs(const PassArgs &A, uint32_t col, uint32_t coset) {
+  const size_t n = (size_t)1 << A.d;
+  return {A.src + ((size_t)(A.src_single ? 0 : coset) * A.cols + col) * n, A.dst + ((size_t)coset * A.cols + col) * n,
+          A.scale ? A.scale + (size_t)(A.coset_first + coset * A.coset_stride) * n : nullptr};
+}
+// tile -> global index of its hi block and first lo-run: element e of the tile is gidx(e, hi_base, lo0, s, tb)
+struct TilePos {
+  uint32_t hi_base, lo0;
+};
+__device__ __forceinline__ TilePos tile_pos(const PassArgs &A, uint32_t tile) {
+  const uint32_t runs = 1u << (A.s - A.tb);  // lo-runs per hi block
+  const uint32_t hi = tile / runs, lo0 = (tile % runs) << A.tb;
+  return {hi << (A.s + A.a), lo0};
+}
+
+// Twiddle tables hold one row per exponent e; register j of a round takes row bitrev(j).
+// rows 1 .. R-1 of a packed table T[(e-1) * M + lo] (round_table_kernel), tp = &T[lo], stride = M; row 0 is 1 and not stored
+template <int R>
+__device__ __forceinline__ void load_packed(gl_t (&t)[R], const gl_t *tp, size_t stride) {
+#pragma unroll
+  for (int e = 1; e < R; e++) {
+    t[e] = *tp;
+    tp += stride;
+  }
+}
+// the R rows of a folded table F[(e * 2^rl + high) * M + lo] (fold_table_kernel), tp = &F[high * M + lo], stride = 2^rl * M
+template <int R>
+__device__ __forceinline__ void load_folded(gl_t (&t)[R], const gl_t *tp, size_t stride) {
+#pragma unroll
+  for (int e = 0; e < R; e++) {
+    t[e] = *tp;
+    tp += stride;
+  }
 }
 
 // one round: layers on tile bits [beta0, beta0 + LOGR); the group twiddle of position j is
@@ -211,19 +215,8 @@ __device__ __forceinline__ void round_regs(gl_t *lds, const PassArgs &A, uint32_
     }
 #pragma unroll
     for (int j = 0; j < R; j++) v[j] = lds[li[j]];
-    gl_t t[R];  // t[e]: twiddle of table row e - 1
-    if constexpr (MUL) {
-      const gl_t *tp = tw + lo;
-#pragma unroll
-      for (int e = 1; e < R; e++) {
-#ifdef NTT_EXP_NOTW   // timing experiment only (wrong results): what waiting for the twiddle loads costs
-        t[e] = (gl_t)(size_t)tp;
-#else
-        t[e] = *tp;
-#endif
-        tp += tstride;
-      }
-    }
+    gl_t t[R];
+    if constexpr (MUL) load_packed(t, tw + lo, tstride);
     if constexpr (DIT && MUL) {
       static_for<1, R>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
@@ -252,9 +245,6 @@ __device__ __forceinline__ void do_round(gl_t *lds, const PassArgs &A, uint32_t 
     else round_regs<DIT, INV, L, false>(lds, A, TB, beta0, lo0, tw);       \
   } while (0)
   switch (logr) {
-#if NTT_PER == 16
-  case 4: P2_ROUND(4); break;
-#endif
   case 3: P2_ROUND(3); break;
   case 2: P2_ROUND(2); break;
   default: P2_ROUND(1); break;
@@ -266,47 +256,26 @@ __device__ __forceinline__ void do_round(gl_t *lds, const PassArgs &A, uint32_t 
 // TBC = 12: the full 2^12-element tile with NTT_THREADS lanes -- the global loads/stores of a lane are NTT_PER
 // independent accesses issued back to back (compile-time trip count) so their latencies overlap;
 // TBC = 0: any smaller tile (small transforms), runtime loops.
-// waves per SIMD the full-tile kernel is compiled for: 8 = four 512-lane workgroups per CU, i.e. <= 64 VGPRs.  hipcc reaches
-// 59-60 on its own; saying so makes it schedule for that bound (LDE 1.22-1.24 -> 1.205-1.21 ms at 2^20 rows, round 4) and
-// keeps an edit that would silently cost a quarter of the occupancy (every variant above 64 VGPRs measured 20-30 % slower)
-// from compiling into one
-#ifndef NTT_MIN_WAVES
-#if NTT_PER != 8
-#define NTT_MIN_WAVES 1
-#else
-#define NTT_MIN_WAVES 8
-#endif
-#endif
 template <int DIT, bool INV, int TBC>
 __device__ __forceinline__ void tile_body(gl_t *lds, const PassArgs &A, uint32_t tile, uint32_t col, uint32_t coset) {
+  static_assert(TBC == 0 || TBC == NTT_TILE_BITS, "a full tile or a runtime-sized smaller one");
+  constexpr int PER = NTT_PER, NT = NTT_THREADS;
   const uint32_t TB = TBC ? TBC : A.a + A.tb;
-  const size_t n = (size_t)1 << A.d;
-  const uint32_t runs = 1u << (A.s - A.tb);  // lo-runs per hi block
-  const uint32_t hi = tile / runs, lo0 = (tile % runs) << A.tb;
-  const uint32_t hi_base = hi << (A.s + A.a);
-  const gl_t *src = A.src + ((size_t)(A.src_single ? 0 : coset) * A.cols + col) * n;
-  gl_t *dst = A.dst + ((size_t)coset * A.cols + col) * n;
-  const gl_t *scale = A.scale ? A.scale + (size_t)(A.coset_first + coset * A.coset_stride) * n : nullptr;
+  const auto [hi_base, lo0] = tile_pos(A, tile);
+  const auto [src, dst, scale] = col_ptrs(A, col, coset);
   const uint32_t tsize = 1u << TB;
   // lane e + i * NT of the tile: when a contiguous run (2^tb elements) divides NT, the global index is linear in i
   // (g0 + i * gstep) and so is the swizzled LDS index (l0 + i * NT: the swizzle only touches bits below log2 NT)
-  constexpr int NT12 = NTT_THREADS;
-  const bool glin = (1u << A.tb) <= (uint32_t)NT12;
-  const uint32_t g0 = gidx(threadIdx.x, hi_base, lo0, A.s, A.tb), gstep = (NT12 >> (glin ? A.tb : 0)) << A.s;
+  const bool glin = (1u << A.tb) <= (uint32_t)NT;
+  const uint32_t g0 = gidx(threadIdx.x, hi_base, lo0, A.s, A.tb), gstep = (NT >> (glin ? A.tb : 0)) << A.s;
   const uint32_t l0 = pidx(threadIdx.x);
   if constexpr (TBC != 0) {
-    constexpr int PER = NTT_PER, NT = (1 << TBC) / PER;
-    static_assert(NT == NT12, "full tile: NTT_THREADS lanes");
     gl_t x[PER];
     uint32_t g[PER];
 #pragma unroll
     for (int i = 0; i < PER; i++) {
       g[i] = glin ? g0 + (uint32_t)i * gstep : gidx(threadIdx.x + i * NT, hi_base, lo0, A.s, A.tb);
-#ifdef NTT_EXP_NOLOAD   // timing experiment only (wrong results): what the load phase costs
-      x[i] = (gl_t)g[i] * 0x9E3779B97F4A7C15ULL;
-#else
       x[i] = src[g[i]];
-#endif
     }
     if (scale) {
       gl_t sc[PER];
@@ -326,19 +295,19 @@ __device__ __forceinline__ void tile_body(gl_t *lds, const PassArgs &A, uint32_t
     }
   }
   __syncthreads();
-  // A radix-NTT_PER round on tile bits [beta, beta + 3) below bit 9 of a full tile touches, in wave w, exactly the elements
+  // A radix-8 round on tile bits [beta, beta + 3) below bit 9 of a full tile touches, in wave w, exactly the elements
   // whose bits [9, 12) are w (lane g = 64 w + l holds base = (g >> beta << (beta + 3)) | (g & (2^beta - 1)) and its 8
   // strides): consecutive such rounds exchange data inside a wave only, and a wave's LDS operations execute in order --
   // no workgroup barrier between them.
   // That argument needs: 512 lanes in wave64 (wave w = lanes [64 w, 64 w + 64)), ONE group per lane (g == threadIdx.x: the
   // trip count of round_regs' loop is 1) and round_regs' base = (g >> beta << (beta + 3)) | low split -- tied down here so that
   // an edit to any of them fails to compile instead of racing on LDS.
-  static_assert(TBC != 12 || NTT_PER != 8 || NTT_THREADS == 512, "wave-private rounds: one radix-8 group per lane of a 2^12 tile");
+  static_assert(NTT_PER == 8 && NTT_THREADS == 512, "wave-private rounds: one radix-8 group per lane of a 2^12 tile");
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "wave-private rounds assume wave64: gfx950 (CDNA has no wave32 mode) is the only target of this file"
 #endif
   const bool one_group_per_lane = (1u << (TB - 3)) == blockDim.x;
-  auto wave_private = [&](uint32_t beta, uint32_t r) { return TBC == 12 && NTT_PER == 8 && one_group_per_lane && r == 3 && beta + 3 <= 9; };
+  auto wave_private = [&](uint32_t beta, uint32_t r) { return TBC == NTT_TILE_BITS && one_group_per_lane && r == 3 && beta + 3 <= 9; };
   if (DIT) {
     uint32_t beta = A.tb;
     for (uint32_t i = 0; i < A.nrounds; i++) {
@@ -358,7 +327,6 @@ __device__ __forceinline__ void tile_body(gl_t *lds, const PassArgs &A, uint32_t
   }
   const bool post = A.post != 1;
   if constexpr (TBC != 0) {
-    constexpr int PER = NTT_PER, NT = (1 << TBC) / PER;
     gl_t x[PER];
 #pragma unroll
     for (int i = 0; i < PER; i++) x[i] = lds[l0 + (uint32_t)i * NT];
@@ -366,9 +334,6 @@ __device__ __forceinline__ void tile_body(gl_t *lds, const PassArgs &A, uint32_t
 #pragma unroll
       for (int i = 0; i < PER; i++) x[i] = gl_mul(x[i], A.post);
     }
-#ifdef NTT_EXP_NOSTORE  // timing experiment only (wrong results): what the store phase costs
-    if ((x[0] ^ x[1] ^ x[2] ^ x[3] ^ x[4] ^ x[5] ^ x[6] ^ x[7]) == 0x1234567ULL)
-#endif
 #pragma unroll
     for (int i = 0; i < PER; i++) dst[glin ? g0 + (uint32_t)i * gstep : gidx(threadIdx.x + i * NT, hi_base, lo0, A.s, A.tb)] = x[i];
   } else {
@@ -380,27 +345,18 @@ __device__ __forceinline__ void tile_body(gl_t *lds, const PassArgs &A, uint32_t
   }
 }
 
-// One pass as its own launch.  1-D grid decoded XCD-aware: the hardware deals consecutive block ids round-robin over
-// the 8 XCDs, each with its own L2.  The 2^rate_bits coset transforms of one (tile, column) read the SAME coefficients
-// (and neighbouring rows of the scale table): they get consecutive slots of ONE XCD, so the tile comes from HBM once
-// and from that XCD's L2 afterwards (a speed choice only: any placement gives the same result).
+// One pass as its own launch: every size, every round from the packed tables.  The only form of the transforms below 2^12 points
+// and of strided passes of 1, 2 or 4 layers; with P2GPU_NTT_DIRECT=0 of every pass.
 template <int DIT, bool INV, int TBC>
 __global__ __launch_bounds__(TBC ? NTT_THREADS : 256, TBC ? NTT_MIN_WAVES : 1) void ntt_pass_kernel(PassArgs A) {
   extern __shared__ gl_t lds[];
-  const uint32_t units = A.tiles * A.cols_grid;
-  const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
-  const uint32_t coset0 = slot % A.cosets, unit = (slot / A.cosets) * 8u + xcd;
-  if (unit >= units) return;
-  const uint32_t tile = unit % A.tiles, col = unit / A.tiles;
-  // Structured columns (internal.hpp ColHints): a transform is linear, so a zero column maps to zeros and
-  // v * (unit column of the fixed row) to v * (that unit column's transform): structured_fill_kernel wrote them,
-  // nothing to do here (block-uniform scalar branch).
-  if (A.colnz != nullptr && A.colnz[col] != 2u) return;
-  tile_body<DIT, INV, TBC>(lds, A, tile, col, coset0);
+  uint32_t tile, col, coset;
+  if (!pass_unit(A, tile, col, coset)) return;
+  tile_body<DIT, INV, TBC>(lds, A, tile, col, coset);
 }
 
-// ---- direct DIT passes (round 5) -----------------------------------------------------------------------------------------
-// The forward (coefficients -> coset values) transforms are DIT passes on full 2^12 tiles.  ntt_pass_kernel above stages a tile in
+// ---- direct passes: coefficients -> values (DIT) ---------------------------------------------------------------------------------
+// Those transforms are DIT passes on full 2^12 tiles.  ntt_pass_kernel above stages a tile in
 // LDS, runs every round LDS -> registers -> LDS with a table twiddle on 7 of 8 inputs, and copies the tile out: five LDS round
 // trips and three barriers for the 12-layer pass, three and three for the 5-layer one.  Two observations remove a third of that:
 //   * The LAST round of a pass holds, in lane t, exactly the elements t | (j << beta) that lane t would copy to global memory
@@ -413,13 +369,6 @@ __global__ __launch_bounds__(TBC ? NTT_THREADS : 256, TBC ? NTT_MIN_WAVES : 1) v
 //     lane's group index): a scalar branch on k, then compile-time shift amounts.
 // Same values (the field result of a butterfly network does not depend on how its twiddles are factored): bit-exact against the
 // oracle and against ntt_pass_kernel (P2GPU_NTT_DIRECT=0).  The 12-layer first pass goes further (ntt_dit_head2_kernel below).
-template <int E>
-__device__ __forceinline__ gl_t mul_pow2_any(gl_t x) {  // x * 2^E, 0 <= E < 192 (2^96 = -1)
-  if constexpr (E == 0) return x;
-  else if constexpr (E < 96) return mul_pow2<E>(x);
-  else if constexpr (E == 96) return gl_sub((gl_t)0, x);
-  else return gl_sub((gl_t)0, mul_pow2<E - 96>(x));
-}
 // the shift twiddles of a last round of RL layers after a round of RP layers: register j *= w_{2^(RP+RL)}^(k * brev(j))
 template <bool INV, int RL, int RP, int K>
 __device__ __forceinline__ void shift_twiddles(gl_t (&v)[1 << RL]) {
@@ -447,7 +396,8 @@ __device__ __forceinline__ void shift_twiddles_k(gl_t (&v)[1 << RL], uint32_t k)
 }
 // A round on tile bits [beta0, beta0 + LOGR) of a 2^12 tile in LDS whose input twiddles also carry the general part of the LAST
 // round's (RL layers, the tile's top bits = this round's `high`): table row e = brev(j), then high, then lo.
-template <bool INV, int LOGR>
+// DIF: the same table multiplies the round's OUTPUTS (its own general twiddle x the top round's deferred part).
+template <int DIT, bool INV, int LOGR>
 __device__ __forceinline__ void round_folded(gl_t *lds, const PassArgs &A, uint32_t beta0, uint32_t rl, uint32_t lo0, const gl_t *ftw) {
   constexpr int R = 1 << LOGR;
   const uint32_t ngroups = 1u << (12 - LOGR);
@@ -467,29 +417,32 @@ __device__ __forceinline__ void round_folded(gl_t *lds, const PassArgs &A, uint3
     for (int j = 0; j < R; j++) li[j] = l0 ^ lj[j];
 #pragma unroll
     for (int j = 0; j < R; j++) v[j] = lds[li[j]];
-    const gl_t *tp = ftw + ((size_t)high << s0) + lo;
-#pragma unroll
-    for (int e = 0; e < R; e++) {
-      t[e] = *tp;
-      tp += estride;
+    load_folded(t, ftw + ((size_t)high << s0) + lo, estride);
+    if constexpr (DIT) {
+      static_for<0, R>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        v[j] = gl_mul(v[j], t[brev_c(j, LOGR)]);
+      });
     }
-    static_for<0, R>([&](auto jc) {
-      constexpr int j = decltype(jc)::value;
-      v[j] = gl_mul(v[j], t[brev_c(j, LOGR)]);
-    });
-    dft_regs<LOGR, 1, INV>(v);
+    dft_regs<LOGR, DIT, INV>(v);
+    if constexpr (!DIT) {
+      static_for<0, R>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        v[j] = gl_mul(v[j], t[brev_c(j, LOGR)]);
+      });
+    }
 #pragma unroll
     for (int j = 0; j < R; j++) lds[li[j]] = v[j];
   }
 }
-// The last round of a pass, LDS -> registers -> global: RL layers on the tile's top bits, shift twiddles (the round before had RP
-// layers; its folded table carried the rest), then the pass's output scale.
-// second swizzle, for the head pass whose first round runs in registers (ntt_dit_head2_kernel): its LDS accesses differ, within a
+// Second swizzle, for the head pass whose first round runs in registers (ntt_dit_head2_kernel): its LDS accesses differ, within a
 // lane group, in element bits {3,4,5,6} (16-lane store groups after round 0), {6..10} / {6..9} (round on bits 3-5, wave = bits 0-2),
 // {3,4,5,9,10} / {3,4,5,9} (round on bits 6-8) and {0..4} (last round): slot bits s0 = e0^e3^e6, s1 = e1^e4^e7, s2 = e2^e5^e8,
 // s3 = e3^e9, s4 = e4^e10 have full rank on each of them (found by exhaustive search over shift-and-mask forms: the only two-term
 // one).  GF(2)-linear like pidx: pidx2(a ^ b) = pidx2(a) ^ pidx2(b).
 __device__ __forceinline__ constexpr uint32_t pidx2(uint32_t e) { return e ^ ((e >> 3) & 7u) ^ ((e >> 6) & 31u); }
+// The last round of a pass, LDS -> registers -> global: RL layers on the tile's top bits, shift twiddles (the round before had RP
+// layers; its folded table carried the rest), then the pass's output scale.
 template <bool INV, int RL, int RP, int SW = 0>
 __device__ __forceinline__ void round_to_global(const gl_t *lds, gl_t *dst, const PassArgs &A, uint32_t hi_base, uint32_t lo0) {
   constexpr int R = 1 << RL;
@@ -517,18 +470,6 @@ __device__ __forceinline__ void round_to_global(const gl_t *lds, gl_t *dst, cons
     for (int j = 0; j < R; j++) dst[a0 + ((uint32_t)j << (beta0 - A.tb + A.s))] = v[j];
   }
 }
-// block -> (tile, column, coset): the XCD-aware decode of ntt_pass_kernel
-__device__ __forceinline__ bool pass_unit(const PassArgs &A, uint32_t &tile, uint32_t &col, uint32_t &coset) {
-  const uint32_t units = A.tiles * A.cols_grid;
-  const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
-  coset = slot % A.cosets;
-  const uint32_t unit = (slot / A.cosets) * 8u + xcd;
-  if (unit >= units) return false;
-  tile = unit % A.tiles;
-  col = unit / A.tiles;
-  return !(A.colnz != nullptr && A.colnz[col] != 2u);
-}
-static_assert(NTT_THREADS == 512 && NTT_TILE_BITS == 12 && NTT_PER == 8, "direct passes: 512 lanes x 8 elements");
 // The 12-layer first pass of a DIT transform of >= 2^12 points (s = 0, tb = 0: contiguous tiles), three LDS round trips and two
 // barriers.  Its FIRST round runs in registers: a lane loads 8 CONSECUTIVE words (64 B: the round on bits 0-2 is then its own eight
 // registers; a wave still covers 4 KB contiguous), scales them by the coset scale, runs the twiddle-free 8-point transform and only
@@ -544,10 +485,7 @@ __global__ __launch_bounds__(NTT_THREADS, NTT_MIN_WAVES) void ntt_dit_head2_kern
   extern __shared__ gl_t lds[];
   uint32_t tile, col, coset;
   if (!pass_unit(A, tile, col, coset)) return;
-  const size_t n = (size_t)1 << A.d;
-  const gl_t *src = A.src + ((size_t)(A.src_single ? 0 : coset) * A.cols + col) * n;
-  gl_t *dst = A.dst + ((size_t)coset * A.cols + col) * n;
-  const gl_t *scale = A.scale ? A.scale + (size_t)(A.coset_first + coset * A.coset_stride) * n : nullptr;
+  const auto [src, dst, scale] = col_ptrs(A, col, coset);
   const uint32_t tbase = tile << 12, t = threadIdx.x, w = t >> 6, l = t & 63u;
   gl_t v[8];
   {
@@ -598,9 +536,9 @@ __global__ __launch_bounds__(NTT_THREADS, NTT_MIN_WAVES) void ntt_dit_head2_kern
     for (int e = 0; e < 8; e++) tw[e] = tp[e * NTT_THREADS];
 #pragma unroll
     for (int i = 0; i < 8; i++) v[i] = lds[p0 ^ pidx2((uint32_t)i << 6)];
-    static_for<0, 8>([&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      v[i] = gl_mul(v[i], tw[brev_c(i, 3)]);
+    static_for<0, 8>([&](auto jc) {
+      constexpr int j = decltype(jc)::value;
+      v[j] = gl_mul(v[j], tw[brev_c(j, 3)]);
     });
     dft_regs<3, 1, INV>(v);
 #pragma unroll
@@ -617,12 +555,8 @@ __global__ __launch_bounds__(NTT_THREADS, NTT_MIN_WAVES) void ntt_dit_strided_ke
   extern __shared__ gl_t lds[];
   uint32_t tile, col, coset;
   if (!pass_unit(A, tile, col, coset)) return;
-  const size_t n = (size_t)1 << A.d;
-  const gl_t *src = A.src + ((size_t)(A.src_single ? 0 : coset) * A.cols + col) * n;
-  gl_t *dst = A.dst + ((size_t)coset * A.cols + col) * n;
-  const uint32_t runs = 1u << (A.s - A.tb);
-  const uint32_t hi = tile / runs, lo0 = (tile % runs) << A.tb;
-  const uint32_t hi_base = hi << (A.s + A.a);
+  const auto [src, dst, scale] = col_ptrs(A, col, coset);
+  const auto [hi_base, lo0] = tile_pos(A, tile);
   {
     // first round: group g = lane; low = its tb contiguous bits, high = the tile bits above the round
     const uint32_t g = threadIdx.x, low = g & ((1u << A.tb) - 1), high = g >> A.tb;
@@ -632,29 +566,12 @@ __global__ __launch_bounds__(NTT_THREADS, NTT_MIN_WAVES) void ntt_dit_strided_ke
 #pragma unroll
     for (int j = 0; j < 8; j++) v[j] = src[a0 + ((uint32_t)j << A.s)];
     constexpr bool FOLD1 = RM == 0 && RL != 0;  // the first round is the one before the last
-    if constexpr (FOLD1) {
-      const gl_t *tp = A.ftw + ((size_t)high << A.s) + lo;
-#pragma unroll
-      for (int e = 0; e < 8; e++) {
-        t[e] = *tp;
-        tp += (size_t)1 << (A.s + RL);
-      }
-      static_for<0, 8>([&](auto jc) {
-        constexpr int j = decltype(jc)::value;
-        v[j] = gl_mul(v[j], t[brev_c(j, 3)]);
-      });
-    } else {
-      const gl_t *tp = A.ptw + A.tw_off[0] + lo;
-#pragma unroll
-      for (int e = 1; e < 8; e++) {
-        t[e] = *tp;
-        tp += (size_t)1 << A.s;
-      }
-      static_for<1, 8>([&](auto jc) {
-        constexpr int j = decltype(jc)::value;
-        v[j] = gl_mul(v[j], t[brev_c(j, 3)]);
-      });
-    }
+    if constexpr (FOLD1) load_folded(t, A.ftw + ((size_t)high << A.s) + lo, (size_t)1 << (A.s + RL));
+    else load_packed(t, A.ptw + A.tw_off[0] + lo, (size_t)1 << A.s);
+    static_for<(FOLD1 ? 0 : 1), 8>([&](auto jc) {
+      constexpr int j = decltype(jc)::value;
+      v[j] = gl_mul(v[j], t[brev_c(j, 3)]);
+    });
     dft_regs<3, 1, INV>(v);
     if constexpr (RL == 0) {
       if (A.post != 1) {
@@ -673,14 +590,14 @@ __global__ __launch_bounds__(NTT_THREADS, NTT_MIN_WAVES) void ntt_dit_strided_ke
   if constexpr (RL != 0) {
     __syncthreads();
     if constexpr (RM != 0) {
-      round_folded<INV, RM>(lds, A, A.tb + 3, RL, lo0, A.ftw);
+      round_folded<1, INV, RM>(lds, A, A.tb + 3, RL, lo0, A.ftw);
       __syncthreads();
     }
     round_to_global<INV, RL, (RM != 0 ? RM : 3)>(lds, dst, A, hi_base, lo0);
   }
 }
 
-// ---- the mirror images for the inverse (DIF) transforms: values -> coefficients -------------------------------------------------
+// ---- the mirror images: values -> coefficients (DIF) ----------------------------------------------------------------------------
 // A DIF round multiplies its OUTPUTS: after the round on [beta, beta + r) output j takes w^-(lo brev(j)), lo = the element's bits
 // below beta.  For the pass's FIRST (top) round lo = lo' + 2^s0' k with k the INPUT index of the round below: w^-(2^s0' k brev(j)) is a
 // power of w_64 -- a shift, k wave-uniform -- applied at once, and w^-(lo' brev(j)) is constant over the group of the round below
@@ -705,42 +622,6 @@ __device__ __forceinline__ void round_from_global(const gl_t *src, gl_t *lds, co
     for (int j = 0; j < R; j++) lds[l0 ^ sw((uint32_t)j << beta0)] = v[j];
   }
 }
-// DIF round in LDS whose OUTPUT twiddles are the folded table (its own general twiddle x the top round's deferred part)
-template <bool INV, int LOGR>
-__device__ __forceinline__ void round_folded_dif(gl_t *lds, const PassArgs &A, uint32_t beta0, uint32_t rl, uint32_t lo0, const gl_t *ftw) {
-  constexpr int R = 1 << LOGR;
-  const uint32_t ngroups = 1u << (12 - LOGR);
-  const uint32_t s0 = beta0 - A.tb + A.s;
-  uint32_t lj[R];
-#pragma unroll
-  for (int j = 0; j < R; j++) lj[j] = pidx((uint32_t)j << beta0);
-  const size_t estride = (size_t)1 << (s0 + rl);
-  for (uint32_t g = threadIdx.x; g < ngroups; g += NTT_THREADS) {
-    const uint32_t low = g & ((1u << beta0) - 1), high = g >> beta0;
-    const uint32_t base = (high << (beta0 + LOGR)) | low;
-    const uint32_t lo = ((low >> A.tb) << A.s) + lo0 + (low & ((1u << A.tb) - 1));
-    gl_t v[R], t[R];
-    uint32_t li[R];
-    const uint32_t l0 = pidx(base);
-#pragma unroll
-    for (int j = 0; j < R; j++) li[j] = l0 ^ lj[j];
-#pragma unroll
-    for (int j = 0; j < R; j++) v[j] = lds[li[j]];
-    const gl_t *tp = ftw + ((size_t)high << s0) + lo;
-#pragma unroll
-    for (int e = 0; e < R; e++) {
-      t[e] = *tp;
-      tp += estride;
-    }
-    dft_regs<LOGR, 0, INV>(v);
-    static_for<0, R>([&](auto jc) {
-      constexpr int j = decltype(jc)::value;
-      v[j] = gl_mul(v[j], t[brev_c(j, LOGR)]);
-    });
-#pragma unroll
-    for (int j = 0; j < R; j++) lds[li[j]] = v[j];
-  }
-}
 // A strided DIF pass of a = 3 + RM + RL layers: top round (RL layers) global -> registers -> LDS with shift twiddles, [middle round
 // in LDS with the folded table,] bottom round (3 layers) LDS -> registers -> global.  RL = 0: a = 3, one round, no LDS.
 template <bool INV, int RM, int RL>
@@ -748,17 +629,13 @@ __global__ __launch_bounds__(NTT_THREADS, NTT_MIN_WAVES) void ntt_dif_strided_ke
   extern __shared__ gl_t lds[];
   uint32_t tile, col, coset;
   if (!pass_unit(A, tile, col, coset)) return;
-  const size_t n = (size_t)1 << A.d;
-  const gl_t *src = A.src + ((size_t)(A.src_single ? 0 : coset) * A.cols + col) * n;
-  gl_t *dst = A.dst + ((size_t)coset * A.cols + col) * n;
-  const uint32_t runs = 1u << (A.s - A.tb);
-  const uint32_t hi = tile / runs, lo0 = (tile % runs) << A.tb;
-  const uint32_t hi_base = hi << (A.s + A.a);
+  const auto [src, dst, scale] = col_ptrs(A, col, coset);
+  const auto [hi_base, lo0] = tile_pos(A, tile);
   if constexpr (RL != 0) {
     round_from_global<INV, RL, (RM != 0 ? RM : 3)>(src, lds, A, hi_base, lo0);
     __syncthreads();
     if constexpr (RM != 0) {
-      round_folded_dif<INV, RM>(lds, A, A.tb + 3, RL, lo0, A.ftw);
+      round_folded<0, INV, RM>(lds, A, A.tb + 3, RL, lo0, A.ftw);
       __syncthreads();
     }
   }
@@ -777,21 +654,8 @@ __global__ __launch_bounds__(NTT_THREADS, NTT_MIN_WAVES) void ntt_dif_strided_ke
       for (int j = 0; j < 8; j++) v[j] = lds[l0 ^ pidx((uint32_t)j << A.tb)];
     }
     constexpr bool FOLD1 = RM == 0 && RL != 0;  // the bottom round is the one below the top
-    if constexpr (FOLD1) {
-      const gl_t *tp = A.ftw + ((size_t)high << A.s) + lo;
-#pragma unroll
-      for (int e = 0; e < 8; e++) {
-        t[e] = *tp;
-        tp += (size_t)1 << (A.s + RL);
-      }
-    } else {
-      const gl_t *tp = A.ptw + A.tw_off[0] + lo;
-#pragma unroll
-      for (int e = 1; e < 8; e++) {
-        t[e] = *tp;
-        tp += (size_t)1 << A.s;
-      }
-    }
+    if constexpr (FOLD1) load_folded(t, A.ftw + ((size_t)high << A.s) + lo, (size_t)1 << (A.s + RL));
+    else load_packed(t, A.ptw + A.tw_off[0] + lo, (size_t)1 << A.s);
     dft_regs<3, 0, INV>(v);
     static_for<(FOLD1 ? 0 : 1), 8>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
@@ -813,9 +677,7 @@ __global__ __launch_bounds__(NTT_THREADS, NTT_MIN_WAVES) void ntt_dif_tail2_kern
   extern __shared__ gl_t lds[];
   uint32_t tile, col, coset;
   if (!pass_unit(A, tile, col, coset)) return;
-  const size_t n = (size_t)1 << A.d;
-  const gl_t *src = A.src + ((size_t)(A.src_single ? 0 : coset) * A.cols + col) * n;
-  gl_t *dst = A.dst + ((size_t)coset * A.cols + col) * n;
+  const auto [src, dst, scale] = col_ptrs(A, col, coset);
   const uint32_t tbase = tile << 12, t = threadIdx.x, w = t >> 6, l = t & 63u;
   round_from_global<INV, 3, 3, 1>(src, lds, A, tbase, 0);
   __syncthreads();
@@ -829,9 +691,9 @@ __global__ __launch_bounds__(NTT_THREADS, NTT_MIN_WAVES) void ntt_dif_tail2_kern
 #pragma unroll
     for (int i = 0; i < 8; i++) v[i] = lds[p0 ^ pidx2((uint32_t)i << 6)];
     dft_regs<3, 0, INV>(v);
-    static_for<0, 8>([&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      v[i] = gl_mul(v[i], tw[brev_c(i, 3)]);
+    static_for<0, 8>([&](auto jc) {
+      constexpr int j = decltype(jc)::value;
+      v[j] = gl_mul(v[j], tw[brev_c(j, 3)]);
     });
 #pragma unroll
     for (int i = 0; i < 8; i++) lds[p0 ^ pidx2((uint32_t)i << 6)] = v[i];
@@ -862,8 +724,6 @@ __global__ __launch_bounds__(NTT_THREADS, NTT_MIN_WAVES) void ntt_dif_tail2_kern
   for (int i = 0; i < 4; i++) d2[i] = make_ulonglong2(v[2 * i], v[2 * i + 1]);
 }
 
-static inline size_t lds_bytes(uint32_t TB) { return std::max<size_t>((size_t)1 << TB, 256) * sizeof(gl_t); }  // no padding: pidx() is a permutation of every 256-element block
-
 // ---- plan -----------------------------------------------------------------------
 // packed twiddles of one round: T[(e-1) * M + lo] = root_n^((lo * e) << (d - s0 - r)), e in [1, 2^r)
 __global__ void round_table_kernel(gl_t *out, gl_t root_n, uint32_t d, uint32_t s0, uint32_t r) {
@@ -893,135 +753,6 @@ __global__ void head_fold_table_kernel(gl_t *out, gl_t root_n, uint32_t d) {
   const uint64_t ex = (((uint64_t)lo * e) << (d - 9)) + (((uint64_t)lo * bitrev32(J, 3)) << (d - 12));
   out[i] = gl_pow(root_n, ex);
 }
-// P2GPU_NTT_DIRECT=0: every pass through ntt_pass_kernel (A/B measurements, and the reference the direct kernels are tested against)
-static bool direct_on() {
-  static const bool on = env_flag("P2GPU_NTT_DIRECT", true);
-  return on;
-}
-
-static void split_rounds(uint32_t a, std::vector<uint32_t> &r) {
-  // rounds of LMAX layers (LMAX = log2 NTT_PER), remainder fixed up without ever using a lone 1 when avoidable
-  const uint32_t LMAX = NTT_PER == 16 ? 4 : 3;
-  r.clear();
-  uint32_t q = a / LMAX, rem = a % LMAX;
-  if (rem == 1 && q >= 1 && LMAX >= 3) {  // L + 1 -> (L - 1) + 2
-    for (uint32_t i = 0; i + 1 < q; i++) r.push_back(LMAX);
-    r.push_back(LMAX - 1);
-    r.push_back(2);
-  } else {
-    for (uint32_t i = 0; i < q; i++) r.push_back(LMAX);
-    if (rem) r.push_back(rem);
-  }
-}
-
-NttPlan *ntt_plan_create(hipStream_t st, uint32_t d, int dit, bool inverse) {
-  NttPlan *p = new NttPlan();
-  p->d = d;
-  p->dit = dit;
-  p->inverse = inverse;
-  const uint32_t TBMAX = NTT_TILE_BITS;
-  const uint32_t b = d < TBMAX ? d : TBMAX;
-  struct P { uint32_t s, a, tb; };
-  std::vector<P> strided;
-  {
-    uint32_t rem = d - b, s = b;
-    uint32_t npass = rem == 0 ? 0 : (rem <= 9 ? 1 : 2);
-    for (uint32_t i = 0; i < npass; i++) {
-      uint32_t a = (npass == 1) ? rem : (i == 0 ? (rem + 1) / 2 : rem / 2);
-      uint32_t tb = TBMAX - a;
-      if (tb > s) tb = s;
-      strided.push_back(P{s, a, tb});
-      s += a;
-    }
-  }
-  std::vector<P> passes;
-  if (dit) {
-    passes.push_back(P{0, b, 0});
-    for (auto &x : strided) passes.push_back(x);
-  } else {
-    for (size_t i = strided.size(); i-- > 0;) passes.push_back(strided[i]);
-    passes.push_back(P{0, b, 0});
-  }
-  // table layout
-  size_t total = 0;
-  std::vector<uint32_t> rr;
-  for (auto &ps : passes) {
-    NttPass np;
-    np.s = ps.s; np.a = ps.a; np.tb = ps.tb;
-    split_rounds(ps.a, rr);
-    np.nrounds = (uint32_t)rr.size();
-    if (np.nrounds > (uint32_t)MAX_ROUNDS) {  // (cannot happen for tiles of <= 2^16 elements)
-      delete p;
-      return nullptr;
-    }
-    uint32_t beta = ps.tb;
-    for (uint32_t i = 0; i < np.nrounds; i++) {
-      np.r[i] = rr[i];
-      np.tw_off[i] = (uint32_t)total;
-      uint32_t s0 = beta - ps.tb + ps.s;
-      if (s0 > 0) total += (size_t)((1u << rr[i]) - 1) << s0;
-      beta += rr[i];
-    }
-    // the direct form (DIT, full tiles): the 12-layer head [3,3,3,3], strided passes [3], [3,2], [3,3], [3,2,2], [3,3,2], [3,3,3]
-    if (((dit && !inverse) || (!dit && inverse)) && NTT_TILE_BITS == 12 && NTT_PER == 8 && ps.a + ps.tb == 12 && np.r[0] == 3 &&
-        (ps.s == 0 ? (ps.a == 12) : (ps.a == 3 || (ps.a >= 5 && ps.a <= 9)))) {
-      np.direct = true;
-      if (np.nrounds >= 2) {
-        const uint32_t q = np.nrounds - 2, rl = np.r[np.nrounds - 1];  // the round before the last
-        uint32_t bq = ps.tb;
-        for (uint32_t i = 0; i < q; i++) bq += np.r[i];
-        if (ps.s == 0) {  // the head pass: its 4096 folded twiddles in the lane order of ntt_dit_head2_kernel / ntt_dif_tail2_kernel
-          np.ftw2_off = (uint32_t)total;
-          total += 4096;
-        } else {
-          np.ftw_off = (uint32_t)total;
-          total += (size_t)1 << (np.r[q] + rl + (bq - ps.tb + ps.s));
-        }
-      }
-    }
-    p->passes.push_back(np);
-  }
-  p->table_len = total;
-  if (total >> 32) {  // tw_off / ftw_off / ftw2_off are 32-bit word offsets (d = 24 with its folded tables: ~2^25 words)
-    delete p;
-    return nullptr;
-  }
-  if (total) {
-    if (hipMalloc((void **)&p->ptw, total * sizeof(gl_t)) != hipSuccess) {
-      delete p;
-      return nullptr;
-    }
-    gl_t root = gl_root(d);
-    if (inverse) root = gl_inv(root);
-    for (auto &np : p->passes) {
-      uint32_t beta = np.tb;
-      for (uint32_t i = 0; i < np.nrounds; i++) {
-        uint32_t s0 = beta - np.tb + np.s;
-        if (s0 > 0) {
-          uint32_t cnt = ((1u << np.r[i]) - 1) << s0;
-          hipLaunchKernelGGL(round_table_kernel, dim3((cnt + 255) / 256), dim3(256), 0, st, p->ptw + np.tw_off[i], root, d,
-                             s0, np.r[i]);
-        }
-        beta += np.r[i];
-      }
-      if (np.direct && np.nrounds >= 2) {
-        const uint32_t q = np.nrounds - 2, rl = np.r[np.nrounds - 1];
-        uint32_t bq = np.tb;
-        for (uint32_t i = 0; i < q; i++) bq += np.r[i];
-        const uint32_t s0 = bq - np.tb + np.s, cnt = 1u << (np.r[q] + rl + s0);
-        if (np.s == 0) hipLaunchKernelGGL(head_fold_table_kernel, dim3(16), dim3(256), 0, st, p->ptw + np.ftw2_off, root, d);
-        else hipLaunchKernelGGL(fold_table_kernel, dim3((cnt + 255) / 256), dim3(256), 0, st, p->ptw + np.ftw_off, root, d, s0, np.r[q], rl);
-      }
-    }
-  }
-  return p;
-}
-void ntt_plan_destroy(NttPlan *p) {
-  if (!p) return;
-  if (p->ptw) (void)hipFree(p->ptw);
-  delete p;
-}
-
 // The whole transform of the structured columns of a batch (ColHints): class 0 -> zeros (not even stored when the
 // column's clean mark says dst holds them already), class 1 -> val[c] * basis.  One lane per 2 elements, coalesced;
 // blocks of dense columns return at once.  By linearity these are the canonical values the butterfly network
@@ -1061,14 +792,41 @@ __global__ __launch_bounds__(256) void structured_fill_kernel(gl_t *dst, uint32_
   }
 }
 
-static void fill_pass_args(PassArgs &A, const NttPlan *plan, size_t i, const gl_t *src, gl_t *dst, uint32_t cols, uint32_t cosets,
-                           const gl_t *scale, gl_t post, bool src_per_coset, CosetMap cm, uint32_t stride_all, const uint32_t *colnz) {
+namespace {
+
+size_t lds_bytes(uint32_t TB) { return std::max<size_t>((size_t)1 << TB, 256) * sizeof(gl_t); }  // no padding: pidx() is a permutation of every 256-element block
+
+// P2GPU_NTT_DIRECT=0: every pass through ntt_pass_kernel (A/B measurements, and the reference the direct kernels are tested against)
+bool direct_on() {
+  static const bool on = env_flag("P2GPU_NTT_DIRECT", true);
+  return on;
+}
+
+// rounds of three layers; a remainder of one layer joins the round before it as 2 + 2 (a lone 1 only when a == 1)
+void split_rounds(uint32_t a, std::vector<uint32_t> &r) {
+  r.assign(a / 3, 3);
+  if (a % 3 == 1 && a >= 4) {
+    r.back() = 2;
+    r.push_back(2);
+  } else if (a % 3) {
+    r.push_back(a % 3);
+  }
+}
+
+// Does the pass have a direct kernel?  Full tiles whose first round has three layers: the 12-layer contiguous pass [3,3,3,3]
+// (head / tail) and the strided passes [3], [3,2], [3,3], [3,2,2], [3,3,2], [3,3,3].
+bool has_direct_form(const NttPass &ps) {
+  return ps.a + ps.tb == NTT_TILE_BITS && ps.r[0] == 3 && (ps.s == 0 ? ps.a == 12 : (ps.a == 3 || (ps.a >= 5 && ps.a <= 9)));
+}
+
+void fill_pass_args(PassArgs &A, const NttPlan *plan, size_t i, const gl_t *src, gl_t *dst, uint32_t cols, uint32_t cosets,
+                    const gl_t *scale, gl_t post, bool src_per_coset, CosetMap cm, uint32_t stride_all, const uint32_t *colnz) {
   const size_t np = plan->passes.size();
   const NttPass &ps = plan->passes[i];
   A.src = (i == 0) ? src : dst;
   A.dst = dst;
   A.ptw = plan->ptw;
-  A.scale = (i == 0 && plan->dit) ? scale : nullptr;
+  A.scale = (i == 0 && plan->dir == NttDir::ToValues) ? scale : nullptr;
   A.post = (i == np - 1) ? post : 1;
   A.d = plan->d;
   A.s = ps.s; A.a = ps.a; A.tb = ps.tb;
@@ -1079,95 +837,155 @@ static void fill_pass_args(PassArgs &A, const NttPlan *plan, size_t i, const gl_
   A.nrounds = ps.nrounds;
   A.colnz = colnz;
   A.ftw = ps.direct && ps.s != 0 ? plan->ptw + ps.ftw_off : nullptr;
-  A.ftw2 = ps.direct && ps.s == 0 ? plan->ptw + ps.ftw2_off : nullptr;
+  A.ftw2 = ps.direct && ps.s == 0 ? plan->ptw + ps.ftw_off : nullptr;
   for (int k = 0; k < MAX_ROUNDS; k++) { A.r[k] = ps.r[k]; A.tw_off[k] = ps.tw_off[k]; }
   A.tiles = 1u << (plan->d - (A.a + A.tb));
   A.cols_grid = cols; A.cosets = cosets;
 }
-// same spelling as rocprofv3's demangled kernel names, so the bench line and profiles/ agree
-static const char *pass_kernel_name(const NttPlan *plan, bool full) {
-  // string literals: the profiler keeps the pointer
-  static const char *const names[2][2][2] = {
-      {{"ntt_pass_kernel<0, false, 0>", "ntt_pass_kernel<0, true, 0>"}, {"ntt_pass_kernel<1, false, 0>", "ntt_pass_kernel<1, true, 0>"}},
-      {{"ntt_pass_kernel<0, false, 12>", "ntt_pass_kernel<0, true, 12>"}, {"ntt_pass_kernel<1, false, 12>", "ntt_pass_kernel<1, true, 12>"}}};
-  // (the "12" in the names is NTT_TILE_BITS of the default build)
-  return names[full ? 1 : 0][plan->dit ? 1 : 0][plan->inverse ? 1 : 0];
+
+template <int DIT, bool INV>
+void launch_generic(hipStream_t st, const PassArgs &A, dim3 grid, uint32_t TB, size_t lb) {
+  if (TB == NTT_TILE_BITS) hipLaunchKernelGGL((ntt_pass_kernel<DIT, INV, NTT_TILE_BITS>), grid, dim3(NTT_THREADS), lb, st, A);
+  else hipLaunchKernelGGL((ntt_pass_kernel<DIT, INV, 0>), grid, dim3(TB >= 8 ? 256 : 64), lb, st, A);
 }
-// (Both passes of a two-pass transform in ONE launch -- per-XCD work queues, the intermediate handed over through L2 -- was built in
-// round 4, bit-exact, and measured slower and heavier on HBM than two launches: profiles/r04_lde_fused.md; removed in round 5,
-// `git show 33c653e:acvm-backend-plonky2_amd/csrc/ntt.hip` has it.)
-static void ntt_passes(hipStream_t st, const NttPlan *plan, const gl_t *src, gl_t *dst, uint32_t cols, uint32_t cosets,
-                       const gl_t *scale, gl_t post, bool src_per_coset, CosetMap cm, uint32_t stride_all, const uint32_t *colnz,
-                       uint32_t dense) {
+
+// (Both passes of a two-pass transform in ONE launch -- per-XCD work queues, the intermediate handed over through L2 -- was
+// built, bit-exact, and measured slower and heavier on HBM than two launches: profiles/r04_lde_fused.md;
+// `git show 33c653e:acvm-backend-plonky2_amd/csrc/ntt.hip` has it, and 891bf88 is the last commit with the NTT_EXP_* timing
+// experiments and the radix-16 / 2^13-tile build knobs.)
+// The names given to ProfScope are rocprofv3's demangled symbols, so the bench line and profiles/ agree; string literals: the
+// profiler keeps the pointer.
+void ntt_passes(hipStream_t st, const NttPlan *plan, const gl_t *src, gl_t *dst, uint32_t cols, uint32_t cosets,
+                const gl_t *scale, gl_t post, bool src_per_coset, CosetMap cm, uint32_t stride_all, const uint32_t *colnz,
+                uint32_t dense) {
   const uint32_t d = plan->d;
-  const size_t np = plan->passes.size();
-  for (size_t i = 0; i < np; i++) {
+  const bool dit = plan->dir == NttDir::ToValues;
+  for (size_t i = 0; i < plan->passes.size(); i++) {
+    const NttPass &ps = plan->passes[i];
     PassArgs A;
     fill_pass_args(A, plan, i, src, dst, cols, cosets, scale, post, src_per_coset, cm, stride_all, colnz);
     const uint32_t TB = A.a + A.tb;
     dim3 grid((((A.tiles * cols + 7u) / 8u) * 8u) * cosets);
-    const uint32_t threads = TB >= 8 ? 256 : 64;
     // expected HBM bytes: every output element is written once; the input is read once per element, except
     // that the cosets of one (tile, column) share their source through one XCD's L2 (first LDE pass)
     // (structured columns are skipped by the kernels: `dense`, when the caller knows it, is what the launch really transforms)
     const double bytes = 8.0 * (double)(dense ? dense : cols) * ((size_t)1 << d) * (cosets + (A.src_single ? 1.0 : (double)cosets));
     const size_t lb = lds_bytes(TB);
-    if (plan->passes[i].direct && direct_on()) {
-      const NttPass &ps = plan->passes[i];
-      const uint32_t rm = ps.nrounds == 3 ? ps.r[1] : 0, rl = ps.nrounds >= 2 ? ps.r[ps.nrounds - 1] : 0;
-      // (profile names = rocprofv3's demangled symbols)
-      if (!plan->dit) {
-        if (ps.s == 0) {
-          ProfScope psd("ntt_dif_tail2_kernel<true>", bytes);
-          hipLaunchKernelGGL((ntt_dif_tail2_kernel<true>), grid, dim3(NTT_THREADS), lb, st, A);
-        } else {
-#define P2_STRIDED_DIF(RM, RL)                                                                                    \
-  do {                                                                                                            \
-    ProfScope psd("ntt_dif_strided_kernel<true, " #RM ", " #RL ">", bytes);                                       \
-    hipLaunchKernelGGL((ntt_dif_strided_kernel<true, RM, RL>), grid, dim3(NTT_THREADS), (RL) ? lb : 0, st, A);     \
-  } while (0)
-          if (rm == 0 && rl == 0) P2_STRIDED_DIF(0, 0);
-          else if (rm == 0 && rl == 2) P2_STRIDED_DIF(0, 2);
-          else if (rm == 0 && rl == 3) P2_STRIDED_DIF(0, 3);
-          else if (rm == 2 && rl == 2) P2_STRIDED_DIF(2, 2);
-          else if (rm == 3 && rl == 2) P2_STRIDED_DIF(3, 2);
-          else P2_STRIDED_DIF(3, 3);
-#undef P2_STRIDED_DIF
-        }
-      } else if (ps.s == 0) {
-        ProfScope psd("ntt_dit_head2_kernel<false>", bytes);
-        hipLaunchKernelGGL((ntt_dit_head2_kernel<false>), grid, dim3(NTT_THREADS), lb, st, A);
-      } else {
-#define P2_STRIDED(RM, RL)                                                                                        \
-  do {                                                                                                            \
-    ProfScope psd("ntt_dit_strided_kernel<false, " #RM ", " #RL ">", bytes);                                      \
-    hipLaunchKernelGGL((ntt_dit_strided_kernel<false, RM, RL>), grid, dim3(NTT_THREADS), (RL) ? lb : 0, st, A);    \
-  } while (0)
-        if (rm == 0 && rl == 0) P2_STRIDED(0, 0);
-        else if (rm == 0 && rl == 2) P2_STRIDED(0, 2);
-        else if (rm == 0 && rl == 3) P2_STRIDED(0, 3);
-        else if (rm == 2 && rl == 2) P2_STRIDED(2, 2);
-        else if (rm == 3 && rl == 2) P2_STRIDED(3, 2);
-        else P2_STRIDED(3, 3);
-#undef P2_STRIDED
-      }
-      continue;
-    }
-    ProfScope psx(pass_kernel_name(plan, TB == NTT_TILE_BITS), bytes);
-#define P2_LAUNCH(DITV, INVV)                                                                                \
-  do {                                                                                                       \
-    if (TB == NTT_TILE_BITS) hipLaunchKernelGGL((ntt_pass_kernel<DITV, INVV, NTT_TILE_BITS>), grid, dim3(NTT_THREADS), lb, st, A);           \
-    else hipLaunchKernelGGL((ntt_pass_kernel<DITV, INVV, 0>), grid, dim3(threads), lb, st, A);               \
-  } while (0)
-    if (plan->dit) {
-      if (plan->inverse) P2_LAUNCH(1, true);
-      else P2_LAUNCH(1, false);
+    if (!(ps.direct && direct_on())) {
+      ProfScope psx(dit ? (TB == NTT_TILE_BITS ? "ntt_pass_kernel<1, false, 12>" : "ntt_pass_kernel<1, false, 0>")
+                        : (TB == NTT_TILE_BITS ? "ntt_pass_kernel<0, true, 12>" : "ntt_pass_kernel<0, true, 0>"), bytes);
+      if (dit) launch_generic<1, false>(st, A, grid, TB, lb);
+      else launch_generic<0, true>(st, A, grid, TB, lb);
+    } else if (ps.s == 0) {
+      ProfScope psd(dit ? "ntt_dit_head2_kernel<false>" : "ntt_dif_tail2_kernel<true>", bytes);
+      if (dit) hipLaunchKernelGGL((ntt_dit_head2_kernel<false>), grid, dim3(NTT_THREADS), lb, st, A);
+      else hipLaunchKernelGGL((ntt_dif_tail2_kernel<true>), grid, dim3(NTT_THREADS), lb, st, A);
     } else {
-      if (plan->inverse) P2_LAUNCH(0, true);
-      else P2_LAUNCH(0, false);
+#define P2_STRIDED(RM, RL)                                                                                               \
+  do {                                                                                                                   \
+    ProfScope psd(dit ? "ntt_dit_strided_kernel<false, " #RM ", " #RL ">" : "ntt_dif_strided_kernel<true, " #RM ", " #RL ">", bytes); \
+    if (dit) hipLaunchKernelGGL((ntt_dit_strided_kernel<false, RM, RL>), grid, dim3(NTT_THREADS), (RL) ? lb : 0, st, A);  \
+    else hipLaunchKernelGGL((ntt_dif_strided_kernel<true, RM, RL>), grid, dim3(NTT_THREADS), (RL) ? lb : 0, st, A);       \
+  } while (0)
+      if (ps.rm == 0 && ps.rl == 0) P2_STRIDED(0, 0);
+      else if (ps.rm == 0 && ps.rl == 2) P2_STRIDED(0, 2);
+      else if (ps.rm == 0 && ps.rl == 3) P2_STRIDED(0, 3);
+      else if (ps.rm == 2 && ps.rl == 2) P2_STRIDED(2, 2);
+      else if (ps.rm == 3 && ps.rl == 2) P2_STRIDED(3, 2);
+      else P2_STRIDED(3, 3);
+#undef P2_STRIDED
     }
-#undef P2_LAUNCH
   }
+}
+
+}  // namespace
+
+NttPlan *ntt_plan_create(hipStream_t st, uint32_t d, NttDir dir) {
+  std::unique_ptr<NttPlan, decltype(&ntt_plan_destroy)> p(new NttPlan(), ntt_plan_destroy);
+  p->d = d;
+  p->dir = dir;
+  const uint32_t TBMAX = NTT_TILE_BITS;
+  const uint32_t b = d < TBMAX ? d : TBMAX;
+  struct P { uint32_t s, a, tb; };
+  std::vector<P> strided;
+  {
+    uint32_t rem = d - b, s = b;
+    uint32_t npass = rem == 0 ? 0 : (rem <= 9 ? 1 : 2);
+    for (uint32_t i = 0; i < npass; i++) {
+      uint32_t a = (npass == 1) ? rem : (i == 0 ? (rem + 1) / 2 : rem / 2);
+      uint32_t tb = TBMAX - a;
+      if (tb > s) tb = s;
+      strided.push_back(P{s, a, tb});
+      s += a;
+    }
+  }
+  std::vector<P> passes;
+  if (dir == NttDir::ToValues) {
+    passes.push_back(P{0, b, 0});
+    for (auto &x : strided) passes.push_back(x);
+  } else {
+    for (size_t i = strided.size(); i-- > 0;) passes.push_back(strided[i]);
+    passes.push_back(P{0, b, 0});
+  }
+  // table layout
+  size_t total = 0;
+  std::vector<uint32_t> rr;
+  for (auto &ps : passes) {
+    NttPass np;
+    np.s = ps.s; np.a = ps.a; np.tb = ps.tb;
+    split_rounds(ps.a, rr);
+    np.nrounds = (uint32_t)rr.size();
+    if (np.nrounds > (uint32_t)MAX_ROUNDS) return nullptr;  // (cannot happen: a <= 12 layers are four rounds)
+    uint32_t beta = ps.tb;
+    for (uint32_t i = 0; i < np.nrounds; i++) {
+      np.r[i] = rr[i];
+      np.tw_off[i] = (uint32_t)total;
+      uint32_t s0 = beta - ps.tb + ps.s;
+      if (s0 > 0) total += (size_t)((1u << rr[i]) - 1) << s0;
+      if (i + 2 == np.nrounds) np.fold_s0 = s0;
+      beta += rr[i];
+    }
+    np.direct = has_direct_form(np);
+    if (np.direct && np.nrounds >= 2) {
+      np.rm = np.nrounds == 3 ? np.r[1] : 0;
+      np.rl = np.r[np.nrounds - 1];
+      np.fold_r = np.r[np.nrounds - 2];
+      np.ftw_off = (uint32_t)total;
+      // (the 12-layer pass: 8 x 512 words in the lane order of ntt_dit_head2_kernel / ntt_dif_tail2_kernel)
+      total += ps.s == 0 ? 4096 : (size_t)1 << (np.fold_r + np.rl + np.fold_s0);
+    }
+    p->passes.push_back(np);
+  }
+  p->table_len = total;
+  if (total >> 32) return nullptr;  // tw_off / ftw_off are 32-bit word offsets (d = 24 with its folded tables: ~2^25 words)
+  if (total) {
+    if (hipMalloc((void **)&p->ptw, total * sizeof(gl_t)) != hipSuccess) return nullptr;
+    gl_t root = gl_root(d);
+    if (dir == NttDir::ToCoeffs) root = gl_inv(root);
+    for (auto &np : p->passes) {
+      uint32_t beta = np.tb;
+      for (uint32_t i = 0; i < np.nrounds; i++) {
+        uint32_t s0 = beta - np.tb + np.s;
+        if (s0 > 0) {
+          uint32_t cnt = ((1u << np.r[i]) - 1) << s0;
+          hipLaunchKernelGGL(round_table_kernel, dim3((cnt + 255) / 256), dim3(256), 0, st, p->ptw + np.tw_off[i], root, d,
+                             s0, np.r[i]);
+        }
+        beta += np.r[i];
+      }
+      if (np.direct && np.nrounds >= 2) {
+        const uint32_t cnt = 1u << (np.fold_r + np.rl + np.fold_s0);
+        if (np.s == 0) hipLaunchKernelGGL(head_fold_table_kernel, dim3(16), dim3(256), 0, st, p->ptw + np.ftw_off, root, d);
+        else hipLaunchKernelGGL(fold_table_kernel, dim3((cnt + 255) / 256), dim3(256), 0, st, p->ptw + np.ftw_off, root, d, np.fold_s0, np.fold_r, np.rl);
+      }
+    }
+  }
+  return p.release();
+}
+void ntt_plan_destroy(NttPlan *p) {
+  if (!p) return;
+  if (p->ptw) (void)hipFree(p->ptw);
+  delete p;
 }
 
 void ntt_batch(hipStream_t st, const NttPlan *plan, const gl_t *src, gl_t *dst, uint32_t cols, uint32_t cosets,
@@ -1192,168 +1010,6 @@ void ntt_batch(hipStream_t st, const NttPlan *plan, const gl_t *src, gl_t *dst, 
   }
   ntt_passes(st, plan, src, dst, cols, cosets, scale, post, src_per_coset, cm, stride_cols ? stride_cols : cols, hints ? hints->cls : nullptr,
              hints && hints->dense_hint && hints->dense_hint <= cols ? hints->dense_hint : 0);
-}
-
-// ---- zero-column flags --------------------------------------------------------------
-// Class of every column of vals [cols][n] (flags zeroed by the launcher): 0 = zero in every row; 1 = zero in every
-// row but `sparse_row`, whose value goes to scalar[c]; 2 = anything else.  plonky2's build() hangs a random value
-// on every unused wire of the PublicInputGate row (circuit_builder.rs randomize_unused_pi_wires; visible in the
-// reference's own proofs, tests/golden/reference_proofs.py), so in a real witness the wires no gate uses are
-// class 1 with that row, not class 0.  sparse_row = UINT32_MAX: no such row.
-__global__ __launch_bounds__(256) void column_nonzero_kernel(const gl_t *__restrict__ vals, uint32_t d, SparseRows rows,
-                                                             uint32_t *flags, gl_t *scalar, uint32_t sstride) {
-  const size_t n = (size_t)1 << d;
-  const gl_t *p = vals + (size_t)blockIdx.y * n;
-  uint64_t acc = 0;
-  const size_t step = (size_t)gridDim.x * blockDim.x;
-  const uint32_t r0 = rows.row[0], r1 = rows.row[1], r2 = rows.row[2], r3 = rows.row[3];  // UINT32_MAX: never matches
-#pragma unroll 8
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
-    const gl_t v = p[i];
-    acc |= (i == r0 || i == r1 || i == r2 || i == r3) ? (gl_t)0 : v;  // a select, not a branch: the loads stay batched
-  }
-  // dense: a plain store (every wave of a dense column would otherwise hammer one address with atomics); the other
-  // classes are told apart from the special rows' values by column_class_kernel, launched behind this one
-  if (__any(acc != 0) && (threadIdx.x & 63) == 0) flags[blockIdx.y] = 2u;
-  if (blockIdx.x == 0 && threadIdx.x < rows.count) scalar[(size_t)threadIdx.x * sstride + blockIdx.y] = p[rows.row[threadIdx.x]];
-}
-__global__ void column_class_kernel(uint32_t *flags, const gl_t *scalar, uint32_t sstride, uint32_t nrows, uint32_t cols) {
-  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= cols || flags[c] == 2u) return;
-  bool more = false;
-  for (uint32_t s = 1; s < nrows; s++) more |= scalar[(size_t)s * sstride + c] != 0;
-  flags[c] = more ? 3u : ((nrows && scalar[c] != 0) ? 1u : 0u);
-}
-// "clean" bookkeeping of the buffers a column's transforms are written to (coefficients + LDE), so that the zeros of
-// an unused wire are stored once per handle instead of once per proof.  Both steps are stream-ordered around the
-// transforms: BEFORE them a non-zero column loses its clean mark (its buffers are about to be overwritten), AFTER them
-// a zero column gains it (its buffers now hold zeros).  Anything that aborts in between leaves marks only cleared.
-__global__ void column_clean_kernel(const uint32_t *nz, uint32_t cols, uint32_t *clean, int after) {
-  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= cols) return;
-  if (after) {
-    if (nz[c] == 0) clean[c] = 1;
-  } else {
-    if (nz[c] != 0) clean[c] = 0;
-  }
-}
-void column_clean_update(hipStream_t st, const uint32_t *nz, uint32_t cols, uint32_t *clean, bool after) {
-  if (!cols) return;
-  hipLaunchKernelGGL(column_clean_kernel, dim3((cols + 255) / 256), dim3(256), 0, st, nz, cols, clean, after ? 1 : 0);
-}
-void column_flags(hipStream_t st, const gl_t *vals, uint32_t cols, uint32_t d, const SparseRows &rows, uint32_t *flags,
-                  gl_t *scalar, uint32_t sstride) {
-  if (!cols) return;
-  (void)hipMemsetAsync(flags, 0, sizeof(uint32_t) * cols, st);
-  const size_t n = (size_t)1 << d;
-  const uint32_t bx = (uint32_t)std::max<size_t>(1, n / (256 * 8));
-  ProfScope ps("column_nonzero_kernel", 8.0 * cols * (double)n);
-  hipLaunchKernelGGL(column_nonzero_kernel, dim3(bx, cols), dim3(256), 0, st, vals, d, rows, flags, scalar, sstride);
-  hipLaunchKernelGGL(column_class_kernel, dim3((cols + 255) / 256), dim3(256), 0, st, flags, scalar, sstride, rows.count, cols);
-}
-
-// ---- tables -------------------------------------------------------------------
-// tw[i] = root^i for i < count
-__global__ void powers_kernel(gl_t *out, gl_t root, uint32_t count) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < count) out[i] = gl_pow(root, i);
-}
-// scale[c][p] = (shift * wN^c)^(bitrev_d(p)) * mult
-__global__ void coset_scale_kernel(gl_t *out, gl_t shift, gl_t wN, uint32_t d, uint32_t cosets, gl_t mult) {
-  uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t c = blockIdx.y;
-  if (p >= (1u << d)) return;
-  gl_t base = gl_mul(shift, gl_pow(wN, c));
-  out[((size_t)c << d) + p] = gl_mul(gl_pow(base, bitrev32(p, d)), mult);
-}
-
-void fill_powers(hipStream_t st, gl_t *out, gl_t root, uint32_t count) {
-  if (!count) return;
-  hipLaunchKernelGGL(powers_kernel, dim3((count + 255) / 256), dim3(256), 0, st, out, root, count);
-}
-void fill_coset_scale(hipStream_t st, gl_t *out, gl_t shift, gl_t wN, uint32_t d, uint32_t cosets, gl_t mult) {
-  uint32_t n = 1u << d;
-  hipLaunchKernelGGL(coset_scale_kernel, dim3((n + 255) / 256, cosets), dim3(256), 0, st, out, shift, wN, d, cosets,
-                     mult);
-}
-
-// ---- self-test of the field primitives (stage-level test operator p2gpu_field_selftest) -------------------
-// a[i], b[i]: arbitrary u64.  Every carry-chain form of gl.hpp / mul_pow2 against the portable code, which is
-// what the host and the oracle run: bad[0] canon, [1] add, [2] sub, [3] reduce128, [4] mul, [5] mul_add,
-// [6] mul_pow2<1..95>, [7] Acc160, [8..13] the congruent-word (non-canonical) forms, [14..15] unused.
-__global__ void field_selftest_kernel(const uint64_t *a, const uint64_t *b, uint32_t n, unsigned long long *bad) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint64_t x = a[i], y = b[i];
-  const gl_t xc = gl_canon_c(x), yc = gl_canon_c(y);
-  if (gl_canon(x) != xc) atomicAdd(&bad[0], 1ULL);
-  if (gl_add(xc, yc) != gl_add_c(xc, yc)) atomicAdd(&bad[1], 1ULL);
-  if (gl_sub(xc, yc) != gl_sub_c(xc, yc)) atomicAdd(&bad[2], 1ULL);
-  if (gl_reduce128(x, y) != gl_reduce128_c(x, y)) atomicAdd(&bad[3], 1ULL);
-  const uint64_t plo = xc * yc, phi = __umul64hi(xc, yc);
-  const gl_t prod = gl_reduce128_c(plo, phi);
-  if (gl_mul(xc, yc) != prod) atomicAdd(&bad[4], 1ULL);
-  {
-    uint64_t lo = plo + xc, hi = phi + (lo < xc);
-    if (gl_mul_add(xc, yc, xc) != gl_reduce128_c(lo, hi)) atomicAdd(&bad[5], 1ULL);
-  }
-  gl_t pw = 1;
-  bool ok = true;
-  static_for<1, 96>([&](auto ec) {
-    constexpr int e = decltype(ec)::value;
-    pw = gl_add_c(pw, pw);
-    const uint64_t l = xc * pw, h = __umul64hi(xc, pw);
-    if (mul_pow2<e>(xc) != gl_reduce128_c(l, h)) ok = false;
-  });
-  if (!ok) atomicAdd(&bad[6], 1ULL);
-  {
-    Acc160 acc;
-    acc.clear();
-    acc.mac(xc, yc);
-    acc.mac(yc, yc);
-    acc.mac(xc, xc);
-    const uint64_t l2 = yc * yc, h2 = __umul64hi(yc, yc), l3 = xc * xc, h3 = __umul64hi(xc, xc);
-    const gl_t want = gl_add_c(gl_add_c(prod, gl_reduce128_c(l2, h2)), gl_reduce128_c(l3, h3));
-    if (acc.value() != want) atomicAdd(&bad[7], 1ULL);
-  }
-  // The congruent-word forms (gl.hpp, round 3): operands ANY u64 -- x, y are used raw, so the edge set's words in [p, 2^64)
-  // reach every branch -- result some u64 congruent to the canonical portable value.  [8] gl_mul_nc, [9] gl_mul_add_nc (one
-  // factor canonical: the product plus the addend stays below 2^128), [10] gl_reduce128_nc, [11] gl_add / [12] gl_sub with a
-  // non-canonical FIRST operand (a congruent word comes out; canonical when both operands are), [13] a chain: congruent words fed back into the congruent forms.
-  if (gl_canon(gl_mul_nc(x, y)) != prod) atomicAdd(&bad[8], 1ULL);
-  {
-    uint64_t lo = plo + xc, hi = phi + (lo < xc);
-    if (gl_canon(gl_mul_add_nc(x, yc, xc)) != gl_reduce128_c(lo, hi)) atomicAdd(&bad[9], 1ULL);
-  }
-  if (gl_canon(gl_reduce128_nc(x, y)) != gl_reduce128_c(x, y)) atomicAdd(&bad[10], 1ULL);
-  if (gl_canon(gl_add(x, yc)) != gl_add_c(xc, yc) || gl_add(xc, yc) != gl_add_c(xc, yc)) atomicAdd(&bad[11], 1ULL);
-  if (gl_canon(gl_sub(x, yc)) != gl_sub_c(xc, yc) || gl_sub(xc, yc) != gl_sub_c(xc, yc)) atomicAdd(&bad[12], 1ULL);
-  {
-    const uint64_t u = gl_mul_nc(x, y), v = gl_mul_add_nc(y, xc, yc);   // congruent to x y and y x + y
-    const uint64_t w = gl_mul_nc(u, v);
-    uint64_t l2 = plo + yc, h2 = phi + (l2 < yc);
-    const gl_t vv = gl_reduce128_c(l2, h2);
-    const uint64_t l3 = prod * vv, h3 = __umul64hi(prod, vv);
-    if (gl_canon(w) != gl_reduce128_c(l3, h3)) atomicAdd(&bad[13], 1ULL);
-    if (gl_canon(gl_add(w, xc)) != gl_add_c(gl_reduce128_c(l3, h3), xc)) atomicAdd(&bad[13], 1ULL);
-    if (gl_canon(gl_sub(w, xc)) != gl_sub_c(gl_reduce128_c(l3, h3), xc)) atomicAdd(&bad[13], 1ULL);
-  }
-}
-void field_selftest(hipStream_t st, const uint64_t *a, const uint64_t *b, uint32_t n, unsigned long long *bad) {
-  hipLaunchKernelGGL(field_selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, st, a, b, n, bad);
-}
-
-// bit-reversal permutation of columns (only for the stage-level test operators
-// that speak plonky2's natural-order coefficient convention)
-__global__ void bitrev_cols_kernel(const gl_t *in, gl_t *out, uint32_t d, uint32_t cols) {
-  uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t c = blockIdx.y;
-  if (p >= (1u << d)) return;
-  out[((size_t)c << d) + bitrev32(p, d)] = in[((size_t)c << d) + p];
-}
-void bitrev_cols(hipStream_t st, const gl_t *in, gl_t *out, uint32_t d, uint32_t cols) {
-  uint32_t n = 1u << d;
-  hipLaunchKernelGGL(bitrev_cols_kernel, dim3((n + 255) / 256, cols), dim3(256), 0, st, in, out, d, cols);
 }
 
 }  // namespace p2
