@@ -1,6 +1,6 @@
 // generators.hpp -- the gates' witness generators, one body each, shared by the two kernels that run them:
 //   fill_witness_kernel (witness.hip)  one lane per row, straight on the wire matrix;
-//   genwit_walk_kernel  (genwit.hip)   one lane per scheduled op, on the per-proof class values.
+//   genwit_walk_kernel  (genwit.hip)   one lane per scheduled op and witness of the batch, on that witness's class values.
 // A body sees its row through an accessor A:
 //   gl_t get(col)            the wire's value
 //   void set(col, gl_t v)    a derived wire (the level walk compares instead when the wire's class already has a value)

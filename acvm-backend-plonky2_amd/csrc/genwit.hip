@@ -16,6 +16,11 @@
 // compression circuit: 6 170 levels of median width 38 -- a chain, not a wave front), a wide kernel scatters the slot
 // values over the routed cells, fill_witness derives the rest.  The first contradiction, by op order, comes back in
 // one word after everything is queued.
+// Batch (p2gpu_generate_witness_batch): B witnesses of one plan through the SAME kernels.  Only the values are per
+// witness -- val[slot][B], seed_vals[seed][B], err[B], the witness index innermost -- and a lane of the walk takes the pair
+// (op, witness) with the witness as the fast index: neighbouring lanes run one generator on neighbouring words.  Groups of
+// WALK_GROUP witnesses get a workgroup each; a group shares nothing it writes with another, so nothing synchronises across
+// workgroups.  The lone call is the batch of one on the plan's own buffers.
 #include <chrono>
 #include <unordered_map>
 #include "generators.hpp"
@@ -28,6 +33,9 @@ namespace {
 constexpr uint32_t UNSET = 0xFFFFFFFFu;   // cell without a slot
 constexpr uint32_t WRITER = 0x80000000u;  // cell_slot bit: this cell's op writes the slot (every other one compares)
 constexpr uint32_t WALK_TPB = 512;
+// witnesses per workgroup of the walk; a power of two.  8 is the starting value (41 ops of the median SHA level x 8 = 328 of 512
+// lanes), NOT yet a measured choice: profiles/device_witness.md says how 4 / 8 / 16 are to be compared
+constexpr uint32_t WALK_GROUP = 8;
 enum : uint32_t {
   OP_SEED = 0, OP_CONSTANT, OP_ARITHMETIC, OP_BASE_SPLIT, OP_BASE_JOIN, OP_RA_COPY, OP_RA_CONSTS, OP_POSEIDON, OP_U32_ARITHMETIC,
   OP_U32_ADD_MANY, OP_U32_SUBTRACTION, OP_U32_RANGE_CHECK, OP_COMPARISON
@@ -40,49 +48,51 @@ struct WalkArgs {
   const uint32_t *level_off;  // [levels + 1]
   uint32_t levels;
   const uint32_t *cell_slot;  // [R][n]
-  gl_t *val;                  // [slots]
+  gl_t *val;                  // [slots][B]
   const uint2 *seed_cells;    // (row, col)
-  const gl_t *seed_vals;
+  const gl_t *seed_vals;      // [seeds][B]
   const uint8_t *row_gate;
   const GateDesc *gates;
   const gl_t *gconsts, *prc;
-  unsigned long long *err;    // smallest (op position << 8 | column) that contradicts
-  uint32_t d, R, ngc;
+  unsigned long long *err;    // [B]: per witness, the smallest (op position << 8 | column) that contradicts
+  uint32_t d, R, ngc, B;
 };
 
-// the row as the level walk sees it: slot values behind the routed cells
+// the row as the level walk sees it: witness b's slot values behind the routed cells
 struct RowSlots {
   const WalkArgs &a;
   size_t row;
   uint32_t pos;  // of the op in the schedule
+  uint32_t b;    // witness of the batch
+  __device__ __forceinline__ gl_t &slot(uint32_t s) const { return a.val[(size_t)s * a.B + b]; }
   __device__ __forceinline__ gl_t get(uint32_t col) const {
     if (col >= a.R) return 0;
     const uint32_t s = a.cell_slot[((size_t)col << a.d) + row];
-    return s == UNSET ? (gl_t)0 : a.val[s & ~WRITER];
+    return s == UNSET ? (gl_t)0 : slot(s & ~WRITER);
   }
   __device__ __forceinline__ void set(uint32_t col, gl_t v) {
     if (col >= a.R) return;  // gate-internal column: fill_witness derives it
     const uint32_t s = a.cell_slot[((size_t)col << a.d) + row];
     if (s == UNSET) return;
-    if (s & WRITER) a.val[s & ~WRITER] = v;
-    else if (a.val[s] != v) reject(col);
+    if (s & WRITER) slot(s & ~WRITER) = v;
+    else if (slot(s) != v) reject(col);
   }
   __device__ __forceinline__ gl_t lc(uint32_t i) const { return i < a.ngc ? a.gconsts[((size_t)i << a.d) + row] : (gl_t)0; }
-  __device__ __forceinline__ void reject(uint32_t col) { atomicMin(a.err, ((unsigned long long)pos << 8) | col); }
+  __device__ __forceinline__ void reject(uint32_t col) { atomicMin(a.err + b, ((unsigned long long)pos << 8) | col); }
 };
 
-__device__ __forceinline__ void run_op(const WalkArgs &a, uint32_t pos) {
+__device__ __forceinline__ void run_op(const WalkArgs &a, uint32_t pos, uint32_t b) {
   const OpRec op = a.ops[pos];
   const uint32_t code = op.y & 0xFF, sub = op.y >> 8;
   if (code == OP_SEED) {
     const uint2 cell = a.seed_cells[op.x];
-    const gl_t v = a.seed_vals[op.x];
-    RowSlots w{a, cell.x, pos};
+    const gl_t v = a.seed_vals[(size_t)op.x * a.B + b];
+    RowSlots w{a, cell.x, pos, b};
     if (v >= GL_P) w.reject(cell.y);
     else w.set(cell.y, v);
     return;
   }
-  RowSlots w{a, op.x, pos};
+  RowSlots w{a, op.x, pos, b};
   const GateDesc g = a.gates[a.row_gate[op.x]];
   switch (code) {
   case OP_CONSTANT: gen_constant(w, g); break;
@@ -101,33 +111,45 @@ __device__ __forceinline__ void run_op(const WalkArgs &a, uint32_t pos) {
   }
 }
 
-// ONE workgroup: the waves of a workgroup share their CU's vector cache, so what a level stored is what the next level
-// loads after the barrier; the rest of the device stays free for the proofs in flight.
+// ONE workgroup per group of WALK_GROUP witnesses (the last group may hold fewer): the waves of a workgroup share their CU's
+// vector cache, so what a level stored is what the next level loads after the barrier, and a group reads and writes its own
+// witnesses' words only; the rest of the device stays free for the proofs in flight.  With 1 << sh the group's width rounded
+// up to a power of two, lane t takes witness t & mask of the group and the level's ops t >> sh, + 512 >> sh, ... (the lone
+// call: sh = 0, a lane per op).
 __global__ __launch_bounds__(WALK_TPB) void genwit_walk_kernel(WalkArgs a) {
+  const uint32_t b0 = blockIdx.x * WALK_GROUP, gw = min(WALK_GROUP, a.B - b0);
+  const uint32_t sh = gw > 1 ? 32 - __clz(gw - 1) : 0, lb = threadIdx.x & ((1u << sh) - 1);
+  const uint32_t first = threadIdx.x >> sh, step = WALK_TPB >> sh;
   for (uint32_t l = 0; l < a.levels; l++) {
     const uint32_t end = a.level_off[l + 1];
-    for (uint32_t pos = a.level_off[l] + threadIdx.x; pos < end; pos += WALK_TPB) run_op(a, pos);
+    if (lb < gw)
+      for (uint32_t pos = a.level_off[l] + first; pos < end; pos += step) run_op(a, pos, b0 + lb);
     __syncthreads();
   }
 }
 
-// wires[col][row] = the slot's value, zero for a cell without one
-__global__ __launch_bounds__(256) void genwit_scatter_kernel(const uint32_t *cell_slot, const gl_t *val, size_t cells, gl_t *wires) {
+// wires[b][col][row] = witness b's value of the slot, zero for a cell without one and for the gate-internal columns
+// (cells <= i < matrix); cell_slot is read once for the whole batch.  A lane keeps its cell and loops over b: the stores of a
+// wave are 64 consecutive words of one matrix, and a lane's loads are the B consecutive words of its slot (whole cache lines
+// from B = 16 on) -- a lane per (cell, b) would coalesce the loads and scatter every store over B matrices instead.
+__global__ __launch_bounds__(256) void genwit_scatter_kernel(const uint32_t *cell_slot, const gl_t *val, size_t cells, size_t matrix,
+                                                             uint32_t B, gl_t *wires) {
   const size_t step = (size_t)gridDim.x * 256;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < cells; i += step) {
-    const uint32_t s = cell_slot[i];
-    wires[i] = s == UNSET ? (gl_t)0 : val[s & ~WRITER];
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < matrix; i += step) {
+    const uint32_t s = i < cells ? cell_slot[i] : UNSET;
+    const gl_t *v = s == UNSET ? nullptr : val + (size_t)(s & ~WRITER) * B;
+    for (uint32_t b = 0; b < B; b++) wires[b * matrix + i] = v ? v[b] : (gl_t)0;
   }
 }
 
 // the seeds no slot carries: pi_rows = 0: those on gate-internal columns; 1: those in PublicInputGate rows, whose wires are
-// the caller's whatever ran in between
-__global__ void genwit_seed_write_kernel(const uint2 *cells, const gl_t *vals, uint32_t count, uint32_t R, uint32_t d, int pi_rows,
-                                         const uint8_t *row_gate, const GateDesc *gates, gl_t *wires) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
-  const uint2 c = cells[i];
-  if (pi_rows ? gates[row_gate[c.x]].kind == G_PUBLIC_INPUT : c.y >= R) wires[((size_t)c.y << d) + c.x] = vals[i];
+// the caller's whatever ran in between.  A lane per (seed, witness), the witness the fast index as in vals.
+__global__ void genwit_seed_write_kernel(const uint2 *cells, const gl_t *vals, uint32_t count, uint32_t B, uint32_t R, uint32_t d,
+                                         int pi_rows, const uint8_t *row_gate, const GateDesc *gates, size_t matrix, gl_t *wires) {
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= (size_t)count * B) return;
+  const uint2 c = cells[k / B];
+  if (pi_rows ? gates[row_gate[c.x]].kind == G_PUBLIC_INPUT : c.y >= R) wires[(k % B) * matrix + ((size_t)c.y << d) + c.x] = vals[k];
 }
 
 // ---- plan compilation (host) ----
@@ -156,9 +178,26 @@ struct p2gpu_witness_plan {
   std::vector<uint2> h_seed_cells;
   DBuf<unsigned long long> err;
   uint64_t *pin = nullptr;  // page-locked: [n_seeds] staging of the seed values, then the contradiction word
+  // the same four for p2gpu_generate_witness_batch, sized for batch_cap witnesses by the first call that needs them
+  struct Values {
+    gl_t *val, *seed_vals;
+    unsigned long long *err;
+    uint64_t *pin;
+  };
+  size_t batch_cap = 0;
+  DBuf<gl_t> bval, bseed_vals;
+  DBuf<unsigned long long> berr;
+  uint64_t *bpin = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  void release_batch() {
+    bval.release(); bseed_vals.release(); berr.release();
+    if (bpin) (void)hipHostFree(bpin);
+    bpin = nullptr;
+    batch_cap = 0;
+  }
   void release() {
     ops.release(); level_off.release(); cell_slot.release(); val.release(); seed_vals.release(); seed_cells.release(); err.release();
+    release_batch();
     if (pin) (void)hipHostFree(pin);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
@@ -468,61 +507,111 @@ int plan_compile(p2gpu_witness_plan *p, const uint32_t *seed_cells, size_t n_see
   return P2GPU_OK;
 }
 
-// everything of one witness on the handle's stream; returns after the contradiction word has arrived
-int generate(p2gpu_witness_plan *p, const uint64_t *seed_values, gl_t *wires) {
+// the batched buffers, grown to hold `batch` witnesses (the stream is idle between calls: one call at a time per handle).
+// batch_cap is a capacity in witnesses: a call lays its values out with its own B as the stride, in the front of the buffers.
+// Nothing is cleared: every slot has a writer (plan_compile refuses a plan with an unreached one) and is written before it is read.
+int reserve_batch(p2gpu_witness_plan *p, size_t batch) {
+  if (batch <= p->batch_cap) return P2GPU_OK;
+  p->release_batch();
+  HIP_TRY(p->bval.alloc(batch * std::max<uint32_t>(1, p->slots)));
+  HIP_TRY(p->bseed_vals.alloc(batch * std::max<uint32_t>(1, p->n_seeds)));
+  HIP_TRY(p->berr.alloc(batch));
+  HIP_TRY(hipHostMalloc((void **)&p->bpin, 8 * batch * ((size_t)p->n_seeds + 1), hipHostMallocDefault));
+  p->batch_cap = batch;
+  return P2GPU_OK;
+}
+
+// everything of B witnesses on the handle's stream: v.pin holds the seed values [n_seeds][B] on entry and, from
+// v.pin + n_seeds * B on, the B contradiction words when this returns.  wires: [B][num_wires][n]
+int walk_and_scatter(p2gpu_witness_plan *p, const p2gpu_witness_plan::Values &v, uint32_t B, gl_t *wires) {
   p2gpu_circuit *c = p->c;
   hipStream_t st = c->stream;
   const uint32_t ngc = c->NC - c->num_selectors;
-  HIP_TRY(hipSetDevice(c->device));
-  if (p->n_seeds) {
-    memcpy(p->pin, seed_values, 8 * (size_t)p->n_seeds);
-    HIP_TRY(hipMemcpyAsync(p->seed_vals.p, p->pin, 8 * (size_t)p->n_seeds, hipMemcpyHostToDevice, st));
-  }
-  HIP_TRY(hipMemsetAsync(p->err.p, 0xFF, 8, st));
+  const size_t n_vals = (size_t)p->n_seeds * B;
+  if (n_vals) HIP_TRY(hipMemcpyAsync(v.seed_vals, v.pin, 8 * n_vals, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(v.err, 0xFF, 8 * (size_t)B, st));
   WalkArgs a;
-  a.ops = p->ops.p; a.level_off = p->level_off.p; a.levels = p->levels; a.cell_slot = p->cell_slot.p; a.val = p->val.p;
-  a.seed_cells = p->seed_cells.p; a.seed_vals = p->seed_vals.p; a.row_gate = c->d_row_gate.p; a.gates = c->d_gates.p;
-  a.gconsts = c->d_gconsts.p; a.prc = c->d_prc.p; a.err = p->err.p; a.d = c->d; a.R = c->R; a.ngc = ngc;
+  a.ops = p->ops.p; a.level_off = p->level_off.p; a.levels = p->levels; a.cell_slot = p->cell_slot.p; a.val = v.val;
+  a.seed_cells = p->seed_cells.p; a.seed_vals = v.seed_vals; a.row_gate = c->d_row_gate.p; a.gates = c->d_gates.p;
+  a.gconsts = c->d_gconsts.p; a.prc = c->d_prc.p; a.err = v.err; a.d = c->d; a.R = c->R; a.ngc = ngc; a.B = B;
   HIP_TRY(hipEventRecord(p->ev0, st));
   {
-    ProfScope ps("genwit_walk_kernel", 16.0 * (double)p->n_ops);
-    hipLaunchKernelGGL(genwit_walk_kernel, dim3(1), dim3(WALK_TPB), 0, st, a);
+    ProfScope ps("genwit_walk_kernel", 16.0 * (double)p->n_ops * B);
+    hipLaunchKernelGGL(genwit_walk_kernel, dim3((B + WALK_GROUP - 1) / WALK_GROUP), dim3(WALK_TPB), 0, st, a);
   }
   HIP_TRY(hipEventRecord(p->ev1, st));
-  const size_t cells = (size_t)c->R * c->n;
+  const size_t cells = (size_t)c->R * c->n, matrix = (size_t)c->W * c->n;
   {
-    ProfScope ps("genwit_scatter_kernel", 12.0 * (double)cells);
-    hipLaunchKernelGGL(genwit_scatter_kernel, dim3((unsigned)std::min<size_t>((cells + 255) / 256, 1 << 16)), dim3(256), 0, st,
-                       p->cell_slot.p, p->val.p, cells, wires);
+    ProfScope ps("genwit_scatter_kernel", 4.0 * (double)cells + 8.0 * (double)(cells + matrix) * B);
+    hipLaunchKernelGGL(genwit_scatter_kernel, dim3((unsigned)std::min<size_t>((matrix + 255) / 256, 1 << 16)), dim3(256), 0, st,
+                       p->cell_slot.p, v.val, cells, matrix, B, wires);
   }
-  HIP_TRY(hipMemsetAsync(wires + cells, 0, 8 * (size_t)(c->W - c->R) * c->n, st));
-  const dim3 sg((p->n_seeds + 255) / 256);
-  if (p->n_seeds)
-    hipLaunchKernelGGL(genwit_seed_write_kernel, sg, dim3(256), 0, st, p->seed_cells.p, p->seed_vals.p, p->n_seeds, c->R, c->d, 0,
-                       c->d_row_gate.p, c->d_gates.p, wires);
-  fill_witness(st, wires, c->d_row_gate.p, c->d_gates.p, c->d_gconsts.p, c->d_prc.p, c->d, ngc, c->W);
-  if (p->n_seeds)
-    hipLaunchKernelGGL(genwit_seed_write_kernel, sg, dim3(256), 0, st, p->seed_cells.p, p->seed_vals.p, p->n_seeds, c->R, c->d, 1,
-                       c->d_row_gate.p, c->d_gates.p, wires);
-  HIP_TRY(hipMemcpyAsync(p->pin + p->n_seeds, p->err.p, 8, hipMemcpyDeviceToHost, st));
+  const dim3 sg((unsigned)((n_vals + 255) / 256));
+  if (n_vals)
+    hipLaunchKernelGGL(genwit_seed_write_kernel, sg, dim3(256), 0, st, p->seed_cells.p, v.seed_vals, p->n_seeds, B, c->R, c->d, 0,
+                       c->d_row_gate.p, c->d_gates.p, matrix, wires);
+  for (uint32_t b = 0; b < B; b++)
+    fill_witness(st, wires + b * matrix, c->d_row_gate.p, c->d_gates.p, c->d_gconsts.p, c->d_prc.p, c->d, ngc, c->W);
+  if (n_vals)
+    hipLaunchKernelGGL(genwit_seed_write_kernel, sg, dim3(256), 0, st, p->seed_cells.p, v.seed_vals, p->n_seeds, B, c->R, c->d, 1,
+                       c->d_row_gate.p, c->d_gates.p, matrix, wires);
+  HIP_TRY(hipMemcpyAsync(v.pin + n_vals, v.err, 8 * (size_t)B, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());
   float ms = 0;
   if (hipEventElapsedTime(&ms, p->ev0, p->ev1) == hipSuccess) p->walk_ms = ms;
-  const uint64_t e = p->pin[p->n_seeds];
-  if (e != UINT64_MAX) {
-    const size_t pos = (size_t)(e >> 8);
-    const uint32_t col = (uint32_t)(e & 0xFF);
-    if (pos >= p->h_ops.size()) { set_err("p2gpu_generate_witness: internal error (contradiction word)"); return P2GPU_E_DEVICE; }
-    const OpRec op = p->h_ops[pos];
-    if ((op.y & 0xFF) == OP_SEED)
-      set_err("seed %u for cell (row %u, column %u) %s", op.x, p->h_seed_cells[op.x].x, col,
-              seed_values[op.x] >= GL_P ? "is not a canonical field element" : "contradicts the value its copy class already has");
-    else
-      set_err("unsatisfiable: the generator of row %u contradicts the value cell (row %u, column %u) already has", op.x, op.x, col);
-    return P2GPU_E_UNSATISFIED;
-  }
   return P2GPU_OK;
+}
+
+// a contradiction word as (row, col) and as p2gpu_last_error's text behind `who`; seed_values: that witness's, [n_seeds]
+int name_contradiction(const p2gpu_witness_plan *p, uint64_t e, const uint64_t *seed_values, const char *who, uint32_t cell[2]) {
+  const size_t pos = (size_t)(e >> 8);
+  const uint32_t col = (uint32_t)(e & 0xFF);
+  if (pos >= p->h_ops.size()) { set_err("p2gpu_generate_witness: internal error (contradiction word)"); return P2GPU_E_DEVICE; }
+  const OpRec op = p->h_ops[pos];
+  const bool seed = (op.y & 0xFF) == OP_SEED;
+  cell[0] = seed ? p->h_seed_cells[op.x].x : op.x;
+  cell[1] = col;
+  if (seed)
+    set_err("%sseed %u for cell (row %u, column %u) %s", who, op.x, cell[0], col,
+            seed_values[op.x] >= GL_P ? "is not a canonical field element" : "contradicts the value its copy class already has");
+  else
+    set_err("%sunsatisfiable: the generator of row %u contradicts the value cell (row %u, column %u) already has", who, op.x, op.x, col);
+  return P2GPU_E_UNSATISFIED;
+}
+
+// one witness: the batch of one on the plan's own buffers; returns after the contradiction word has arrived
+int generate(p2gpu_witness_plan *p, const uint64_t *seed_values, gl_t *wires) {
+  HIP_TRY(hipSetDevice(p->c->device));
+  if (p->n_seeds) memcpy(p->pin, seed_values, 8 * (size_t)p->n_seeds);
+  if (int rc = walk_and_scatter(p, {p->val.p, p->seed_vals.p, p->err.p, p->pin}, 1, wires)) return rc;
+  const uint64_t e = p->pin[p->n_seeds];
+  uint32_t cell[2];
+  return e == UINT64_MAX ? P2GPU_OK : name_contradiction(p, e, seed_values, "", cell);
+}
+
+// seed_values: [batch][n_seeds]; status: [batch]; bad_cells: [batch][2] or null
+int generate_batch(p2gpu_witness_plan *p, const uint64_t *seed_values, size_t batch, gl_t *wires, int *status, uint32_t *bad_cells) {
+  HIP_TRY(hipSetDevice(p->c->device));
+  if (int rc = reserve_batch(p, batch)) return rc;
+  const uint32_t B = (uint32_t)batch, S = p->n_seeds;
+  for (uint32_t b = 0; b < B; b++)
+    for (uint32_t i = 0; i < S; i++) p->bpin[(size_t)i * B + b] = seed_values[(size_t)b * S + i];
+  if (int rc = walk_and_scatter(p, {p->bval.p, p->bseed_vals.p, p->berr.p, p->bpin}, B, wires)) return rc;
+  int rc = P2GPU_OK;
+  for (uint32_t b = B; b-- > 0;) {  // downwards: p2gpu_last_error keeps the lowest failing witness
+    const uint64_t e = p->bpin[(size_t)S * B + b];
+    uint32_t cell[2] = {UINT32_MAX, UINT32_MAX};
+    status[b] = P2GPU_OK;
+    if (e != UINT64_MAX) {
+      char who[48];
+      snprintf(who, sizeof who, "witness %u of the batch: ", b);
+      status[b] = name_contradiction(p, e, seed_values + (size_t)b * S, who, cell);
+      if (status[b] != P2GPU_E_UNSATISFIED || rc == P2GPU_OK) rc = status[b];  // (an internal error, once seen, is what returns)
+    }
+    if (bad_cells) bad_cells[2 * b] = cell[0], bad_cells[2 * b + 1] = cell[1];
+  }
+  return rc;
 }
 
 }  // namespace
@@ -580,6 +669,14 @@ int p2gpu_generate_witness(p2gpu_witness_plan *p, const uint64_t *seed_values, u
   if (!p || !wires_dev_out || (p->n_seeds && !seed_values)) return P2GPU_E_ARG;
   ProfGuard pg(p->c);
   return generate(p, seed_values, wires_dev_out);
+} P2GPU_CATCH
+
+int p2gpu_generate_witness_batch(p2gpu_witness_plan *p, const uint64_t *seed_values, size_t batch, uint64_t *wires_dev_out, int *status,
+                                 uint32_t *bad_cells) try {
+  if (!p || !wires_dev_out || !status || batch == 0 || (p->n_seeds && !seed_values)) return P2GPU_E_ARG;
+  if (batch >= ((size_t)1 << 32) / std::max<uint32_t>(1, p->n_seeds)) return P2GPU_E_ARG;  // (the seed-write kernel's grid)
+  ProfGuard pg(p->c);
+  return generate_batch(p, seed_values, batch, wires_dev_out, status, bad_cells);
 } P2GPU_CATCH
 
 int p2gpu_prove_seeds(p2gpu_witness_plan *p, const uint64_t *seed_values, const uint64_t *pis, uint32_t n_pi, uint8_t *proof_out,

@@ -97,6 +97,7 @@ def load_library():
     lib.p2gpu_witness_plan_destroy.restype = None
     lib.p2gpu_witness_plan_info.argtypes = [vp, vp, vp]
     lib.p2gpu_generate_witness.argtypes = [vp, vp, vp]
+    lib.p2gpu_generate_witness_batch.argtypes = [vp, vp, sz, vp, vp, vp]
     lib.p2gpu_prove_seeds.argtypes = [vp, vp, vp, ctypes.c_uint32, u8p, ctypes.POINTER(sz), ctypes.POINTER(_Timings)]
     lib.p2gpu_verify.argtypes = [vp, u8p, sz]
     lib.p2gpu_circuit_export_vk.argtypes = [vp, u8p, ctypes.POINTER(sz)]
@@ -540,6 +541,42 @@ class WitnessPlan:
         cd = self._cd
         out = torch.empty((cd.num_wires, cd.degree), dtype=torch.int64, device=f"cuda:{cd.device_index()}")
         _check(self._lib.p2gpu_generate_witness(self._h, v.ctypes.data if v.size else None, ctypes.c_void_p(out.data_ptr())))
+        return out
+
+    def generate_batch(self, values_list):
+        """``p2gpu_generate_witness_batch``: one level walk for all of `values_list`.  Returns (the wire matrices
+        [B][num_wires][degree] as an int64 tensor on the circuit's GPU, the status per member: 0 or -5, the (row, col) of a
+        failing member's first contradiction or None).  A failing member does not raise; the others' matrices are complete."""
+        import torch
+
+        rows = [self._values(v) for v in values_list]
+        if not rows:
+            raise P2GpuError(-7, "generate_batch needs at least one set of values")
+        v = np.ascontiguousarray(np.stack(rows))
+        cd = self._cd
+        out = torch.empty((len(rows), cd.num_wires, cd.degree), dtype=torch.int64, device=f"cuda:{cd.device_index()}")
+        status = np.zeros(len(rows), dtype=np.intc)
+        bad = np.zeros((len(rows), 2), dtype=np.uint32)
+        rc = self._lib.p2gpu_generate_witness_batch(self._h, v.ctypes.data if v.size else None, len(rows), ctypes.c_void_p(out.data_ptr()),
+                                                    status.ctypes.data, bad.ctypes.data)
+        if rc != -5:
+            _check(rc)
+        return out, [int(s) for s in status], [(int(r), int(c)) if s else None for s, (r, c) in zip(status, bad)]
+
+    def prove_batch(self, values_list, public_inputs=None):
+        """`generate_batch`, then the resident proof (``CircuitData.prove`` on the member's matrix) of every good member, in
+        order.  `public_inputs`: one list per member.  Returns per member the ``ProofWithPublicInputs``, or the ``P2GpuError``
+        a lone ``prove`` would have raised."""
+        wires, status, bad = self.generate_batch(values_list)
+        out = []
+        for b, st in enumerate(status):
+            if st:
+                out.append(P2GpuError(st, "unsatisfiable: witness %d of the batch contradicts itself at cell (row %d, column %d)" % (b, *bad[b])))
+                continue
+            try:
+                out.append(self._cd.prove(wires[b], public_inputs[b] if public_inputs is not None else ()))
+            except P2GpuError as e:
+                out.append(e)
         return out
 
     def prove(self, values, public_inputs=()):

@@ -20,6 +20,9 @@
  *   p2gpu_witness_plan_create / p2gpu_generate_witness / p2gpu_prove_seeds
  *                          <- all of `generate_partial_witness` (plonky2 iop/generator.rs, called by `prove`): the caller
  *                             hands over the `pw.set_target` values only, generators and copy constraints run on the GPU
+ *   p2gpu_generate_witness_batch
+ *                          <- the same for many value sets of one circuit at once (the reference has no counterpart: it
+ *                             calls `prove` once per witness)
  *   p2gpu_last_error       <- the `anyhow::Error` text the reference unwraps
  *   p2gpu_ifft_batch / p2gpu_lde_batch / p2gpu_commit_values
  *                          <- plonky2 PolynomialValues::ifft,
@@ -175,13 +178,27 @@ typedef struct p2gpu_witness_plan p2gpu_witness_plan;
 int p2gpu_witness_plan_create(p2gpu_circuit *c, const uint32_t *seed_cells /* [n_seeds][2] = (row, col) */, size_t n_seeds,
                               p2gpu_witness_plan **out);
 void p2gpu_witness_plan_destroy(p2gpu_witness_plan *p);
-/* counts: ops, levels, widest level, value slots, seeds; ms: plan compilation (host), level walk of the last witness (device) */
+/* counts: ops, levels, widest level, value slots, seeds; ms: plan compilation (host), level walk of the last call (device) */
 int p2gpu_witness_plan_info(const p2gpu_witness_plan *p, uint64_t counts[5], double ms[2]);
 /* seed_values: host, [n_seeds] in the plan's order.  wires_dev_out: device, [num_wires][n], written completely.  One workgroup
  * walks the levels, a kernel copies the class values to the routed cells, p2gpu_fill_witness's kernel derives the rest.  A
  * generator whose output already has another value, or a seed >= p: P2GPU_E_UNSATISFIED, the first offender's cell in
  * p2gpu_last_error (the matrix is then not a witness). */
 int p2gpu_generate_witness(p2gpu_witness_plan *p, const uint64_t *seed_values, uint64_t *wires_dev_out);
+/* `batch` witnesses of one plan in one level walk: the lanes of a level take (op, witness) pairs, and groups of witnesses
+ * (WALK_GROUP in csrc/genwit.hip) get a workgroup each; the cost per witness is not measured yet.  seed_values: host,
+ * [batch][n_seeds].  wires_dev_out: device, [batch][num_wires][n], written completely.  status: host, [batch], P2GPU_OK or
+ * P2GPU_E_UNSATISFIED per witness; bad_cells: host, [batch][2] = (row, col) of a failing witness's first contradiction,
+ * UINT32_MAX twice for a good one; may be NULL.  Witnesses do not affect each other: every matrix whose status is P2GPU_OK is
+ * the complete witness a lone call gives.  Returns P2GPU_OK when every witness is good, P2GPU_E_UNSATISFIED when one is not
+ * (p2gpu_last_error: "witness <b> of the batch: " and the lone call's words for the lowest failing b), P2GPU_E_ARG for a null
+ * plan, output or status, batch == 0, or null values for a plan with seeds.  The plan's buffers for a batch are allocated by the
+ * first call that needs them and grow with the largest batch seen; p2gpu_witness_plan_destroy frees them.  ms[1] of
+ * p2gpu_witness_plan_info is the walk of the last call, lone or batched. */
+int p2gpu_generate_witness_batch(p2gpu_witness_plan *p, const uint64_t *seed_values /* host, [batch][n_seeds] */, size_t batch,
+                                 uint64_t *wires_dev_out /* device, [batch][num_wires][n] */,
+                                 int *status /* host, [batch]: P2GPU_OK or P2GPU_E_UNSATISFIED */,
+                                 uint32_t *bad_cells /* host, [batch][2] = (row, col) of the first contradiction, may be NULL */);
 /* p2gpu_generate_witness into the handle's own buffer, then p2gpu_prove_dev on it: the same proof bytes.  h2d_ms of the timings
  * holds the time the witness took. */
 int p2gpu_prove_seeds(p2gpu_witness_plan *p, const uint64_t *seed_values, const uint64_t *public_inputs, uint32_t n_pi,
