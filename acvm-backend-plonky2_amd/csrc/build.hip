@@ -4,32 +4,39 @@
 // The host counterpart is p2gpu_build_blob (hostcore.hip); both give the same bytes (tests/test_gpu_device_build.py).
 //
 // Sigma: cells are numbered in the reference's listing order, key = row * R + col.
-//   1. touch     every cell named by a copy pair becomes its own class (parent[key] = key; untouched cells stay UNSET)
-//                and is appended once to the list of touched cells;
-//   2. classes   rounds of { hook: for every pair whose ends point at different cells, atomicMin(parent[larger], smaller);
-//                jump: parent[x] <- parent[parent[...]] until every touched cell points at a root } until no pair hooks.
-//                Parents only ever decrease and only within a true class, so the fixed point is parent[x] = the smallest
-//                key of x's class whatever order the atomics land in.  No thread ever waits for another one or retries.
+//   1. touch     every cell named by a copy pair becomes its own class and is appended once to the list of touched cells;
+//   2. classes   rounds of hook / jump until no pair hooks: parent[x] = the smallest key of x's class (devclasses.hpp, the
+//                union-find the device plan compiler shares);
 //   3. cycles    sort the touched cells by (root, key); the successor of a cell is the next entry of its segment, the last
 //                entry's successor is the root (= the segment's first entry);
 //   4. values    sigma[col * n + row] = k_is[col'] * w^row', the identity for cells no pair names.
 #include <cstring>  // (rocprim's headers use memcpy without including it)
 #include <rocprim/rocprim.hpp>
+#include "devclasses.hpp"
 #include "prover_internal.hpp"
 
 using namespace p2;
 
 namespace {
 
-constexpr uint32_t UNSET = 0xFFFFFFFFu;  // no cell's key
+using classes::UNSET;
+using classes::TPB;
+using classes::grid_for;
+using classes::subgroup_power;
 // keys are < R * n <= MAX_ROUTED * 2^24 (circuit_parse: d <= 24): below UNSET, and (root, key) fits one 64-bit sort key
 static_assert(((uint64_t)MAX_ROUTED << 24) <= ((uint64_t)1 << 31), "cell keys must stay below UNSET and 2 * key_bits below 64");
-// parent[] is read while other threads of the same launch lower it: one 32-bit load, exactly once, never re-read
-__device__ __forceinline__ uint32_t ld_parent(const uint32_t *p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
-constexpr uint32_t TPB = 256;
-constexpr int JUMP_STEPS = 32;  // parent look-ups of one thread in one jump launch
 
-inline uint32_t grid_for(size_t count) { return (uint32_t)std::min<size_t>(std::max<size_t>(1, (count + TPB - 1) / TPB), (size_t)1 << 16); }
+// the caller's copy pairs as devclasses.hpp's pair source: cells in the reference's listing order, key = row * R + col
+struct CopyPairs {
+  const uint4 *copies;
+  uint32_t R;
+  __device__ __forceinline__ bool get(size_t i, uint32_t &a, uint32_t &b) const {
+    const uint4 e = copies[i];
+    a = e.x * R + e.y;
+    b = e.z * R + e.w;
+    return true;
+  }
+};
 
 // bad[0..2] = the smallest offending index of row_gate / the gate constants / the copy pairs (UINT64_MAX: none).  The only
 // kernel that reads the caller's arrays unchecked, and it indexes nothing with them.
@@ -80,60 +87,6 @@ __global__ void build_selectors_kernel(const uint8_t *row_gate, const GateDesc *
   }
 }
 
-__device__ __forceinline__ void touch_cell(uint32_t x, uint32_t *parent, unsigned long long *list, unsigned long long *count) {
-  // the plain load is a filter only (a hub cell named by thousands of pairs costs one atomic per wave that still sees it
-  // untouched, not one per pair); the compare-and-swap decides who appends the cell
-  if (ld_parent(parent + x) != UNSET) return;
-  if (atomicCAS(&parent[x], UNSET, x) == UNSET) list[atomicAdd(count, 1ull)] = x;
-}
-__global__ void build_touch_kernel(const uint4 *copies, size_t num_copies, uint32_t R, uint32_t *parent, unsigned long long *list,
-                                   unsigned long long *count) {
-  const size_t step = (size_t)gridDim.x * TPB;
-  for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < num_copies; i += step) {
-    const uint4 e = copies[i];
-    const uint32_t a = e.x * R + e.y, b = e.z * R + e.w;
-    touch_cell(a, parent, list, count);
-    if (b != a) touch_cell(b, parent, list, count);
-  }
-}
-
-// Before the first launch parent is the identity on the touched cells, before every later one each touched cell points at a
-// root.  A value read here may already have been lowered by another thread of the same launch: it is then still a cell of
-// the same class, which is all the atomicMin needs.  A pair whose link lost against a smaller one hooks again next round.
-__global__ void build_hook_kernel(const uint4 *copies, size_t num_copies, uint32_t R, uint32_t *parent, uint32_t *changed) {
-  const size_t step = (size_t)gridDim.x * TPB;
-  bool any = false;
-  for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < num_copies; i += step) {
-    const uint4 e = copies[i];
-    const uint32_t a = e.x * R + e.y, b = e.z * R + e.w;
-    const uint32_t pa = ld_parent(parent + a), pb = ld_parent(parent + b);
-    if (pa == pb) continue;
-    any = true;
-    const uint32_t hi = max(pa, pb), lo = min(pa, pb);
-    if (ld_parent(parent + hi) > lo) atomicMin(&parent[hi], lo);  // (filter: a star's hub takes one atomic per improvement, not per pair)
-  }
-  if (any) *changed = 1;
-}
-
-// parent[x] <- an ancestor up to JUMP_STEPS links higher.  Stores go to the thread's own cell, values read are ancestors
-// whenever they were written, roots do not change during the launch.
-__global__ void build_jump_kernel(const unsigned long long *list, size_t count, uint32_t *parent, uint32_t *changed) {
-  const size_t step = (size_t)gridDim.x * TPB;
-  bool any = false;
-  for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < count; i += step) {
-    const uint32_t x = (uint32_t)list[i];
-    const uint32_t p0 = ld_parent(parent + x);
-    uint32_t p = p0, g = ld_parent(parent + p);
-    for (int k = 0; k < JUMP_STEPS && g != p; k++) {
-      p = g;
-      g = ld_parent(parent + p);
-    }
-    if (g != p) any = true;
-    if (p != p0) __atomic_store_n(parent + x, p, __ATOMIC_RELAXED);
-  }
-  if (any) *changed = 1;
-}
-
 // list[i] = root << key_bits | key
 __global__ void build_sort_keys_kernel(unsigned long long *list, size_t count, const uint32_t *parent, uint32_t key_bits) {
   const size_t step = (size_t)gridDim.x * TPB;
@@ -141,13 +94,6 @@ __global__ void build_sort_keys_kernel(unsigned long long *list, size_t count, c
     const uint32_t x = (uint32_t)list[i];
     list[i] = ((unsigned long long)parent[x] << key_bits) | x;
   }
-}
-
-// w^row from the forward twiddles tw[i] = w^i, i < n / 2:  w^(i + n/2) = -w^i
-__device__ __forceinline__ gl_t subgroup_power(const gl_t *tw, uint32_t d, uint32_t row) {
-  const uint32_t half = 1u << (d - 1);
-  const gl_t v = tw[row & (half - 1)];
-  return row & half ? gl_sub(0, v) : v;
 }
 
 // the identity permutation: sigma[col][row] = k_is[col] * w^row, eight columns per thread
@@ -177,24 +123,7 @@ __global__ void build_sigma_cycles_kernel(const unsigned long long *sorted, size
   }
 }
 
-// the scratch of one build: everything is released when it goes out of scope
-struct BuildScratch {
-  std::vector<void *> ptrs;
-  ~BuildScratch() { release(); }
-  void release() {
-    for (void *p : ptrs) (void)hipFree(p);
-    ptrs.clear();
-  }
-  template <class T> T *alloc(size_t n) {
-    void *p = nullptr;
-    if (hipMalloc(&p, (n ? n : 1) * sizeof(T)) != hipSuccess) {
-      (void)hipGetLastError();
-      return nullptr;
-    }
-    ptrs.push_back(p);
-    return (T *)p;
-  }
-};
+using BuildScratch = classes::Scratch;
 
 }  // namespace
 
@@ -274,7 +203,7 @@ int build_device_tables(p2gpu_circuit *c, const BuildInputs &in, const CreateTra
     unsigned long long *list = S.alloc<unsigned long long>(list_cap);
     if (!parent || !list) return dev_fail("scratch (parents, touched cells)", hipErrorOutOfMemory);
     BT(hipMemsetAsync(parent, 0xFF, 4 * tot, st), "scratch");
-    hipLaunchKernelGGL(build_touch_kernel, dim3(grid_for(E)), dim3(TPB), 0, st, copies, E, R, parent, list, words + 3);
+    hipLaunchKernelGGL(classes::touch_kernel<CopyPairs>, dim3(grid_for(E)), dim3(TPB), 0, st, CopyPairs{copies, R}, E, parent, list, words + 3);
     BT(hipMemcpyAsync(h + 3, words + 3, 8, hipMemcpyDeviceToHost, st), "read touched count");
     BT(hipStreamSynchronize(st), "touch");
     T = (size_t)h[3];
@@ -286,14 +215,14 @@ int build_device_tables(p2gpu_circuit *c, const BuildInputs &in, const CreateTra
     for (int round = 0;; round++) {
       if (round > (1 << 16)) { set_err("p2gpu_circuit_build: internal error (classes did not settle)"); return P2GPU_E_DEVICE; }
       BT(hipMemsetAsync(flags, 0, 4, st), "scratch");
-      hipLaunchKernelGGL(build_hook_kernel, dim3(grid_for(E)), dim3(TPB), 0, st, copies, E, R, parent, flags);
+      hipLaunchKernelGGL(classes::hook_kernel<CopyPairs>, dim3(grid_for(E)), dim3(TPB), 0, st, CopyPairs{copies, R}, E, parent, flags);
       BT(hipMemcpyAsync(&hc, flags, 4, hipMemcpyDeviceToHost, st), "read flag");
       BT(hipStreamSynchronize(st), "hook");
       if (!hc) break;
       for (int j = 0;; j++) {
         if (j > 64) { set_err("p2gpu_circuit_build: internal error (compression did not settle)"); return P2GPU_E_DEVICE; }
         BT(hipMemsetAsync(flags, 0, 4, st), "scratch");
-        hipLaunchKernelGGL(build_jump_kernel, dim3(grid_for(T)), dim3(TPB), 0, st, list, T, parent, flags);
+        hipLaunchKernelGGL(classes::jump_kernel<classes::JUMP_STEPS>, dim3(grid_for(T)), dim3(TPB), 0, st, list, T, parent, flags);
         BT(hipMemcpyAsync(&hc, flags, 4, hipMemcpyDeviceToHost, st), "read flag");
         BT(hipStreamSynchronize(st), "jump");
         if (!hc) break;

@@ -1,7 +1,8 @@
 // genwit.hip -- the witness from the solver's values, on the device (SURVEY 8(f) "P2": `generate_partial_witness`,
 // iop/generator.rs -- every generator in dependency order, every copy constraint propagated).
 //
-// Plan (once per circuit and seed set, p2gpu_witness_plan_create; host code):
+// Plan (once per circuit and seed set; p2gpu_witness_plan_create: host code, below -- p2gpu_witness_plan_build compiles the same
+// plan on the device, genplan.hip, and this one is its differential oracle):
 //   classes   sigma is read back and decoded (sigma[x] = k_is[col'] * w^row': the coset of the value names col', the
 //             subgroup element row'); the cycles become compact class ids.  A handle from a blob and one from
 //             p2gpu_circuit_build hold the same sigma, hence give the same plan.
@@ -24,24 +25,17 @@
 #include <chrono>
 #include <unordered_map>
 #include "generators.hpp"
-#include "prover_internal.hpp"
+#include "genplan.hpp"
 
 using namespace p2;
 
 namespace {
 
-constexpr uint32_t UNSET = 0xFFFFFFFFu;   // cell without a slot
-constexpr uint32_t WRITER = 0x80000000u;  // cell_slot bit: this cell's op writes the slot (every other one compares)
+constexpr uint32_t UNSET = PLAN_UNSET, WRITER = PLAN_WRITER;
 constexpr uint32_t WALK_TPB = 512;
 // witnesses per workgroup of the walk; a power of two.  8 is the starting value (41 ops of the median SHA level x 8 = 328 of 512
 // lanes), NOT yet a measured choice: profiles/device_witness.md says how 4 / 8 / 16 are to be compared
 constexpr uint32_t WALK_GROUP = 8;
-enum : uint32_t {
-  OP_SEED = 0, OP_CONSTANT, OP_ARITHMETIC, OP_BASE_SPLIT, OP_BASE_JOIN, OP_RA_COPY, OP_RA_CONSTS, OP_POSEIDON, OP_U32_ARITHMETIC,
-  OP_U32_ADD_MANY, OP_U32_SUBTRACTION, OP_U32_RANGE_CHECK, OP_COMPARISON
-};
-// x: the row (OP_SEED: the seed's index), y: code | sub << 8 (the slot / copy inside the row)
-typedef uint2 OpRec;
 
 struct WalkArgs {
   const OpRec *ops;
@@ -272,23 +266,25 @@ struct Compiler {
     return P2GPU_OK;
   }
 
-  // an op over the input columns `in` and the columns `out` its generator sets (routed ones only); kept when one of its
-  // cells has a slot, and then every output cell gets one
-  uint32_t add_op(uint32_t code, uint32_t row, uint32_t sub, const std::vector<uint32_t> &in, const std::vector<uint32_t> &out) {
+  // an op of the row (genops.hpp lists its input columns and the columns its generator sets; routed ones only count); kept when
+  // one of its cells has a slot, and then every output cell gets one
+  uint32_t add_op(uint32_t row, const OpCols &oc) {
     bool active = false;
-    for (uint32_t col : in) active |= col < R && cell_slot[key(row, col)] != UNSET;
-    for (uint32_t col : out) active |= col < R && cell_slot[key(row, col)] != UNSET;
+    auto has_slot = [&](uint32_t col) { active |= col < R && cell_slot[key(row, col)] != UNSET; };
+    for_cols(oc.in, has_slot);
+    for_cols(oc.out, has_slot);
     if (!active) return UNSET;
     HostOp op;
-    op.code = code; op.row = row; op.sub = sub;
+    op.code = oc.code; op.row = row; op.sub = oc.sub;
     op.in0 = (uint32_t)cols.size();
-    for (uint32_t col : in) if (col < R && cell_slot[key(row, col)] != UNSET) cols.push_back(col);  // a cell without a slot reads as zero
+    for_cols(oc.in, [&](uint32_t col) { if (col < R && cell_slot[key(row, col)] != UNSET) cols.push_back(col); });  // a cell without a slot reads as zero
     op.in1 = op.out0 = (uint32_t)cols.size();
-    for (uint32_t col : out) if (col < R) {
+    for_cols(oc.out, [&](uint32_t col) {
+      if (col >= R) return;
       uint32_t &s = cell_slot[key(row, col)];
       if (s == UNSET) s = slots++;
       cols.push_back(col);
-    }
+    });
     op.out1 = (uint32_t)cols.size();
     ops.push_back(op);
     return (uint32_t)ops.size() - 1;
@@ -297,67 +293,20 @@ struct Compiler {
   void row_ops(uint32_t row) {
     const GateDesc &g = c->gates[row_gate[row]];
     auto LC = [&](uint32_t i) { return i < ngc ? gconsts[(size_t)i * n + row] : (gl_t)0; };
-    auto range = [](uint32_t a, uint32_t b) { std::vector<uint32_t> v; for (uint32_t i = a; i < b; i++) v.push_back(i); return v; };
-    auto cat = [](std::vector<uint32_t> a, const std::vector<uint32_t> &b) { a.insert(a.end(), b.begin(), b.end()); return a; };
-    switch (g.kind) {
-    case G_CONSTANT: add_op(OP_CONSTANT, row, 0, {}, range(0, g.p[0])); break;
-    case G_ARITHMETIC: {
-      const gl_t c0 = LC(0), c1 = LC(1);
-      for (uint32_t i = 0; i < g.p[0]; i++) {
-        std::vector<uint32_t> in;
-        if (c0) in = {4 * i, 4 * i + 1};
-        if (c1) in.push_back(4 * i + 2);
-        add_op(OP_ARITHMETIC, row, i, in, {4 * i + 3});
-      }
-      break;
-    }
-    case G_BASE_SUM: {
+    const gl_t c0 = LC(0), c1 = LC(1);
+    if (g.kind == G_BASE_SUM) {
       // every cell is an input of one direction and an output of the other: all of them get their slot before either op
       // lists its inputs
       bool active = false;
       for (uint32_t col = 0; col <= g.p[1] && col < R; col++) active |= cell_slot[key(row, col)] != UNSET;
-      if (!active) break;
+      if (!active) return;
       for (uint32_t col = 0; col <= g.p[1] && col < R; col++)
         if (cell_slot[key(row, col)] == UNSET) cell_slot[key(row, col)] = slots++;
-      const uint32_t a = add_op(OP_BASE_SPLIT, row, 0, {0}, range(1, 1 + g.p[1]));
-      const uint32_t b = add_op(OP_BASE_JOIN, row, 0, range(1, 1 + g.p[1]), {0});
+      const uint32_t a = add_op(row, row_op(g, 0, c0, c1)), b = add_op(row, row_op(g, 1, c0, c1));
       if (a != UNSET) ops[a].twin = b, ops[b].twin = a;  // (both see the same cells: kept or dropped together)
-      break;
+      return;
     }
-    case G_RANDOM_ACCESS: {
-      const uint32_t bits = g.p[0], copies = g.p[1], extra = g.p[2], vec = 1u << bits, routed = (2 + vec) * copies + extra;
-      for (uint32_t cp = 0; cp < copies; cp++) {
-        const uint32_t base = (2 + vec) * cp;
-        add_op(OP_RA_COPY, row, cp, cat({base}, range(base + 2, base + 2 + vec)), cat({base + 1}, range(routed + cp * bits, routed + (cp + 1) * bits)));
-      }
-      if (extra) add_op(OP_RA_CONSTS, row, 0, {}, range((2 + vec) * copies, (2 + vec) * copies + extra));
-      break;
-    }
-    case G_POSEIDON: add_op(OP_POSEIDON, row, 0, cat(range(0, 12), {24}), cat(range(12, 24), range(25, 135))); break;
-    case G_U32_ARITHMETIC:
-      for (uint32_t i = 0; i < g.p[0]; i++)
-        add_op(OP_U32_ARITHMETIC, row, i, range(6 * i, 6 * i + 3), cat(range(6 * i + 3, 6 * i + 6), range(6 * g.p[0] + 32 * i, 6 * g.p[0] + 32 * i + 32)));
-      break;
-    case G_U32_ADD_MANY: {
-      const uint32_t na = g.p[0], nops = g.p[1];
-      for (uint32_t i = 0; i < nops; i++) {
-        const uint32_t b = (na + 3) * i;
-        add_op(OP_U32_ADD_MANY, row, i, range(b, b + na + 1), cat(range(b + na + 1, b + na + 3), range((na + 3) * nops + 18 * i, (na + 3) * nops + 18 * i + 18)));
-      }
-      break;
-    }
-    case G_U32_SUBTRACTION:
-      for (uint32_t i = 0; i < g.p[0]; i++)
-        add_op(OP_U32_SUBTRACTION, row, i, range(5 * i, 5 * i + 3), cat(range(5 * i + 3, 5 * i + 5), range(5 * g.p[0] + 16 * i, 5 * g.p[0] + 16 * i + 16)));
-      break;
-    case G_U32_RANGE_CHECK: add_op(OP_U32_RANGE_CHECK, row, 0, range(0, g.p[0]), range(g.p[0], 17 * g.p[0])); break;
-    case G_COMPARISON: {
-      const uint32_t nc = g.p[1], cb = (g.p[0] + nc - 1) / nc;
-      add_op(OP_COMPARISON, row, 0, {0, 1}, range(2, 4 + 5 * nc + cb + 1));
-      break;
-    }
-    default: break;
-    }
+    for (uint32_t k = 0, m = row_num_ops(g); k < m; k++) add_op(row, row_op(g, k, c0, c1));
   }
   // seeds first, then the rows in order; levels; what the schedule did not reach.  order: the ops by (level, creation order)
   int schedule(const std::vector<uint2> &seeds, std::vector<uint32_t> &order, std::vector<uint32_t> &level_off) {
@@ -450,27 +399,62 @@ struct Compiler {
 };
 
 
+// the seed checks of both compilers: every seed inside the matrix, no cell twice
+int plan_seeds(p2gpu_witness_plan *p, const uint32_t *seed_cells, size_t n_seeds) {
+  const p2gpu_circuit *c = p->c;
+  const size_t n = c->n;
+  std::unordered_map<uint64_t, size_t> seen;
+  for (size_t i = 0; i < n_seeds; i++) {
+    const uint32_t row = seed_cells[2 * i], col = seed_cells[2 * i + 1];
+    if (row >= n || col >= c->W) {
+      set_err("seed %zu names cell (row %u, column %u) outside the %zu x %u wire matrix", i, row, col, n, c->W);
+      return P2GPU_E_ARG;
+    }
+    if (!seen.emplace(((uint64_t)row << 32) | col, i).second) {
+      set_err("cell (row %u, column %u) is seeded twice (seeds %zu and %zu)", row, col, seen[((uint64_t)row << 32) | col], i);
+      return P2GPU_E_ARG;
+    }
+    p->h_seed_cells.push_back(make_uint2(row, col));
+  }
+  return P2GPU_OK;
+}
+
+// The tail of both compilers: the plan's own buffers, filled from the three arrays (an upload for the host compiler, a copy
+// inside HBM and ONE read-back -- the op records name_contradiction needs -- for the device one).
+int plan_finish(p2gpu_witness_plan *p, const PlanArrays &a) {
+  p2gpu_circuit *c = p->c;
+  const size_t n_seeds = p->n_seeds, tot = (size_t)c->R * c->n;
+  p->levels = a.levels; p->slots = a.slots; p->n_ops = a.n_ops; p->widest = a.widest;
+  HIP_TRY(p->ops.alloc(std::max<size_t>(1, a.n_ops)));
+  HIP_TRY(p->level_off.alloc((size_t)a.levels + 1));
+  HIP_TRY(p->cell_slot.alloc(tot));
+  HIP_TRY(p->val.alloc(std::max<uint32_t>(1, a.slots)));
+  HIP_TRY(p->seed_vals.alloc(std::max<size_t>(1, n_seeds)));
+  HIP_TRY(p->seed_cells.alloc(std::max<size_t>(1, n_seeds)));
+  HIP_TRY(p->err.alloc(1));
+  HIP_TRY(hipHostMalloc((void **)&p->pin, 8 * (n_seeds + 1), hipHostMallocDefault));
+  HIP_TRY(hipEventCreate(&p->ev0));
+  HIP_TRY(hipEventCreate(&p->ev1));
+  p->h_ops.resize(a.n_ops);
+  if (a.n_ops) {
+    HIP_TRY(hipMemcpyAsync(p->ops.p, a.ops, sizeof(OpRec) * a.n_ops, a.kind, c->stream));
+    if (a.kind == hipMemcpyHostToDevice) memcpy(p->h_ops.data(), a.ops, sizeof(OpRec) * a.n_ops);
+    else HIP_TRY(hipMemcpyAsync(p->h_ops.data(), a.ops, sizeof(OpRec) * a.n_ops, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(hipMemcpyAsync(p->level_off.p, a.level_off, 4 * ((size_t)a.levels + 1), a.kind, c->stream));
+  HIP_TRY(hipMemcpyAsync(p->cell_slot.p, a.cell_slot, 4 * tot, a.kind, c->stream));
+  if (n_seeds) HIP_TRY(hipMemcpyAsync(p->seed_cells.p, p->h_seed_cells.data(), sizeof(uint2) * n_seeds, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(p->val.p, 0, 8 * (size_t)std::max<uint32_t>(1, a.slots), c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // (the arrays go out of scope)
+  return P2GPU_OK;
+}
+
 int plan_compile(p2gpu_witness_plan *p, const uint32_t *seed_cells, size_t n_seeds) {
   p2gpu_circuit *c = p->c;
   Compiler K;
   K.c = c; K.n = c->n; K.R = c->R; K.d = c->d; K.ngc = c->NC - c->num_selectors;
   const size_t n = c->n, tot = (size_t)c->R * n;
-  // ---- seeds ----
-  {
-    std::unordered_map<uint64_t, size_t> seen;
-    for (size_t i = 0; i < n_seeds; i++) {
-      const uint32_t row = seed_cells[2 * i], col = seed_cells[2 * i + 1];
-      if (row >= n || col >= c->W) {
-        set_err("seed %zu names cell (row %u, column %u) outside the %zu x %u wire matrix", i, row, col, n, c->W);
-        return P2GPU_E_ARG;
-      }
-      if (!seen.emplace(((uint64_t)row << 32) | col, i).second) {
-        set_err("cell (row %u, column %u) is seeded twice (seeds %zu and %zu)", row, col, seen[((uint64_t)row << 32) | col], i);
-        return P2GPU_E_ARG;
-      }
-      p->h_seed_cells.push_back(make_uint2(row, col));
-    }
-  }
+  if (int rc = plan_seeds(p, seed_cells, n_seeds)) return rc;
   // ---- the circuit's tables, as the device holds them ----
   K.sigma.resize(tot); K.gconsts.resize((size_t)K.ngc * n); K.row_gate.resize(n);
   HIP_TRY(hipMemcpyAsync(K.sigma.data(), c->d_sigmas.p, 8 * tot, hipMemcpyDeviceToHost, c->stream));
@@ -480,31 +464,23 @@ int plan_compile(p2gpu_witness_plan *p, const uint32_t *seed_cells, size_t n_see
   if (int rc = K.classes()) return rc;
   std::vector<uint32_t> order, level_off;
   if (int rc = K.schedule(p->h_seed_cells, order, level_off)) return rc;
-  auto &ops = K.ops;
-  // ---- to the device ----
-  p->levels = (uint32_t)level_off.size() - 1;
-  p->slots = K.slots;
-  p->n_ops = order.size();
-  for (uint32_t l = 0; l < p->levels; l++) p->widest = std::max(p->widest, level_off[l + 1] - level_off[l]);
-  p->h_ops.reserve(order.size());
-  for (uint32_t i : order) p->h_ops.push_back(make_uint2(ops[i].row, ops[i].code | (ops[i].sub << 8)));
-  HIP_TRY(p->ops.alloc(std::max<size_t>(1, order.size())));
-  HIP_TRY(p->level_off.alloc(level_off.size()));
-  HIP_TRY(p->cell_slot.alloc(tot));
-  HIP_TRY(p->val.alloc(std::max<uint32_t>(1, K.slots)));
-  HIP_TRY(p->seed_vals.alloc(std::max<size_t>(1, n_seeds)));
-  HIP_TRY(p->seed_cells.alloc(std::max<size_t>(1, n_seeds)));
-  HIP_TRY(p->err.alloc(1));
-  HIP_TRY(hipHostMalloc((void **)&p->pin, 8 * (n_seeds + 1), hipHostMallocDefault));
-  HIP_TRY(hipEventCreate(&p->ev0));
-  HIP_TRY(hipEventCreate(&p->ev1));
-  if (!order.empty()) HIP_TRY(hipMemcpyAsync(p->ops.p, p->h_ops.data(), sizeof(OpRec) * order.size(), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(p->level_off.p, level_off.data(), 4 * level_off.size(), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(p->cell_slot.p, K.cell_slot.data(), 4 * tot, hipMemcpyHostToDevice, c->stream));
-  if (n_seeds) HIP_TRY(hipMemcpyAsync(p->seed_cells.p, p->h_seed_cells.data(), sizeof(uint2) * n_seeds, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemsetAsync(p->val.p, 0, 8 * (size_t)std::max<uint32_t>(1, K.slots), c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));  // (the host vectors go out of scope)
-  return P2GPU_OK;
+  std::vector<OpRec> recs;
+  recs.reserve(order.size());
+  for (uint32_t i : order) recs.push_back(make_uint2(K.ops[i].row, K.ops[i].code | (K.ops[i].sub << 8)));
+  PlanArrays a;
+  a.cell_slot = K.cell_slot.data(); a.ops = recs.data(); a.level_off = level_off.data();
+  a.levels = (uint32_t)level_off.size() - 1; a.slots = K.slots; a.n_ops = order.size();
+  for (uint32_t l = 0; l < a.levels; l++) a.widest = std::max(a.widest, level_off[l + 1] - level_off[l]);
+  return plan_finish(p, a);
+}
+
+// the device compiler (genplan.hip) behind the same seed checks and the same tail
+int plan_build(p2gpu_witness_plan *p, const uint32_t *seed_cells, size_t n_seeds) {
+  if (int rc = plan_seeds(p, seed_cells, n_seeds)) return rc;
+  classes::Scratch S;
+  PlanArrays a;
+  if (int rc = plan_compile_device(p->c, p->h_seed_cells, S, a)) return rc;
+  return plan_finish(p, a);  // (S goes out of scope behind it: the plan holds what a host-compiled one holds)
 }
 
 // the batched buffers, grown to hold `batch` witnesses (the stream is idle between calls: one call at a time per handle).
@@ -614,11 +590,9 @@ int generate_batch(p2gpu_witness_plan *p, const uint64_t *seed_values, size_t ba
   return rc;
 }
 
-}  // namespace
-
-extern "C" {
-
-int p2gpu_witness_plan_create(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, p2gpu_witness_plan **out) try {
+// the front checks and the ownership of a half-made plan, for either compiler
+int plan_new(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, p2gpu_witness_plan **out,
+             int (*compile)(p2gpu_witness_plan *, const uint32_t *, size_t)) {
   if (out) *out = nullptr;
   if (!c || !out || (n_seeds && !seed_cells)) return P2GPU_E_ARG;
   if (int rc = prover_handle(c)) return rc;
@@ -634,7 +608,7 @@ int p2gpu_witness_plan_create(p2gpu_circuit *c, const uint32_t *seed_cells, size
   p->n_seeds = (uint32_t)n_seeds;
   int rc;
   try {
-    rc = plan_compile(p, seed_cells, n_seeds);
+    rc = compile(p, seed_cells, n_seeds);
   } catch (...) {
     p->release();
     delete p;
@@ -647,6 +621,34 @@ int p2gpu_witness_plan_create(p2gpu_circuit *c, const uint32_t *seed_cells, size
   }
   p->compile_ms = wall_ms() - t0;
   *out = p;
+  return P2GPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int p2gpu_witness_plan_create(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, p2gpu_witness_plan **out) try {
+  return plan_new(c, seed_cells, n_seeds, out, plan_compile);
+} P2GPU_CATCH
+
+int p2gpu_witness_plan_build(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, p2gpu_witness_plan **out) try {
+  return plan_new(c, seed_cells, n_seeds, out, plan_build);
+} P2GPU_CATCH
+
+int p2gpu_witness_plan_export(const p2gpu_witness_plan *p, uint32_t *cell_slot, uint64_t *ops, uint32_t *level_off, size_t sizes[3]) try {
+  if (!p || !sizes) return P2GPU_E_ARG;
+  const p2gpu_circuit *c = p->c;
+  const size_t tot = (size_t)c->R * c->n;
+  sizes[0] = tot; sizes[1] = p->n_ops; sizes[2] = (size_t)p->levels + 1;
+  if (!cell_slot && !ops && !level_off) return P2GPU_OK;
+  if (!cell_slot || !ops || !level_off) return P2GPU_E_ARG;
+  static_assert(sizeof(OpRec) == sizeof(uint64_t), "an op record is one 64-bit word: row | (code | sub << 8) << 32");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(cell_slot, p->cell_slot.p, 4 * tot, hipMemcpyDeviceToHost, c->stream));
+  if (p->n_ops) HIP_TRY(hipMemcpyAsync(ops, p->ops.p, sizeof(OpRec) * p->n_ops, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(level_off, p->level_off.p, 4 * sizes[2], hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return P2GPU_OK;
 } P2GPU_CATCH
 

@@ -93,6 +93,8 @@ def load_library():
     lib.p2gpu_prove_sparse.argtypes = [a[0], a[1], ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32] + list(a[2:])
     lib.p2gpu_fill_witness.argtypes = [vp, vp]
     lib.p2gpu_witness_plan_create.argtypes = [vp, vp, sz, ctypes.POINTER(vp)]
+    lib.p2gpu_witness_plan_build.argtypes = [vp, vp, sz, ctypes.POINTER(vp)]
+    lib.p2gpu_witness_plan_export.argtypes = [vp, vp, vp, vp, vp]
     lib.p2gpu_witness_plan_destroy.argtypes = [vp]
     lib.p2gpu_witness_plan_destroy.restype = None
     lib.p2gpu_witness_plan_info.argtypes = [vp, vp, vp]
@@ -428,10 +430,11 @@ class CircuitData:
         _check(self._lib.p2gpu_fill_witness(self._h, ctypes.c_void_p(wires_dev.data_ptr())))
         return wires_dev
 
-    def witness_plan(self, seed_cells):
+    def witness_plan(self, seed_cells, compile="host"):
         """``p2gpu_witness_plan_create``: the plan that turns the values of `seed_cells` ([(row, col)]: the cells the
-        caller assigns per proof, ``pw.set_target`` on the Rust side) into the whole witness on the GPU."""
-        return WitnessPlan(self, seed_cells)
+        caller assigns per proof, ``pw.set_target`` on the Rust side) into the whole witness on the GPU.
+        ``compile="device"``: the same plan through ``p2gpu_witness_plan_build``, compiled on the GPU."""
+        return WitnessPlan(self, seed_cells, compile=compile)
 
     def prove_routed(self, routed, public_inputs=()):
         """Prove from the routed columns only ([num_routed_wires][degree], host): gate-internal
@@ -509,7 +512,9 @@ class WitnessPlan:
     """Witness generation on the GPU for one circuit and one set of seed cells (``p2gpu_witness_plan``).  Close it before
     the circuit."""
 
-    def __init__(self, circuit, seed_cells):
+    def __init__(self, circuit, seed_cells, compile="host"):
+        if compile not in ("host", "device"):
+            raise P2GpuError(-7, f'compile must be "host" or "device", not {compile!r}')
         self._cd, self._lib = circuit, circuit._lib
         cells = np.ascontiguousarray(np.array(list(seed_cells), dtype=np.int64).reshape(-1, 2))
         if cells.size and (cells.min() < 0 or cells.max() >= 1 << 32):
@@ -517,7 +522,8 @@ class WitnessPlan:
         cells = cells.astype(np.uint32)
         self.num_seeds = len(cells)
         self._h = ctypes.c_void_p()
-        _check(self._lib.p2gpu_witness_plan_create(circuit._h, cells.ctypes.data if cells.size else None, len(cells), ctypes.byref(self._h)))
+        make = self._lib.p2gpu_witness_plan_build if compile == "device" else self._lib.p2gpu_witness_plan_create
+        _check(make(circuit._h, cells.ctypes.data if cells.size else None, len(cells), ctypes.byref(self._h)))
 
     def _values(self, values):
         v = _u64(np.array([int(x) for x in values], dtype=np.uint64))
@@ -532,6 +538,17 @@ class WitnessPlan:
         out = dict(zip(("ops", "levels", "widest_level", "slots", "seeds"), (int(x) for x in counts)))
         out.update(compile_ms=float(ms[0]), walk_ms=float(ms[1]))
         return out
+
+    def export(self):
+        """``p2gpu_witness_plan_export``: (cell_slot [num_routed_wires][degree] uint32, ops [n_ops] uint64, level_off
+        [levels + 1] uint32), the plan's device arrays as numpy arrays."""
+        sizes = (ctypes.c_size_t * 3)()
+        _check(self._lib.p2gpu_witness_plan_export(self._h, None, None, None, sizes))
+        cell_slot = np.zeros(sizes[0], dtype=np.uint32)
+        ops = np.zeros(max(1, sizes[1]), dtype=np.uint64)
+        level_off = np.zeros(sizes[2], dtype=np.uint32)
+        _check(self._lib.p2gpu_witness_plan_export(self._h, cell_slot.ctypes.data, ops.ctypes.data, level_off.ctypes.data, sizes))
+        return cell_slot.reshape(self._cd.num_routed_wires, self._cd.degree), ops[:sizes[1]], level_off
 
     def generate(self, values):
         """``p2gpu_generate_witness``: the wire matrix [num_wires][degree] as an int64 tensor on the circuit's GPU."""

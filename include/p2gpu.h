@@ -17,7 +17,7 @@
  *   p2gpu_fill_witness / p2gpu_prove_routed
  *                          <- the row-local tail of `generate_partial_witness`: the gates' own
  *                             SimpleGenerators (e.g. arithmetic_u32.rs:376-426)
- *   p2gpu_witness_plan_create / p2gpu_generate_witness / p2gpu_prove_seeds
+ *   p2gpu_witness_plan_create / p2gpu_witness_plan_build / p2gpu_generate_witness / p2gpu_prove_seeds
  *                          <- all of `generate_partial_witness` (plonky2 iop/generator.rs, called by `prove`): the caller
  *                             hands over the `pw.set_target` values only, generators and copy constraints run on the GPU
  *   p2gpu_generate_witness_batch
@@ -177,8 +177,19 @@ int p2gpu_prove_sparse(p2gpu_circuit *c, const uint64_t *wires, uint32_t ncols, 
 typedef struct p2gpu_witness_plan p2gpu_witness_plan;
 int p2gpu_witness_plan_create(p2gpu_circuit *c, const uint32_t *seed_cells /* [n_seeds][2] = (row, col) */, size_t n_seeds,
                               p2gpu_witness_plan **out);
+/* The same plan compiled on the device, on the handle's stream (csrc/genplan.hip): the arguments, the refusals --
+ * code, words and cell -- and every array of the plan are p2gpu_witness_plan_create's, and everything that takes a plan takes
+ * either.  Nothing of the circuit is read back; the scratch is released before it returns. */
+int p2gpu_witness_plan_build(p2gpu_circuit *c, const uint32_t *seed_cells /* [n_seeds][2] = (row, col) */, size_t n_seeds,
+                             p2gpu_witness_plan **out);
+/* The plan's three device arrays, read back: cell_slot [num_routed_wires][n] (the value slot of every routed cell, 0xFFFFFFFF:
+ * none, bit 31: this cell's op writes the slot), ops [n_ops] (row | (code | sub << 8) << 32, by level and creation order),
+ * level_off [levels + 1].  sizes = { num_routed_wires * n, n_ops, levels + 1 } is always filled; with all three pointers NULL
+ * nothing else happens.  A plan from either entry point. */
+int p2gpu_witness_plan_export(const p2gpu_witness_plan *p, uint32_t *cell_slot, uint64_t *ops, uint32_t *level_off, size_t sizes[3]);
 void p2gpu_witness_plan_destroy(p2gpu_witness_plan *p);
-/* counts: ops, levels, widest level, value slots, seeds; ms: plan compilation (host), level walk of the last call (device) */
+/* counts: ops, levels, widest level, value slots, seeds; ms: plan compilation (wall time of _create or _build), level walk of
+ * the last call (device) */
 int p2gpu_witness_plan_info(const p2gpu_witness_plan *p, uint64_t counts[5], double ms[2]);
 /* seed_values: host, [n_seeds] in the plan's order.  wires_dev_out: device, [num_wires][n], written completely.  One workgroup
  * walks the levels, a kernel copies the class values to the routed cells, p2gpu_fill_witness's kernel derives the rest.  A

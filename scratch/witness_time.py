@@ -7,13 +7,17 @@ handles through prove_seeds against prove_dev.
 Many witnesses in one walk (p2gpu_generate_witness_batch): `batch_sha256` -- one batch of B against B lone calls, walk and
 whole call, B = 1 .. 64 -- and `inflight4_sha256.with_batch8` -- the four resident proofs in flight with a fifth handle
 walking batches of 8 beside them.
-usage: witness_time.py [runs] [inflight_seconds] [--only SECTION,...] [--tree DIR] [--against DIR]
+usage: witness_time.py [runs] [inflight_seconds] [--only SECTION,...] [--tree DIR] [--against DIR] [--compile host|device]
   -- one JSON line on stdout.  SECTIONs: plans, sha_plan (the SHA-256 plan alone), lone, batch, inflight; default: all but
   sha_plan.
   --tree DIR     measure the package of another checkout of this repository (built there), with this script: an older
                  commit (sha_plan, plans, lone), or a build with another WALK_GROUP (batch).
   --against DIR  `--only sha_plan` in fresh processes, alternating between DIR and this checkout, `runs` times each: the lone
-                 walk of two commits side by side."""
+                 walk of two commits side by side.
+  --compile HOW  which plan compiler makes every plan: host (p2gpu_witness_plan_create, the default) or device
+                 (p2gpu_witness_plan_build).  `plans.*.compile_ms` is that compiler's time; for five alternating runs in fresh
+                 processes call `--only sha_plan` (or `plans`) once per run and compiler.  P2GPU_TRACE=1 prints the device
+                 compiler's per-phase marks on stderr."""
 import json
 import os
 import statistics
@@ -26,13 +30,16 @@ HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 argv, opts = [], {}
 it = iter(sys.argv[1:])
 for arg in it:
-    if arg in ("--only", "--tree", "--against"):
+    if arg in ("--only", "--tree", "--against", "--compile"):
         opts[arg] = next(it)
     else:
         argv.append(arg)
 runs = int(argv[0]) if argv else 5
 inflight_s = float(argv[1]) if len(argv) > 1 else 3.0
 ROOT = os.path.abspath(opts.get("--tree", HERE))
+# (no keyword for the host compiler: an older checkout given as --tree has none)
+PLAN_KW = {"compile": "device"} if opts.get("--compile", "host") == "device" else {}
+assert opts.get("--compile", "host") in ("host", "device")
 only = set(opts["--only"].split(",")) if "--only" in opts else {"plans", "lone", "batch", "inflight"}
 
 
@@ -74,7 +81,7 @@ def sha_builder():
 def plan_figures(cb, witness):
     cells, values = cb.witness_seeds(witness)
     cd = pkg.CircuitData(cb.blob())
-    plan = cd.witness_plan(cells)
+    plan = cd.witness_plan(cells, **PLAN_KW)
     walks = []
     for _ in range(runs + 1):
         plan.generate(values)
@@ -87,7 +94,7 @@ def plan_figures(cb, witness):
     return info
 
 
-res = {"runs": runs, "tree": ROOT, "plans": {}}
+res = {"runs": runs, "tree": ROOT, "compile": opts.get("--compile", "host"), "plans": {}}
 if "plans" in only:
     for name, prog in test_translate._reference_programs().items():
         cb = pkg.translate.CircuitBuilderFromAcirToPlonky2(num_wires=135)
@@ -105,7 +112,7 @@ blob = cb.blob()
 
 # ---- lone proof: (a) event loop + p2gpu_prove, (b) p2gpu_prove_seeds, floor: p2gpu_prove_dev ----
 cd = pkg.CircuitData(blob)
-plan = cd.witness_plan(cells)
+plan = cd.witness_plan(cells, **PLAN_KW)
 loop_ms, a_ms, b_ms, dev_ms = [], [], [], []
 wires_dev = plan.generate(values).clone()
 for i in range(runs + 1 if "lone" in only else 0):
@@ -177,7 +184,7 @@ if "inflight" not in only:
 
 # ---- four proofs in flight on four handles ----
 handles = [pkg.CircuitData(blob) for _ in range(4)]
-plans = [h.witness_plan(cells) for h in handles]
+plans = [h.witness_plan(cells, **PLAN_KW) for h in handles]
 mats = [p.generate(values).clone() for p in plans]
 
 
@@ -207,7 +214,7 @@ res["inflight4_sha256"] = {"prove_dev_per_s": stats(dev_rate), "prove_seeds_per_
 
 # ---- the same four resident proofs, with and without a fifth handle walking batches of 8 beside them ----
 side_cd = pkg.CircuitData(blob)
-side_plan = side_cd.witness_plan(cells)
+side_plan = side_cd.witness_plan(cells, **PLAN_KW)
 side_vals = members(8)
 side_plan.generate_batch(side_vals)
 alone, beside, batches = [], [], []
