@@ -77,27 +77,16 @@ int tree_alloc(Batch &b, uint32_t C, size_t m0, size_t cap_per) {
 // levels_done: tree levels above the leaf digests that are in place already (the leaf-hash launch builds two: merkle.hip)
 int tree_build(p2gpu_circuit *c, Batch &b, size_t m0, uint32_t levels_done) {
   const uint32_t C = c->C, CL = b.ncl;
-  size_t m = m0 >> levels_done;
+  const size_t m = m0 >> levels_done;
   const size_t cap_target = ((size_t)1 << c->cap_h) >> c->rate_bits;
+  const size_t cap_per = std::min(m, cap_target);  // (leaves fewer than the cap: they are the cap)
   // a tree every rank holds completely (constants/sigmas, FRI steps >= 1) needs no exchange -- except in
   // the one-rank plumbing test, where every tree goes through the transport
   const bool local = CL == C && !(c->shard_world == 1 && sharded(c));
-  // the kernel that computes the cap level stores it in page-locked host memory as well when it can (merkle_tail): no
+  // the kernel that computes the cap level stores it in page-locked host memory as well when it can (tree_levels): no
   // copy kernel between the last level and the transcript's sync
   dig_t *mirror = local && m0 > cap_target ? c->pin.take<dig_t>(C * cap_target) : nullptr;
-  bool mirrored = false;
-  for (size_t l = 1 + levels_done; l < b.level_off.size(); l++) {
-    // the rest of the tree in merkle_tail: a few launches of several levels each (Keccak), or one (Poseidon)
-    const size_t from = merkle_tail_from(hprc(c));
-    if ((size_t)CL * (m >> 1) <= from) {
-      mirrored = merkle_tail(c->stream, b.dig.p + b.level_off[l - 1], CL, (uint32_t)m, (uint32_t)cap_target, hprc(c), mirror);
-      m = cap_target;
-      break;
-    }
-    merkle_level(c->stream, b.dig.p + b.level_off[l - 1], b.dig.p + b.level_off[l], CL, (uint32_t)m, hprc(c));
-    m >>= 1;
-  }
-  const size_t cap_per = m;
+  const bool mirrored = tree_levels(c->stream, b.dig.p + b.level_off[levels_done], CL, (uint32_t)m, (uint32_t)cap_target, hprc(c), mirror);
   dig_t *raw = mirrored ? mirror : c->pin.take<dig_t>(C * cap_per);  // [global coset][cap_per]; pinned: the D2H below is a true async copy
   if (!raw) return pin_exhausted();
   if (local) {

@@ -144,21 +144,19 @@ struct VirtCols {
 // above the leaves the launch has also built (0 or 2: merkle.hip hash_lde_leaves_kf_kernel<V, 2>)
 uint32_t hash_lde_leaves(hipStream_t st, const gl_t *lde, uint32_t cols, uint32_t d, uint32_t cosets, dig_t *dig, const gl_t *prc = nullptr,
                          const VirtCols *virt = nullptr, dig_t *lvl1 = nullptr, dig_t *lvl2 = nullptr);
-// row-major rows (stage-level operator)
-void hash_rows(hipStream_t st, const gl_t *rows, size_t n_rows, uint32_t row_len, dig_t *dig);
-// FRI step leaves: vals [cosets][2][npc] (ext coordinates), leaf = 16 ext values; dig [cosets][npc/16]
-void hash_fri_leaves(hipStream_t st, const gl_t *vals, uint32_t lg_npc, uint32_t cosets, uint32_t arity_bits,
-                     dig_t *dig, const gl_t *prc = nullptr);
-// one tree level: in [cosets][m] -> out [cosets][m/2], out[c][k] = H(in[c][k], in[c][k + m/2])
-// incremental variant: absorb the rate blocks [blk0, blk0 + nblk) (17 columns each) into the sponge
-// states kept in `state` ([cosets][25][n]); `last` also absorbs the tail + padding and writes digests
+// the same leaf digests (Keccak only) for columns that arrive in chunks: absorb the rate blocks [blk0, blk0 + nblk) (17 columns
+// each) into the sponge states kept in `state` ([cosets][25][n]); `last` also absorbs the tail + padding and writes digests
 void hash_lde_absorb(hipStream_t st, const gl_t *lde, uint32_t cols, uint32_t d, uint32_t cosets, uint32_t blk0,
                      uint32_t nblk, bool first, bool last, uint64_t *state, dig_t *dig, const VirtCols *virt = nullptr);
-void merkle_level(hipStream_t st, const dig_t *in, dig_t *out, uint32_t cosets, uint32_t m, const gl_t *prc = nullptr);
-// every level below one with m <= 4096 nodes per coset, down to cap_per nodes per coset, in one launch
-size_t merkle_tail_from(const gl_t *prc);
-// host_mirror (optional, page-locked, [cosets][cap_per]): returns true when the final level was also written there
-bool merkle_tail(hipStream_t st, dig_t *lvl, uint32_t cosets, uint32_t m, uint32_t cap_per, const gl_t *prc = nullptr,
+// Keccak digests of row-major rows (stage-level operator)
+void hash_rows(hipStream_t st, const gl_t *rows, size_t n_rows, uint32_t row_len, dig_t *dig);
+// FRI step leaves: vals [cosets][2][npc] (ext coordinates), leaf = 2^arity_bits ext values; dig [cosets][npc >> arity_bits]
+void hash_fri_leaves(hipStream_t st, const gl_t *vals, uint32_t lg_npc, uint32_t cosets, uint32_t arity_bits,
+                     dig_t *dig, const gl_t *prc = nullptr);
+// every tree level above lvl ([cosets][m]; level l + 1 = [cosets][m >> (l + 1)] stored right behind level l, node k of a coset =
+// H(node k, node k + m >> (l + 1)) of the level below) down to cap_per nodes per coset, by the schedule of treeplan.hpp.
+// host_mirror (optional, page-locked, [cosets][cap_per]): returns true when the cap level was also written there
+bool tree_levels(hipStream_t st, dig_t *lvl, uint32_t cosets, uint32_t m, uint32_t cap_per, const gl_t *prc = nullptr,
                  dig_t *host_mirror = nullptr);
 
 // ---- plonk.hip ----

@@ -14,12 +14,19 @@
 // permuted on the host (cap[2*bitrev3(r) + k] for cap_height 4).
 // Integer-ALU bound (Keccak-f ~ 8k 32-bit ops per 136 B), not HBM bound.
 #include "internal.hpp"
+#include "treeplan.hpp"
 
 namespace p2 {
 
 // ---- PoseidonHash (hasher 1): Poseidon-Goldilocks, width 12, 8 full + 22 partial rounds, x^7 -----------------
 // plonky2 0.2.2 hash/poseidon.rs; the permutation is poseidon.hpp's poseidon_permute_dev (one lane owns one sponge, like
 // the Keccak path; the partial rounds' linear layers three at a time).
+// a HashOut: the first four state words
+__device__ __forceinline__ dig_t poseidon_digest(const gl_t *st) {
+  dig_t d;
+  d.w[0] = st[0]; d.w[1] = st[1]; d.w[2] = st[2]; d.w[3] = st[3];
+  return d;
+}
 // hash_n_to_m_no_pad: overwrite-mode sponge, 8 elements per permutation, first 4 words out
 template <class F>
 __device__ __forceinline__ dig_t poseidon_sponge(uint32_t nwords, F get, const gl_t *prc) {
@@ -32,22 +39,13 @@ __device__ __forceinline__ dig_t poseidon_sponge(uint32_t nwords, F get, const g
       if (off + w < nwords) st[w] = get(off + w);
     poseidon_permute_dev(st, prc);
   }
-  dig_t d;
-  d.w[0] = st[0]; d.w[1] = st[1]; d.w[2] = st[2]; d.w[3] = st[3];
-  return d;
+  return poseidon_digest(st);
 }
 // hash/hashing.rs compress
 __device__ __forceinline__ dig_t poseidon_two_to_one(const dig_t &l, const dig_t &r, const gl_t *prc) {
   gl_t st[12] = {l.w[0], l.w[1], l.w[2], l.w[3], r.w[0], r.w[1], r.w[2], r.w[3], 0, 0, 0, 0};
   poseidon_permute_dev(st, prc);
-  dig_t d;
-  d.w[0] = st[0]; d.w[1] = st[1]; d.w[2] = st[2]; d.w[3] = st[3];
-  return d;
-}
-template <int H>
-__device__ __forceinline__ dig_t node_hash(const dig_t &l, const dig_t &r, const gl_t *prc) {
-  if constexpr (H == 1) return poseidon_two_to_one(l, r, prc);
-  else return keccak_two_to_one(l, r);
+  return poseidon_digest(st);
 }
 
 template <bool PREFETCH = true, class F>
@@ -97,41 +95,17 @@ __device__ __forceinline__ dig_t sponge_hash(uint32_t nwords, F get) {
 // hash_or_noop: rows of <= 3 elements (Keccak: 25 bytes) / <= 4 elements (Poseidon: a HashOut) are copied
 template <int H = 0, bool PREFETCH = true, class F>
 __device__ __forceinline__ dig_t hash_or_noop(uint32_t nwords, F get, const gl_t *prc = nullptr) {
-  if constexpr (H == 1) {
-    if (nwords <= 4) {
-      dig_t d;
-      d.w[0] = nwords > 0 ? get(0) : 0;
-      d.w[1] = nwords > 1 ? get(1) : 0;
-      d.w[2] = nwords > 2 ? get(2) : 0;
-      d.w[3] = nwords > 3 ? get(3) : 0;
-      return d;
-    }
-    return poseidon_sponge(nwords, get, prc);
-  }
-  if (nwords * 8 <= 25) {
+  constexpr uint32_t COPIED = H == 1 ? 4 : 3;
+  if (H == 1 ? nwords <= 4 : nwords * 8 <= 25) {
     dig_t d;
-    d.w[0] = nwords > 0 ? get(0) : 0;
-    d.w[1] = nwords > 1 ? get(1) : 0;
-    d.w[2] = nwords > 2 ? get(2) : 0;
-    d.w[3] = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) d.w[j] = j < COPIED && j < nwords ? get(j) : 0;
     return d;
   }
-  return sponge_hash<PREFETCH>(nwords, get);
+  if constexpr (H == 1) return poseidon_sponge(nwords, get, prc);
+  else return sponge_hash<PREFETCH>(nwords, get);
 }
 
-#ifndef P2_LEAF_WAVES
-#define P2_LEAF_WAVES 1
-#endif
-// The variant with unmaterialised columns absorbs without the prefetch array (most of its words are computed, not
-// loaded): 97 VGPRs, 4 waves per SIMD, no scratch.  Measured at 2^20 rows (wires tree, 154 virtual columns): 1.64 ms
-// either way with 4 waves (with the prefetch: 128 VGPRs + 20 B of scratch), 1.73 ms unbounded (131 VGPRs, 3 waves),
-// 1.64 ms at 5 waves (96 VGPRs + 12 B of scratch) -- the kernel sits at the issue ceiling, not at a latency.
-#ifndef P2_LEAFV_WAVES
-#define P2_LEAFV_WAVES 4
-#endif
-#ifndef P2_LEAFV_PREFETCH
-#define P2_LEAFV_PREFETCH 0
-#endif
 // value of column i on this lane's LDE row: read from memory, or -- for a virtual column (VirtCols) -- the
 // product of the column's scalar with the unit column's LDE value Lk of the row.  The branch is wave-uniform
 // (class and scalar come through scalar loads); gl_mul returns the canonical value the fill kernel would have
@@ -143,20 +117,35 @@ __device__ __forceinline__ gl_t virt_get(const VirtCols &v, uint32_t i, gl_t Lk,
   }
   return base[(size_t)i * n];
 }
+// Row k of coset c of an LDE batch ([coset][col][2^d]) as the leaf hashes read it: row(i) = the value of column i
+template <bool V>
+struct LeafRow {
+  const size_t &n;  // the kernel's own n, by reference like base's other readers: with a copy hipcc folds the kernel's uses of n differently
+  const gl_t *base;
+  const VirtCols &v;
+  gl_t Lk = 0;  // the unit column's LDE value of this row (V only)
+  __device__ __forceinline__ LeafRow(const gl_t *lde, uint32_t cols, const size_t &n_, uint32_t c, size_t k, const VirtCols &v_)
+      : n(n_), base(lde + (size_t)c * cols * n + k), v(v_) {
+    if constexpr (V) Lk = v.basis ? v.basis[(size_t)(v.coset_first + c * v.coset_stride) * n + k] : (gl_t)0;
+  }
+  __device__ __forceinline__ gl_t operator()(uint32_t i) const {
+    if constexpr (V) return virt_get(v, i, Lk, base, n);
+    else return base[(size_t)i * n];
+  }
+};
+// The variant with unmaterialised columns is bounded to 4 waves per SIMD and absorbs without the prefetch array (most of its
+// words are computed, not loaded): 97 VGPRs, no scratch.  Measured at 2^20 rows (wires tree, 154 virtual columns): 1.64 ms
+// either way with 4 waves (with the prefetch: 128 VGPRs + 20 B of scratch), 1.73 ms unbounded (131 VGPRs, 3 waves),
+// 1.64 ms at 5 waves (96 VGPRs + 12 B of scratch) -- the kernel sits at the issue ceiling, not at a latency.
 template <int H, bool V>
-__global__ __launch_bounds__(256, V ? P2_LEAFV_WAVES : P2_LEAF_WAVES) void hash_lde_leaves_kernel(const gl_t *__restrict__ lde, uint32_t cols, uint32_t d,
+__global__ __launch_bounds__(256, V ? 4 : 1) void hash_lde_leaves_kernel(const gl_t *__restrict__ lde, uint32_t cols, uint32_t d,
                                                               dig_t *__restrict__ dig, const gl_t *__restrict__ prc, const VirtCols v) {
   const size_t n = (size_t)1 << d;
   const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t c = blockIdx.y;
   if (k >= n) return;
-  const gl_t *base = lde + (size_t)c * cols * n + k;
-  if constexpr (V) {
-    const gl_t Lk = v.basis ? v.basis[(size_t)(v.coset_first + c * v.coset_stride) * n + k] : (gl_t)0;
-    dig[(size_t)c * n + k] = hash_or_noop<H, P2_LEAFV_PREFETCH != 0>(cols, [&](uint32_t i) { return virt_get(v, i, Lk, base, n); }, prc);
-  } else {
-    dig[(size_t)c * n + k] = hash_or_noop<H>(cols, [&](uint32_t i) { return base[(size_t)i * n]; }, prc);
-  }
+  const LeafRow<V> row(lde, cols, n, c, k, v);
+  dig[(size_t)c * n + k] = hash_or_noop<H, !V>(cols, row, prc);
 }
 
 // ---- Keccak leaf hashing with the sponge state in fixed registers (keccak.hpp P2_KF_*) ----------------------------------
@@ -256,13 +245,7 @@ __global__ __launch_bounds__(256) P2_KF_KERNEL_ATTR void hash_lde_leaves_kf_kern
   const size_t k = LV ? (size_t)blockIdx.x * 64 + t + (size_t)g * (n >> 2) : (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t c = blockIdx.y;
   if (!LV && k >= n) return;
-  const gl_t *base = lde + (size_t)c * cols * n + k;
-  gl_t Lk = 0;
-  if constexpr (V) Lk = v.basis ? v.basis[(size_t)(v.coset_first + c * v.coset_stride) * n + k] : (gl_t)0;
-  auto get = [&](uint32_t i) -> gl_t {
-    if constexpr (V) return virt_get(v, i, Lk, base, n);
-    else return base[(size_t)i * n];
-  };
+  const LeafRow<V> row(lde, cols, n, c, k, v);
   kf_zero();
   // every word of the plain variant is a load: software pipeline -- the 17 loads of block b + 1 are issued before the permutation
   // of block b and land under its 4 309 instructions (the array lives in hipcc's registers across the asm block; kf_check.py
@@ -273,11 +256,7 @@ __global__ __launch_bounds__(256) P2_KF_KERNEL_ATTR void hash_lde_leaves_kf_kern
     if constexpr (!V) {
       const uint32_t rem = cols - off;
 #pragma unroll
-#ifdef P2_KF_NOLOAD  /* timing experiment only (scratch/): what the kernel costs without its memory traffic */
-      for (int w = 0; w < 17; w++) x[w] = (uint32_t)w < rem ? (uint64_t)(k + off + w) : ((uint32_t)w == rem ? (uint64_t)1 : (uint64_t)0);
-#else
-      for (int w = 0; w < 17; w++) x[w] = (uint32_t)w < rem ? base[(size_t)(off + w) * n] : ((uint32_t)w == rem ? (uint64_t)1 : (uint64_t)0);
-#endif
+      for (int w = 0; w < 17; w++) x[w] = (uint32_t)w < rem ? row(off + w) : ((uint32_t)w == rem ? (uint64_t)1 : (uint64_t)0);
     }
   };
   load_block(0);
@@ -301,7 +280,7 @@ __global__ __launch_bounds__(256) P2_KF_KERNEL_ATTR void hash_lde_leaves_kf_kern
         off += 17;
         if (!complete) load_block(off);
       } else {
-        kf_absorb<true>(off, rem, get);
+        kf_absorb<true>(off, rem, row);
         off += 17;
       }
     }
@@ -448,14 +427,8 @@ __global__ __launch_bounds__(256) P2_KF_KERNEL_ATTR void hash_lde_absorb_kf_kern
   const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t c = blockIdx.y;
   if (k >= n) return;
-  const gl_t *base = lde + (size_t)c * cols * n + k;
+  const LeafRow<V> row(lde, cols, n, c, k, v);
   uint64_t *sp = state + (size_t)c * 25 * n + k;
-  gl_t Lk = 0;
-  if constexpr (V) Lk = v.basis ? v.basis[(size_t)(v.coset_first + c * v.coset_stride) * n + k] : (gl_t)0;
-  auto get = [&](uint32_t i) -> gl_t {
-    if constexpr (V) return virt_get(v, i, Lk, base, n);
-    else return base[(size_t)i * n];
-  };
   if (first) kf_zero();
   else
     static_for<0, 25>([&](auto ic) {
@@ -467,7 +440,7 @@ __global__ __launch_bounds__(256) P2_KF_KERNEL_ATTR void hash_lde_absorb_kf_kern
   const uint32_t steps = nblk + (last ? 1u : 0u);
   for (uint32_t b = 0; b < steps; b++) {
     const uint32_t off = 17 * (blk0 + b);
-    kf_absorb<true>(off, b < nblk ? 17u : cols - off, get);  // (groups of 6: this kernel also holds the state pointers)
+    kf_absorb<true>(off, b < nblk ? 17u : cols - off, row);  // (groups of 6: this kernel also holds the state pointers)
     P2_KECCAK_FIXED_PERMUTE();
   }
   if (last) {
@@ -495,28 +468,23 @@ __global__ __launch_bounds__(256) void hash_lde_absorb_kernel(const gl_t *__rest
   const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t c = blockIdx.y;
   if (k >= n) return;
-  const gl_t *base = lde + (size_t)c * cols * n + k;
+  const LeafRow<V> row(lde, cols, n, c, k, v);
   uint64_t *sp = state + (size_t)c * 25 * n + k;
-  gl_t Lk = 0;
-  if constexpr (V) Lk = v.basis ? v.basis[(size_t)(v.coset_first + c * v.coset_stride) * n + k] : (gl_t)0;
-  auto get = [&](uint32_t i) -> gl_t {
-    if constexpr (V) return virt_get(v, i, Lk, base, n);
-    else return base[(size_t)i * n];
-  };
   uint64_t st[25];
 #pragma unroll
   for (int i = 0; i < 25; i++) st[i] = first ? 0 : sp[(size_t)i * n];
   for (uint32_t b = 0; b < nblk; b++) {
     const uint32_t i0 = 17 * (blk0 + b);
 #pragma unroll
-    for (int w = 0; w < 17; w++) st[w] ^= get(i0 + w);
+    for (int w = 0; w < 17; w++) st[w] ^= row(i0 + w);
     keccak_f1600(st);
   }
   if (last) {
+    // (the last block as in sponge_hash, spelled out in both: behind a shared helper hipcc shapes the 17 conditional words differently)
     const uint32_t off = 17 * (blk0 + nblk), rem = cols - off;  // rem < 17
 #pragma unroll
     for (int w = 0; w < 17; w++) {
-      if ((uint32_t)w < rem) st[w] ^= get(off + w);
+      if ((uint32_t)w < rem) st[w] ^= row(off + w);
       if ((uint32_t)w == rem) st[w] ^= 0x01ULL;
     }
     st[16] ^= 0x8000000000000000ULL;
@@ -576,6 +544,8 @@ __global__ __launch_bounds__(256) void hash_fri_leaves_coop_poseidon_kernel(cons
   if (i < 4) dig[(size_t)r * per + kl].w[i] = x;
 }
 
+// one tree level, one lane per node.  <1> = PoseidonHash, the only instantiation: every Keccak level the schedule (treeplan.hpp)
+// gives to this form has whole 256-lane blocks and goes to merkle_level_kf_kernel.
 template <int H>
 __global__ __launch_bounds__(256) void merkle_level_kernel(const dig_t *__restrict__ in, dig_t *__restrict__ out,
                                                            uint32_t m, const gl_t *__restrict__ prc) {
@@ -584,7 +554,8 @@ __global__ __launch_bounds__(256) void merkle_level_kernel(const dig_t *__restri
   const uint32_t c = blockIdx.y;
   if (k >= half) return;
   const dig_t l = in[(size_t)c * m + k], r = in[(size_t)c * m + k + half];
-  out[(size_t)c * half + k] = node_hash<H>(l, r, prc);
+  static_assert(H == 1, "Keccak levels: merkle_level_kf_kernel");
+  out[(size_t)c * half + k] = poseidon_two_to_one(l, r, prc);
 }
 
 // merkle_coop_kernel for PoseidonHash: twelve lanes per permutation (poseidon_permute_coop), four per wave, sixteen per block of
@@ -618,133 +589,90 @@ __global__ __launch_bounds__(256) void merkle_coop_poseidon_kernel(dig_t *lvl, u
     cnt = half;
   }
 }
-// levels with at most this many nodes (all cosets together) go to merkle_tail
-size_t merkle_tail_from(const gl_t *prc) {
-  if (prc) return 16384;      // Poseidon: twelve lanes per node pay up to four waves per SIMD (~27 vs ~75 us per level)
-  return (size_t)1024 * 64;   // Keccak: from one wave per SIMD
-}
-bool merkle_tail(hipStream_t st, dig_t *lvl, uint32_t cosets, uint32_t m, uint32_t cap_per, const gl_t *prc, dig_t *host_mirror) {
-  if (m <= cap_per) return false;
-  if (prc) {
-    while (m > cap_per) {
-      if ((size_t)cosets * (m >> 1) > 16384) {
-        merkle_level(st, lvl, lvl + (size_t)cosets * m, cosets, m, prc);
-        lvl += (size_t)cosets * m;
-        m >>= 1;
-        continue;
-      }
-      uint32_t levels = 0;
-      while (levels < 5 && (m >> levels) > cap_per) levels++;
-      {
-        ProfScope ps("merkle_coop_poseidon_kernel", 96.0 * cosets * (double)(m - (m >> levels)));
-        hipLaunchKernelGGL(merkle_coop_poseidon_kernel, dim3(cosets * (m >> levels)), dim3(256), 0, st, lvl, cosets, m, levels, prc);
-      }
-      for (uint32_t q = 0; q < levels; q++) {
-        lvl += (size_t)cosets * m;
-        m >>= 1;
-      }
+
+// Builds the levels above `lvl` ([cosets][m] digests, the levels after it contiguous behind it: [cosets][m/2], ...) down to
+// cap_per nodes per coset, one launch per step of treeplan.hpp's schedule.  host_mirror (optional, page-locked,
+// [cosets][cap_per]): returns true when the cap level was also written there.
+bool tree_levels(hipStream_t st, dig_t *lvl, uint32_t cosets, uint32_t m, uint32_t cap_per, const gl_t *prc, dig_t *host_mirror) {
+  const TreePlan plan = tree_plan(prc ? 1 : 0, cosets, m, cap_per);
+  for (uint32_t i = 0; i < plan.count; i++) {
+    const TreeStep &s = plan.step[i];
+    const dim3 grid(s.grid_x, s.grid_y), block(s.block);
+    dig_t *out = lvl + (size_t)cosets * s.m;
+    ProfScope ps(tree_kernel_name(s.kernel), s.bytes(cosets));
+    switch (s.kernel) {
+      case TreeKernel::LevelPoseidon: hipLaunchKernelGGL(merkle_level_kernel<1>, grid, block, 0, st, lvl, out, s.m, prc); break;
+      case TreeKernel::LevelKfMany: hipLaunchKernelGGL(merkle_level_kf_kernel<1>, grid, block, 0, st, lvl, out, s.m); break;
+      case TreeKernel::LevelKfLone: hipLaunchKernelGGL(merkle_level_kf_kernel<0>, grid, block, 0, st, lvl, out, s.m); break;
+      case TreeKernel::LevelsKf: hipLaunchKernelGGL(merkle_levels_kf_kernel, grid, block, 0, st, lvl, cosets, s.m, s.levels); break;
+      case TreeKernel::CoopKeccak: hipLaunchKernelGGL(merkle_coop_kernel, grid, block, 0, st, lvl, cosets, s.m, s.levels, host_mirror, cap_per); break;
+      case TreeKernel::CoopPoseidon: hipLaunchKernelGGL(merkle_coop_poseidon_kernel, grid, block, 0, st, lvl, cosets, s.m, s.levels, prc); break;
     }
-    return false;
+    for (uint32_t q = 0; q < s.levels; q++) lvl += (size_t)cosets * (s.m >> q);
   }
-  {
-    // Keccak: a level with more than 2 048 nodes (two per wave: one wave per SIMD on the chip) is still cheaper one lane
-    // per node (7.5 us); below that the 25-lane form (3.5-5 us per level), four levels per launch
-    bool mirrored = false;
-    while (m > cap_per) {
-      if ((size_t)cosets * (m >> 1) > 2048 && (m >> 1) >= 256) {
-        // single-lane levels; the latency-bound ones (<= one wave per SIMD on the chip) up to three per launch
-        uint32_t lv = 1;
-        if ((size_t)cosets * (m >> 1) <= (size_t)1024 * 64)
-          while (lv < 3 && (size_t)cosets * (m >> (lv + 1)) > 2048 && (m >> (lv + 1)) >= 256 && (m >> (lv + 1)) >= cap_per) lv++;
-        if (lv == 1) {
-          merkle_level(st, lvl, lvl + (size_t)cosets * m, cosets, m, prc);
-        } else {
-          ProfScope ps("merkle_levels_kf_kernel", 96.0 * cosets * (double)(m - (m >> lv)));
-          hipLaunchKernelGGL(merkle_levels_kf_kernel, dim3(cosets * ((m >> lv) >> 6)), dim3(256), 0, st, lvl, cosets, m, lv);
-        }
-        for (uint32_t i = 0; i < lv; i++) {
-          lvl += (size_t)cosets * m;
-          m >>= 1;
-        }
-        continue;
-      }
-      uint32_t levels = 0;
-      while (levels < 4 && (m >> levels) > cap_per) levels++;
-      {
-        ProfScope ps("merkle_coop_kernel", 96.0 * cosets * (double)(m - (m >> levels)));
-        hipLaunchKernelGGL(merkle_coop_kernel, dim3(cosets * (m >> levels)), dim3(256), 0, st, lvl, cosets, m, levels, host_mirror, cap_per);
-        if (host_mirror != nullptr && (m >> levels) == cap_per) mirrored = true;  // (a cap this wide ends on a plain level launch)
-      }
-      for (uint32_t i = 0; i < levels; i++) {
-        lvl += (size_t)cosets * m;
-        m >>= 1;
-      }
-    }
-    return mirrored;
-  }
+  return host_mirror != nullptr && plan.cap_from_coop_keccak();
 }
 
-// P2GPU_LEAF_LEVELS=0: the leaf kernels leave every tree level to merkle_level / merkle_tail (A/B measurements)
+// P2GPU_LEAF_LEVELS=0: the leaf kernels leave every tree level to tree_levels (A/B measurements)
 static bool leaf_levels_on() {
   static const bool on = env_flag("P2GPU_LEAF_LEVELS", true);
   return on;
 }
+// does the batch have columns that exist only as (class, scalar)?  If not the kernels get an empty VirtCols.
+static bool has_virtual(const VirtCols *virt, uint32_t cols) { return virt && virt->cls && virt->first < cols; }
+
+// A leaf kernel under the name rocprofv3 shows for it (<0> Keccak, <1> Poseidon; the bench line and profiles/ use the same
+// spelling): the two forms differ in their arguments, `levels` = tree levels a launch builds above the leaf digests.
+struct LeafVariant {
+  const char *name;
+  void (*plain)(const gl_t *, uint32_t, uint32_t, dig_t *, const gl_t *, VirtCols);
+  void (*fixed)(const gl_t *, uint32_t, uint32_t, dig_t *, dig_t *, dig_t *, VirtCols);
+  uint32_t levels;
+};
+#define P2_LEAF_PLAIN(...) LeafVariant{#__VA_ARGS__, __VA_ARGS__, nullptr, 0}
+#define P2_LEAF_FIXED(LV, ...) LeafVariant{#__VA_ARGS__, nullptr, __VA_ARGS__, LV}
 // Returns how many tree levels above the leaf digests the launch has ALSO built (0 or 2): lvl1 / lvl2 = storage of the levels with
 // n/2 and n/4 nodes per coset ([cosets][n/2], [cosets][n/4]; nullptr: leaves only).
 uint32_t hash_lde_leaves(hipStream_t st, const gl_t *lde, uint32_t cols, uint32_t d, uint32_t cosets, dig_t *dig, const gl_t *prc,
                          const VirtCols *virt, dig_t *lvl1, dig_t *lvl2) {
   size_t n = (size_t)1 << d;
   uint32_t threads = n >= 256 ? 256 : 64;
-  // Keccak, a hashed leaf (more than 3 elements) and full 256-lane blocks: the fixed-register sponge (profile names = the
-  // symbols rocprofv3 shows)
+  // Keccak, a hashed leaf (more than 3 elements) and full 256-lane blocks: the fixed-register sponge
   const bool kf = !prc && cols * 8 > 25 && n >= 256;
-  // ... only where it measured faster (profiles/r05_tree_levels.md, 2^20 rows, lone proof): the wires tree of a witness with
-  // unmaterialised columns (14 permutations per leaf; grouped-load sponge): 1603 us against 1545 + 57 + 31 for leaves + two level
-  // launches.  Not the 2-block leaves of Z / partial products (302 vs 300) or the 1-block leaves of the quotient (204 vs 185:
-  // after one permutation half, then three quarters of a block's waves have nothing left to do), and not a dense wires tree,
-  // whose prefetching sponge <false, 0> cannot spare the registers (1615 vs 1483 + 59 + 32 through the grouped-load form)
-  const bool virt_on = virt && virt->cls && virt->first < cols;
+  // ... which also builds two levels only where it measured faster (profiles/r05_tree_levels.md, 2^20 rows, lone proof): the wires
+  // tree of a witness with unmaterialised columns (14 permutations per leaf; grouped-load sponge): 1603 us against 1545 + 57 + 31
+  // for leaves + two level launches.  Not the 2-block leaves of Z / partial products (302 vs 300) or the 1-block leaves of the
+  // quotient (204 vs 185: after one permutation half, then three quarters of a block's waves have nothing left to do), and not
+  // a dense wires tree, whose prefetching sponge <false, 0> cannot spare the registers (1615 vs 1483 + 59 + 32 through the
+  // grouped-load form)
+  const bool virt_on = has_virtual(virt, cols);  // the wires of a proof with unmaterialised columns (same digests)
   const bool lv2 = kf && virt_on && lvl1 != nullptr && lvl2 != nullptr && cols > 3 * 17 && leaf_levels_on();
-  const double node_bytes = lv2 ? 96.0 * cosets * (double)(n / 2 + n / 4) : 0.0;
+  const LeafVariant k = prc   ? (virt_on ? P2_LEAF_PLAIN(hash_lde_leaves_kernel<1, true>) : P2_LEAF_PLAIN(hash_lde_leaves_kernel<1, false>))
+                        : !kf ? (virt_on ? P2_LEAF_PLAIN(hash_lde_leaves_kernel<0, true>) : P2_LEAF_PLAIN(hash_lde_leaves_kernel<0, false>))
+                        : !virt_on ? P2_LEAF_FIXED(0, hash_lde_leaves_kf_kernel<false, 0>)
+                        : lv2      ? P2_LEAF_FIXED(2, hash_lde_leaves_kf_kernel<true, 2>)
+                                   : P2_LEAF_FIXED(0, hash_lde_leaves_kf_kernel<true, 0>);
+  const double node_bytes = k.levels ? 96.0 * cosets * (double)(n / 2 + n / 4) : 0.0;
   const dim3 grid((uint32_t)((n + threads - 1) / threads), cosets);
-  if (virt_on) {  // the wires of a proof with unmaterialised columns (same digests)
-    ProfScope ps(prc ? "hash_lde_leaves_kernel<1, true>" : (kf ? (lv2 ? "hash_lde_leaves_kf_kernel<true, 2>" : "hash_lde_leaves_kf_kernel<true, 0>") : "hash_lde_leaves_kernel<0, true>"),
-                 (8.0 * cols + 32.0) * cosets * (double)n + node_bytes);
-    if (prc) hipLaunchKernelGGL((hash_lde_leaves_kernel<1, true>), grid, dim3(threads), 0, st, lde, cols, d, dig, prc, *virt);
-    else if (lv2) hipLaunchKernelGGL((hash_lde_leaves_kf_kernel<true, 2>), grid, dim3(threads), 0, st, lde, cols, d, dig, lvl1, lvl2, *virt);
-    else if (kf) hipLaunchKernelGGL((hash_lde_leaves_kf_kernel<true, 0>), grid, dim3(threads), 0, st, lde, cols, d, dig, lvl1, lvl2, *virt);
-    else hipLaunchKernelGGL((hash_lde_leaves_kernel<0, true>), grid, dim3(threads), 0, st, lde, cols, d, dig, prc, *virt);
-    return lv2 ? 2u : 0u;
-  }
-  // same spelling as rocprofv3's demangled names (<0> Keccak, <1> Poseidon), so the bench line and profiles/ agree
-  ProfScope ps(prc ? "hash_lde_leaves_kernel<1, false>" : (kf ? "hash_lde_leaves_kf_kernel<false, 0>" : "hash_lde_leaves_kernel<0, false>"),
-               (8.0 * cols + 32.0) * cosets * (double)n + node_bytes);
-  if (prc) hipLaunchKernelGGL((hash_lde_leaves_kernel<1, false>), grid, dim3(threads), 0, st, lde, cols, d, dig, prc, VirtCols());
-  else if (kf) hipLaunchKernelGGL((hash_lde_leaves_kf_kernel<false, 0>), grid, dim3(threads), 0, st, lde, cols, d, dig, lvl1, lvl2, VirtCols());
-  else hipLaunchKernelGGL((hash_lde_leaves_kernel<0, false>), grid, dim3(threads), 0, st, lde, cols, d, dig, prc, VirtCols());
-  return lv2 ? 2u : 0u;
+  const VirtCols vc = virt_on ? *virt : VirtCols();
+  ProfScope ps(k.name, (8.0 * cols + 32.0) * cosets * (double)n + node_bytes);
+  if (k.fixed) hipLaunchKernelGGL(k.fixed, grid, dim3(threads), 0, st, lde, cols, d, dig, lvl1, lvl2, vc);
+  else hipLaunchKernelGGL(k.plain, grid, dim3(threads), 0, st, lde, cols, d, dig, prc, vc);
+  return k.levels;
 }
+#undef P2_LEAF_PLAIN
+#undef P2_LEAF_FIXED
 void hash_lde_absorb(hipStream_t st, const gl_t *lde, uint32_t cols, uint32_t d, uint32_t cosets, uint32_t blk0,
                      uint32_t nblk, bool first, bool last, uint64_t *state, dig_t *dig, const VirtCols *virt) {
   size_t n = (size_t)1 << d;
   uint32_t threads = n >= 256 ? 256 : 64;
+  const bool virt_on = has_virtual(virt, cols), kf = n >= 256;  // (full 256-lane blocks: the fixed-register sponge)
   ProfScope ps("hash_lde_absorb_kernel", (8.0 * 17 * nblk + (first ? 0 : 200) + (last ? 32 + 8.0 * (cols - 17 * (blk0 + nblk)) : 200)) *
                                              cosets * (double)n);
-  if (n >= 256) {
-    if (virt && virt->cls && virt->first < cols)
-      hipLaunchKernelGGL(hash_lde_absorb_kf_kernel<true>, dim3((n + threads - 1) / threads, cosets), dim3(threads), 0, st, lde, cols,
-                         d, blk0, nblk, first ? 1 : 0, last ? 1 : 0, state, dig, *virt);
-    else
-      hipLaunchKernelGGL(hash_lde_absorb_kf_kernel<false>, dim3((n + threads - 1) / threads, cosets), dim3(threads), 0, st, lde, cols,
-                         d, blk0, nblk, first ? 1 : 0, last ? 1 : 0, state, dig, VirtCols());
-    return;
-  }
-  if (virt && virt->cls && virt->first < cols)
-    hipLaunchKernelGGL(hash_lde_absorb_kernel<true>, dim3((n + threads - 1) / threads, cosets), dim3(threads), 0, st, lde, cols,
-                       d, blk0, nblk, first ? 1 : 0, last ? 1 : 0, state, dig, *virt);
-  else
-    hipLaunchKernelGGL(hash_lde_absorb_kernel<false>, dim3((n + threads - 1) / threads, cosets), dim3(threads), 0, st, lde, cols,
-                       d, blk0, nblk, first ? 1 : 0, last ? 1 : 0, state, dig, VirtCols());
+  hipLaunchKernelGGL(kf ? (virt_on ? hash_lde_absorb_kf_kernel<true> : hash_lde_absorb_kf_kernel<false>)
+                        : (virt_on ? hash_lde_absorb_kernel<true> : hash_lde_absorb_kernel<false>),
+                     dim3((n + threads - 1) / threads, cosets), dim3(threads), 0, st, lde, cols, d, blk0, nblk, first ? 1 : 0, last ? 1 : 0,
+                     state, dig, virt_on ? *virt : VirtCols());
 }
 void hash_rows(hipStream_t st, const gl_t *rows, size_t n_rows, uint32_t row_len, dig_t *dig) {
   hipLaunchKernelGGL(hash_rows_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, st, rows, n_rows, row_len, dig);
@@ -755,23 +683,9 @@ void hash_fri_leaves(hipStream_t st, const gl_t *vals, uint32_t lg_npc, uint32_t
   ProfScope ps(prc ? "hash_fri_leaves_kernel<1>" : "hash_fri_leaves_kernel<0>", (16.0 * (1u << ab) + 32.0) * cosets * (double)per);
   if (prc && (2u << ab) >= 8 && (size_t)cosets * per <= 4096)  // latency-bound: 4 permutations of ~12 us instead of ~75
     hipLaunchKernelGGL(hash_fri_leaves_coop_poseidon_kernel, dim3((cosets * per + 15) / 16), dim3(256), 0, st, vals, lg_npc, ab, cosets, dig, prc);
-  else if (prc) hipLaunchKernelGGL(hash_fri_leaves_kernel<1>, dim3((per + threads - 1) / threads, cosets), dim3(threads), 0, st, vals, lg_npc, ab, dig, prc);
-  else hipLaunchKernelGGL(hash_fri_leaves_kernel<0>, dim3((per + threads - 1) / threads, cosets), dim3(threads), 0, st, vals, lg_npc, ab, dig, prc);
-}
-void merkle_level(hipStream_t st, const dig_t *in, dig_t *out, uint32_t cosets, uint32_t m, const gl_t *prc) {
-  uint32_t half = m >> 1;
-  uint32_t threads = half >= 256 ? 256 : 64;
-  const bool kf_big = !prc && (size_t)half * cosets >= (size_t)2 * 1024 * 64;
-  const bool kf_small = !prc && !kf_big && threads == 256;
-  ProfScope ps(prc ? "merkle_level_kernel<1>" : (kf_big ? "merkle_level_kf_kernel<1>" : (kf_small ? "merkle_level_kf_kernel<0>" : "merkle_level_kernel<0>")),
-               96.0 * cosets * (double)half);
-  if (prc) hipLaunchKernelGGL(merkle_level_kernel<1>, dim3((half + threads - 1) / threads, cosets), dim3(threads), 0, st, in, out, m, prc);
-  // >= 2 waves per SIMD on the whole chip (2 * 1024 SIMDs * 64 lanes): throughput placement; below: a SIMD sees a lone wave
-  else if ((size_t)half * cosets >= (size_t)2 * 1024 * 64)
-    hipLaunchKernelGGL(merkle_level_kf_kernel<1>, dim3((half + threads - 1) / threads, cosets), dim3(threads), 0, st, in, out, m);
-  else if (threads == 256)
-    hipLaunchKernelGGL(merkle_level_kf_kernel<0>, dim3((half + threads - 1) / threads, cosets), dim3(threads), 0, st, in, out, m);
-  else hipLaunchKernelGGL(merkle_level_kernel<0>, dim3((half + threads - 1) / threads, cosets), dim3(threads), 0, st, in, out, m, prc);
+  else
+    hipLaunchKernelGGL(prc ? hash_fri_leaves_kernel<1> : hash_fri_leaves_kernel<0>, dim3((per + threads - 1) / threads, cosets), dim3(threads), 0,
+                       st, vals, lg_npc, ab, dig, prc);
 }
 
 }  // namespace p2

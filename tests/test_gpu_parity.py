@@ -133,7 +133,7 @@ def test_direct_dit_passes_match_oracle(pkg, orc, gpu, d):
 def test_ab_switches_keep_every_byte(gpu):
     """The A/B switches of round 5, each in a process of its own (they are read once): P2GPU_NTT_DIRECT=0 sends every pass through
     ntt_pass_kernel (the round 1-4 path),
-    P2GPU_LEAF_LEVELS=0 leaves every tree level to merkle_level / merkle_tail instead of
+    P2GPU_LEAF_LEVELS=0 leaves every tree level to tree_levels (merkle.hip) instead of
     building the first two inside the leaf-hash launch.  Same LDE words, same proof bytes (virtual-column wires tree, plain
     Z / quotient trees, a 231-dense-column witness) as the default build."""
     import os
@@ -231,10 +231,19 @@ def test_keccak_rows_match_oracle(pkg, orc, gpu, ncols):
     assert np.array_equal(pkg.hash_rows(rows), orc.hash_rows(rows))
 
 
-@pytest.mark.parametrize("d,ncols", [(1, 4), (4, 20), (9, 5), (12, 84), (13, 3)])
-def test_commit_cap_matches_oracle(pkg, orc, gpu, d, ncols):
+@pytest.mark.parametrize("d,ncols,rate_bits,cap_height", [
+    (1, 4, 3, 4), (4, 20, 3, 4), (9, 5, 3, 4), (12, 84, 3, 4), (13, 3, 3, 4),
+    # the smallest shapes that reach each step kind and boundary of the Keccak tree schedule (csrc/treeplan.hpp; the steps are
+    # those tests/golden/tree_schedule.txt.gz lists for cosets = 2^rate_bits, nodes = 2^d, cap = 2^(cap_height - rate_bits)):
+    (15, 4, 3, 4),  # merkle_level_kf_kernel<1> (the smallest size with two waves per SIMD), 3 + 2 fused levels, 4 + 4 coop levels
+    (13, 5, 3, 4),  # 3 fused levels, a lone merkle_level_kf_kernel<0>, 4 + 4 coop levels over hashed (not copied) leaves
+    (12, 5, 1, 1),  # 2 cosets, one cap node per coset: a lone <0> level, coop over 4, 4 and 3 levels, mirrored
+    (13, 5, 3, 7),  # a cap of 16 per coset: the last coop launch has one level
+    (3, 5, 3, 6),   # the leaves are the cap: no step at all
+])
+def test_commit_cap_matches_oracle(pkg, orc, gpu, d, ncols, rate_bits, cap_height):
     v = _rand((ncols, 1 << d), d * 31 + ncols)
-    assert pkg.commit_values(v, 3, 4) == orc.commit_values(v, 3, 4)
+    assert pkg.commit_values(v, rate_bits, cap_height) == orc.commit_values(v, rate_bits, cap_height)
 
 
 @pytest.mark.parametrize("d,mix,seed", [

@@ -164,6 +164,31 @@ def test_poseidon_fused_layers_on_the_host(tmp_path):
     assert lines[-1].startswith("mismatches 0 ") and int(lines[-1].split()[-1]) <= 58
 
 
+def test_tree_schedule_is_the_recorded_one(tmp_path):
+    """Which kernel builds which level of a Merkle tree is decided by one host function (csrc/treeplan.hpp: no HIP in it, so g++
+    compiles it).  Its schedule -- per launch the profile name, grid, block, input nodes per coset, levels and profile bytes, then
+    whether the cap is mirrored to the host -- equals, byte for byte, the schedule recorded from the launch code it replaced
+    (profiles/merkle_refactor.md has the recipe; the recording is kept compressed): both hashers, 1 / 2 / 4 / 8 cosets, 2^0 .. 2^24 leaves per coset, caps of
+    1 .. 16 per coset, with and without the two levels a leaf launch builds."""
+    import subprocess
+
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "acvm-backend-plonky2_amd", "csrc", "tests", "treeplan_print.cpp")
+    exe = str(tmp_path / "treeplan_print")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-o", exe, src], check=True, timeout=300)
+    r = subprocess.run([exe], capture_output=True, timeout=300)
+    assert r.returncode == 0
+    import gzip
+
+    with gzip.open(os.path.join(GOLDEN, "tree_schedule.txt.gz"), "rb") as f:  # 11 524 lines of text, gzip -n -9
+        gold = f.read()
+    assert len(gold.splitlines()) > 10000
+    if r.stdout != gold:  # the first lines that differ, with the case they belong to
+        got, want = r.stdout.splitlines(), gold.splitlines()
+        i = next((j for j, (x, y) in enumerate(zip(got, want)) if x != y), min(len(got), len(want)))
+        case = next((ln for ln in reversed(want[:i + 1]) if ln.startswith(b"#")), b"")
+        pytest.fail(f"line {i + 1} ({case.decode()}): printed {got[i:i + 3]}, recorded {want[i:i + 3]}")
+
+
 def test_poseidon_hash_no_pad(orc):
     out = np.ones(4, dtype=np.uint64)
     orc.lib().orc_poseidon_hash_no_pad(None, 0, out.ctypes.data)
