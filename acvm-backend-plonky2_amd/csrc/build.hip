@@ -10,8 +10,6 @@
 //   3. cycles    sort the touched cells by (root, key); the successor of a cell is the next entry of its segment, the last
 //                entry's successor is the root (= the segment's first entry);
 //   4. values    sigma[col * n + row] = k_is[col'] * w^row', the identity for cells no pair names.
-#include <cstring>  // (rocprim's headers use memcpy without including it)
-#include <rocprim/rocprim.hpp>
 #include "devclasses.hpp"
 #include "prover_internal.hpp"
 
@@ -209,35 +207,14 @@ int build_device_tables(p2gpu_circuit *c, const BuildInputs &in, const CreateTra
     T = (size_t)h[3];
     if (T > list_cap) { set_err("p2gpu_circuit_build: internal error (touched cells)"); return P2GPU_E_DEVICE; }
     tr.mark("build: touched cells");
-    // classes: while a pair is left to hook, every round removes at least one root; in practice a handful of rounds.  The
-    // bounds are backstops against a defect, not part of the algorithm
-    uint32_t hc = 0;
-    for (int round = 0;; round++) {
-      if (round > (1 << 16)) { set_err("p2gpu_circuit_build: internal error (classes did not settle)"); return P2GPU_E_DEVICE; }
-      BT(hipMemsetAsync(flags, 0, 4, st), "scratch");
-      hipLaunchKernelGGL(classes::hook_kernel<CopyPairs>, dim3(grid_for(E)), dim3(TPB), 0, st, CopyPairs{copies, R}, E, parent, flags);
-      BT(hipMemcpyAsync(&hc, flags, 4, hipMemcpyDeviceToHost, st), "read flag");
-      BT(hipStreamSynchronize(st), "hook");
-      if (!hc) break;
-      for (int j = 0;; j++) {
-        if (j > 64) { set_err("p2gpu_circuit_build: internal error (compression did not settle)"); return P2GPU_E_DEVICE; }
-        BT(hipMemsetAsync(flags, 0, 4, st), "scratch");
-        hipLaunchKernelGGL(classes::jump_kernel<classes::JUMP_STEPS>, dim3(grid_for(T)), dim3(TPB), 0, st, list, T, parent, flags);
-        BT(hipMemcpyAsync(&hc, flags, 4, hipMemcpyDeviceToHost, st), "read flag");
-        BT(hipStreamSynchronize(st), "jump");
-        if (!hc) break;
-      }
-    }
+    if (int rc = classes::settle(CopyPairs{copies, R}, E, list, T, parent, flags, st, "p2gpu_circuit_build")) return rc;
     tr.mark("build: copy classes");
     // cycles
     unsigned long long *sorted = S.alloc<unsigned long long>(T);
     if (!sorted) return dev_fail("scratch (sort)", hipErrorOutOfMemory);
     hipLaunchKernelGGL(build_sort_keys_kernel, dim3(grid_for(T)), dim3(TPB), 0, st, list, T, parent, key_bits);
-    size_t tmp_bytes = 0;
-    BT(rocprim::radix_sort_keys(nullptr, tmp_bytes, list, sorted, T, 0u, 2 * key_bits, st), "sort (size)");
-    void *tmp = S.alloc<uint8_t>(tmp_bytes);
-    if (!tmp) return dev_fail("scratch (sort)", hipErrorOutOfMemory);
-    BT(rocprim::radix_sort_keys(tmp, tmp_bytes, list, sorted, T, 0u, 2 * key_bits, st), "sort");
+    const auto sort = S.radix_sort_keys(list, sorted, T, 0u, 2 * key_bits, st);
+    BT(sort.e, sort.step);
     if (trace_on()) {
       (void)hipStreamSynchronize(st);
       tr.mark("build: sort by (root, key)");

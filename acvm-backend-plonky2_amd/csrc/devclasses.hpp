@@ -9,10 +9,14 @@
 //   jump    parent[x] <- parent[parent[...]] until every touched cell points at a root.
 // Rounds of { hook, jump until settled } until no pair hooks.  Parents only ever decrease and only within a true class, so the
 // fixed point is parent[x] = the smallest key of x's class whatever order the atomics land in.  No thread ever waits for
-// another one or retries.
+// another one or retries.  settle() is that loop; Scratch holds a compilation's device memory and runs rocprim's scans and
+// sorts on a temporary it grows on demand.
 #pragma once
 #include <algorithm>
+#include <cstring>  // (rocprim's headers use memcpy without including it)
 #include <vector>
+#include <rocprim/rocprim.hpp>
+#include "circuit.hpp"
 #include "gl.hpp"
 
 namespace p2 {
@@ -84,6 +88,39 @@ __global__ void jump_kernel(const unsigned long long *list, size_t count, uint32
   if (any) *changed = 1;
 }
 
+// Rounds of { hook, jump until settled } over the touched cells list[0 .. T), T > 0, until no pair hooks; `flag` (a device
+// word) is cleared in front of every launch and read back behind it.  While a pair is left to hook, every round removes at
+// least one root; in practice a handful of rounds.  The bounds are backstops against a defect, not part of the algorithm:
+// past them the call fails, it never loops on.  `who` opens the error text.
+template <class P>
+int settle(const P &pairs, size_t num_pairs, const unsigned long long *list, size_t T, uint32_t *parent, uint32_t *flag, hipStream_t st,
+           const char *who) {
+  uint32_t hc = 0;
+  auto ok = [&](hipError_t e, const char *what) {
+    if (e == hipSuccess) return true;
+    (void)hipGetLastError();
+    set_err("%s: %s: %s", who, what, hipGetErrorString(e));
+    return false;
+  };
+  auto clear = [&] { return ok(hipMemsetAsync(flag, 0, 4, st), "scratch"); };
+  auto read = [&](const char *what) { return ok(hipMemcpyAsync(&hc, flag, 4, hipMemcpyDeviceToHost, st), "read flag") && ok(hipStreamSynchronize(st), what); };
+  for (int round = 0;; round++) {
+    if (round > (1 << 16)) { set_err("%s: internal error (classes did not settle)", who); return P2GPU_E_DEVICE; }
+    if (!clear()) return P2GPU_E_DEVICE;
+    hipLaunchKernelGGL(hook_kernel<P>, dim3(grid_for(num_pairs)), dim3(TPB), 0, st, pairs, num_pairs, parent, flag);
+    if (!read("hook")) return P2GPU_E_DEVICE;
+    if (!hc) break;
+    for (int j = 0;; j++) {
+      if (j > 64) { set_err("%s: internal error (compression did not settle)", who); return P2GPU_E_DEVICE; }
+      if (!clear()) return P2GPU_E_DEVICE;
+      hipLaunchKernelGGL(jump_kernel<JUMP_STEPS>, dim3(grid_for(T)), dim3(TPB), 0, st, list, T, parent, flag);
+      if (!read("jump")) return P2GPU_E_DEVICE;
+      if (!hc) break;
+    }
+  }
+  return P2GPU_OK;
+}
+
 // w^row from the forward twiddles tw[i] = w^i, i < n / 2:  w^(i + n/2) = -w^i
 __device__ __forceinline__ gl_t subgroup_power(const gl_t *tw, uint32_t d, uint32_t row) {
   const uint32_t half = 1u << (d - 1);
@@ -101,6 +138,8 @@ struct Scratch {
   void release() {
     for (void *p : ptrs) (void)hipFree(p);
     ptrs.clear();
+    tmp = nullptr;
+    tmp_cap = 0;
   }
   template <class T> T *alloc(size_t n) {
     void *p = nullptr;
@@ -110,6 +149,37 @@ struct Scratch {
     }
     ptrs.push_back(p);
     return (T *)p;
+  }
+  // rocprim's temporary storage, grown on demand (an outgrown one stays until release()), and the three calls that use it:
+  // size query, grow, run.  A failure comes back with the step it happened in, in the words of the sorts' error texts.
+  // Templates, so that a unit holds the kernels of the calls it makes and no others; pointer and size types as the callers
+  // have them: they name rocprim's kernels.
+  struct Result {
+    hipError_t e;
+    const char *step;
+  };
+  void *tmp = nullptr;
+  size_t tmp_cap = 0;
+  template <class Run> Result with_tmp(Run &&run) {
+    size_t bytes = 0;
+    const hipError_t e = run(nullptr, bytes);
+    if (e != hipSuccess) return {e, "sort (size)"};
+    if (bytes > tmp_cap) {
+      tmp = alloc<uint8_t>(bytes);
+      tmp_cap = tmp ? bytes : 0;
+      if (!tmp) return {hipErrorOutOfMemory, "scratch (sort)"};
+    }
+    return {run(tmp, tmp_cap), "sort"};
+  }
+  template <class T> hipError_t exclusive_scan(const T *in, T *out, size_t m, hipStream_t st) {
+    return with_tmp([&](void *t, size_t &b) { return rocprim::exclusive_scan(t, b, in, out, T(0), m, rocprim::plus<T>(), st); }).e;
+  }
+  template <class K, class N> Result radix_sort_keys(K *in, K *out, N m, unsigned bit0, unsigned bit1, hipStream_t st) {
+    return with_tmp([&](void *t, size_t &b) { return rocprim::radix_sort_keys(t, b, in, out, m, bit0, bit1, st); });
+  }
+  template <class K, class V, class N>
+  Result radix_sort_pairs(K *kin, K *kout, V *vin, V *vout, N m, unsigned bit0, unsigned bit1, hipStream_t st) {
+    return with_tmp([&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, kin, kout, vin, vout, m, bit0, bit1, st); });
   }
 };
 

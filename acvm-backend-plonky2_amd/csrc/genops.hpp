@@ -1,6 +1,6 @@
 // genops.hpp -- the closed registry of witness-generator operations: which ops a gate row holds and which columns
-// each of them reads and sets.  ONE enumerator, called by the host plan compiler (genwit.hip) and by the device one
-// (genplan.hip); the bodies that run the ops are generators.hpp's.
+// each of them reads and sets.  ONE enumerator, called by the host plan compiler (planhost.hpp) and by the device one
+// (genplan.hip); the bodies that run the ops are generators.hpp's.  Plain C++ besides P2_HD: g++ compiles it.
 #pragma once
 #include "gates.hpp"
 

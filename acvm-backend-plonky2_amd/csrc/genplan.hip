@@ -1,5 +1,5 @@
 // genplan.hip -- the witness plan compiled on the device (p2gpu_witness_plan_build): the same cell_slot words, op records and
-// level offsets as the host compiler of genwit.hip (Compiler::classes / add_op / row_ops / schedule), which stays as the
+// level offsets as the host compiler of planhost.hpp (Compiler::classes / add_op / row_ops / schedule), which stays as the
 // differential oracle (tests/test_gpu_witness_plan.py compares the exported arrays byte for byte).
 //
 // Cells are numbered as sigma is laid out, key = col << d | row.  Every phase restates the host rule it replaces:
@@ -15,9 +15,9 @@
 //                cells an op lists as inputs -- those with a slot when the op is created -- are those with a slot in the end.
 //   4. levels    one persistent workgroup; see plan_schedule_kernel.
 //   5. unreached one pass over the routed cells, three atomicMin words, the host's priority.
-// Scratch (DESIGN 6b states the bound) lives in the caller's classes::Scratch and is gone when the plan is attached.
-#include <cstring>  // (rocprim's headers use memcpy without including it)
-#include <rocprim/rocprim.hpp>
+// The phases are PlanCtx's decode .. unreached below.  Scratch (DESIGN 6b states the bound) lives in the
+// caller's classes::Scratch and is gone when the plan is attached.
+#include "devclasses.hpp"
 #include "genplan.hpp"
 
 using namespace p2;
@@ -425,55 +425,51 @@ __global__ void plan_unreached_kernel(const uint32_t *cell_slot, size_t tot, con
   }
 }
 
-}  // namespace
+// what the phases of one compilation share: the sizes, the stream, the counters and the scratch pointers (all inside S)
+struct PlanCtx {
+  p2gpu_circuit *c;
+  classes::Scratch &S;
+  const std::vector<PlanSeed> &seeds;
+  hipStream_t st;
+  size_t n, tot;
+  uint32_t R, d, ngc, NS;
+  double t0;
+  unsigned long long h[C_COUNT];  // the counters as last read back
+  unsigned long long *ctr = nullptr;
+  uint2 *d_seeds = nullptr;
+  uint32_t *partner = nullptr, *parent = nullptr, *cell_slot = nullptr;
+  unsigned long long *list = nullptr;
+  uint32_t slots = 0, NO = 0, n_done = 0;
+  OpRec *recs = nullptr, *ordered = nullptr;
+  int32_t *level = nullptr, *slot_level = nullptr;
+  unsigned long long *slot_min = nullptr, *keys = nullptr;
+  uint32_t *level_off = nullptr;
+  uint32_t hres[S_COUNT];
+  SchedArgs sched;
 
-namespace p2 {
-
-int plan_compile_device(p2gpu_circuit *c, const std::vector<uint2> &seeds, classes::Scratch &S, PlanArrays &out) {
-  hipStream_t st = c->stream;
-  const size_t n = c->n, tot = (size_t)c->R * n;
-  const uint32_t R = c->R, d = c->d, ngc = c->NC - c->num_selectors, NS = (uint32_t)seeds.size();
-  if (d < 1 || tot >= UNSET) { set_err("p2gpu_witness_plan_create: circuit too large"); return P2GPU_E_ARG; }
-  const double t0 = now_ms();
-  auto mark = [&](const char *label) {
+  PlanCtx(p2gpu_circuit *c_, const std::vector<PlanSeed> &seeds_, classes::Scratch &S_)
+      : c(c_), S(S_), seeds(seeds_), st(c_->stream), n(c_->n), tot((size_t)c_->R * c_->n), R(c_->R), d(c_->d),
+        ngc(c_->NC - c_->num_selectors), NS((uint32_t)seeds_.size()), t0(now_ms()) {}
+  Rows rows() const { return Rows{c->d_row_gate.p, c->d_gates.p, c->d_gconsts.p, d, R, ngc}; }
+  OpView view() const { return OpView{rows(), recs, d_seeds, cell_slot}; }
+  void mark(const char *label) const {
     if (!trace_on()) return;
     (void)hipStreamSynchronize(st);
     fprintf(stderr, "[p2gpu] plan %-28s +%.2f ms\n", label, now_ms() - t0);
-  };
-  auto dev_fail = [&](const char *what, hipError_t e) {
+  }
+  int fail(const char *what, hipError_t e) const {
     (void)hipGetLastError();
     set_err("p2gpu_witness_plan_build: %s: %s", what, hipGetErrorString(e));
     return P2GPU_E_DEVICE;
-  };
-#define PT(e, what)                                   \
-  do {                                                \
-    const hipError_t e_ = (e);                        \
-    if (e_ != hipSuccess) return dev_fail(what, e_);  \
-  } while (0)
-  // rocprim's temporary storage, grown on demand
-  void *tmp = nullptr;
-  size_t tmp_cap = 0;
-  auto need_tmp = [&](size_t bytes) {
-    if (bytes <= tmp_cap) return true;
-    tmp = S.alloc<uint8_t>(bytes);
-    tmp_cap = tmp ? bytes : 0;
-    return tmp != nullptr;
-  };
-  auto scan = [&](const uint32_t *in, uint32_t *o, size_t m) -> hipError_t {
-    size_t bytes = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, o, 0u, m, rocprim::plus<uint32_t>(), st);
-    if (e != hipSuccess) return e;
-    if (!need_tmp(bytes)) return hipErrorOutOfMemory;
-    return rocprim::exclusive_scan(tmp, tmp_cap, in, o, 0u, m, rocprim::plus<uint32_t>(), st);
-  };
-  unsigned long long h[C_COUNT];
-  unsigned long long *ctr = S.alloc<unsigned long long>(C_COUNT);
-  if (!ctr) return dev_fail("scratch", hipErrorOutOfMemory);
-  for (int i = 0; i < C_COUNT; i++) h[i] = 0;
-  h[C_BAD_SIGMA] = h[C_NO_PRODUCER] = h[C_JOIN_ONLY] = h[C_OTHER] = UINT64_MAX;
-  PT(hipMemcpyAsync(ctr, h, sizeof h, hipMemcpyHostToDevice, st), "scratch");
+  }
+  // false, with the error set, when a runtime call failed
+  bool ok(hipError_t e, const char *what) const { return e == hipSuccess || (fail(what, e), false); }
+  int refuse(PlanRefusalKind kind, unsigned long long key) const { return plan_refuse(c, PlanRefusal::at(kind, key, d)); }
+  int decode(), copy_classes(), slots_ops(), levels(), unreached();  // the phases, in order
+};
 
-  // ---- 1. decode sigma ----
+// ---- 1. decode sigma ----
+int PlanCtx::decode() {
   std::vector<gl_t> kpow(2 * (size_t)R);
   for (uint32_t col = 0; col < R; col++) {
     gl_t t = c->k_is[col];
@@ -484,166 +480,169 @@ int plan_compile_device(p2gpu_circuit *c, const std::vector<uint2> &seeds, class
   gl_t *d_kpow = S.alloc<gl_t>(2 * (size_t)R);
   gl_t *wkeys = S.alloc<gl_t>(2 * n);
   uint32_t *wrows = S.alloc<uint32_t>(2 * n);
-  uint32_t *partner = S.alloc<uint32_t>(tot);
-  uint32_t *parent = S.alloc<uint32_t>(tot);
-  unsigned long long *list = S.alloc<unsigned long long>(tot);
-  uint32_t *cell_slot = S.alloc<uint32_t>(tot);
-  uint2 *d_seeds = S.alloc<uint2>(NS);
-  if (!d_kpow || !wkeys || !wrows || !partner || !parent || !list || !cell_slot || !d_seeds) return dev_fail("scratch (classes)", hipErrorOutOfMemory);
-  PT(hipMemcpyAsync(d_kpow, kpow.data(), 16 * (size_t)R, hipMemcpyHostToDevice, st), "copy the coset powers");
-  if (NS) PT(hipMemcpyAsync(d_seeds, seeds.data(), sizeof(uint2) * NS, hipMemcpyHostToDevice, st), "copy the seed cells");
+  partner = S.alloc<uint32_t>(tot);
+  parent = S.alloc<uint32_t>(tot);
+  list = S.alloc<unsigned long long>(tot);
+  cell_slot = S.alloc<uint32_t>(tot);
+  d_seeds = S.alloc<uint2>(NS);
+  if (!d_kpow || !wkeys || !wrows || !partner || !parent || !list || !cell_slot || !d_seeds)
+    return fail("scratch (classes)", hipErrorOutOfMemory);
+  if (!ok(hipMemcpyAsync(d_kpow, kpow.data(), 16 * (size_t)R, hipMemcpyHostToDevice, st), "copy the coset powers")) return P2GPU_E_DEVICE;
+  if (NS && !ok(hipMemcpyAsync(d_seeds, seeds.data(), sizeof(uint2) * NS, hipMemcpyHostToDevice, st), "copy the seed cells")) return P2GPU_E_DEVICE;
   hipLaunchKernelGGL(plan_powers_kernel, dim3(grid_for(n)), dim3(TPB), 0, st, c->tw_fwd.p, d, wkeys, wrows);
-  {
-    size_t bytes = 0;
-    PT(rocprim::radix_sort_pairs(nullptr, bytes, wkeys, wkeys + n, wrows, wrows + n, n, 0u, 64u, st), "sort (size)");
-    if (!need_tmp(bytes)) return dev_fail("scratch (sort)", hipErrorOutOfMemory);
-    PT(rocprim::radix_sort_pairs(tmp, tmp_cap, wkeys, wkeys + n, wrows, wrows + n, n, 0u, 64u, st), "sort");
-  }
+  const auto sort = S.radix_sort_pairs(wkeys, wkeys + n, wrows, wrows + n, n, 0u, 64u, st);
+  if (!ok(sort.e, sort.step)) return P2GPU_E_DEVICE;
   hipLaunchKernelGGL(plan_decode_kernel, dim3(grid_for(tot)), dim3(TPB), 0, st, c->d_sigmas.p, c->d_kis.p, d_kpow, c->tw_fwd.p, wkeys + n,
                      wrows + n, d, R, partner, ctr + C_BAD_SIGMA);
-  // ---- 2. classes ----
-  PT(hipMemsetAsync(parent, 0xFF, 4 * tot, st), "scratch");
+  return P2GPU_OK;
+}
+
+// ---- 2. classes -> class slots ----
+int PlanCtx::copy_classes() {
+  if (!ok(hipMemsetAsync(parent, 0xFF, 4 * tot, st), "scratch")) return P2GPU_E_DEVICE;
   const SigmaPairs pairs{partner};
   hipLaunchKernelGGL(classes::touch_kernel<SigmaPairs>, dim3(grid_for(tot)), dim3(TPB), 0, st, pairs, tot, parent, list, ctr + C_TOUCHED);
-  PT(hipMemcpyAsync(h, ctr, 16, hipMemcpyDeviceToHost, st), "read the decode");
-  PT(hipStreamSynchronize(st), "decode");
+  if (!ok(hipMemcpyAsync(h, ctr, 16, hipMemcpyDeviceToHost, st), "read the decode")) return P2GPU_E_DEVICE;
+  if (!ok(hipStreamSynchronize(st), "decode")) return P2GPU_E_DEVICE;
   mark("decode sigma, touch");
-  if (h[C_BAD_SIGMA] != UINT64_MAX) {
-    set_err("p2gpu_witness_plan_create: sigma of cell (row %zu, column %u) names no routed cell", (size_t)(h[C_BAD_SIGMA] & (n - 1)),
-            (uint32_t)(h[C_BAD_SIGMA] >> d));
-    return P2GPU_E_ARG;
-  }
+  if (h[C_BAD_SIGMA] != UINT64_MAX) return refuse(PLAN_BAD_SIGMA, h[C_BAD_SIGMA]);
   const size_t T = (size_t)h[C_TOUCHED];
   if (T > tot) { set_err("p2gpu_witness_plan_build: internal error (touched cells)"); return P2GPU_E_DEVICE; }
   uint32_t *changed = S.alloc<uint32_t>(1);
-  if (!changed) return dev_fail("scratch", hipErrorOutOfMemory);
-  // while a pair is left to hook, every round removes at least one root; in practice a handful of rounds.  The bounds are
-  // backstops against a defect, not part of the algorithm: past them the compilation fails, it never loops on
-  uint32_t hc = 0;
-  for (int round = 0; T; round++) {
-    if (round > (1 << 16)) { set_err("p2gpu_witness_plan_build: internal error (classes did not settle)"); return P2GPU_E_DEVICE; }
-    PT(hipMemsetAsync(changed, 0, 4, st), "scratch");
-    hipLaunchKernelGGL(classes::hook_kernel<SigmaPairs>, dim3(grid_for(tot)), dim3(TPB), 0, st, pairs, tot, parent, changed);
-    PT(hipMemcpyAsync(&hc, changed, 4, hipMemcpyDeviceToHost, st), "read flag");
-    PT(hipStreamSynchronize(st), "hook");
-    if (!hc) break;
-    for (int j = 0;; j++) {
-      if (j > 64) { set_err("p2gpu_witness_plan_build: internal error (compression did not settle)"); return P2GPU_E_DEVICE; }
-      PT(hipMemsetAsync(changed, 0, 4, st), "scratch");
-      hipLaunchKernelGGL(classes::jump_kernel<classes::JUMP_STEPS>, dim3(grid_for(T)), dim3(TPB), 0, st, list, T, parent, changed);
-      PT(hipMemcpyAsync(&hc, changed, 4, hipMemcpyDeviceToHost, st), "read flag");
-      PT(hipStreamSynchronize(st), "jump");
-      if (!hc) break;
-    }
-  }
+  if (!changed) return fail("scratch", hipErrorOutOfMemory);
+  if (T)
+    if (int rc = classes::settle(pairs, tot, list, T, parent, changed, st, "p2gpu_witness_plan_build")) return rc;
   mark("copy classes");
   // class slots: the rank of the root among roots (the touched list's memory holds the flags and their scan from here on)
   uint32_t *flag = (uint32_t *)list, *rank = flag + tot;
   hipLaunchKernelGGL(plan_root_flags_kernel, dim3(grid_for(tot)), dim3(TPB), 0, st, parent, tot, flag);
-  PT(scan(flag, rank, tot), "scan (roots)");
+  if (!ok(S.exclusive_scan(flag, rank, tot, st), "scan (roots)")) return P2GPU_E_DEVICE;
   hipLaunchKernelGGL(plan_total_kernel, dim3(1), dim3(1), 0, st, (const unsigned long long *)nullptr, flag, rank, tot, ctr + C_CLASSES);
   hipLaunchKernelGGL(plan_class_slots_kernel, dim3(grid_for(tot)), dim3(TPB), 0, st, parent, rank, tot, cell_slot);
-  // ---- 3. slots and ops: the seeds, then the rows ----
+  return P2GPU_OK;
+}
+
+// ---- 3. slots and ops: the seeds, then the rows; the users of every slot ----
+// Leaves the schedule's arguments in `sched` (everything but the ready count is scratch of this phase and the next).
+int PlanCtx::slots_ops() {
+  SchedArgs &a = sched;
   uint32_t *sflag = S.alloc<uint32_t>(2 * (size_t)NS), *rcnt = S.alloc<uint32_t>(4 * n);
-  if (!sflag || !rcnt) return dev_fail("scratch (rows)", hipErrorOutOfMemory);
+  if (!sflag || !rcnt) return fail("scratch (rows)", hipErrorOutOfMemory);
   if (NS) {
     hipLaunchKernelGGL(plan_seed_flags_kernel, dim3((NS + TPB - 1) / TPB), dim3(TPB), 0, st, d_seeds, NS, d, R, cell_slot, sflag);
-    PT(scan(sflag, sflag + NS, NS), "scan (seeds)");
+    if (!ok(S.exclusive_scan(sflag, sflag + NS, NS, st), "scan (seeds)")) return P2GPU_E_DEVICE;
     hipLaunchKernelGGL(plan_seed_slots_kernel, dim3((NS + TPB - 1) / TPB), dim3(TPB), 0, st, d_seeds, NS, d, sflag, sflag + NS, ctr + C_CLASSES,
                        cell_slot);
   }
   hipLaunchKernelGGL(plan_total_kernel, dim3(1), dim3(1), 0, st, ctr + C_CLASSES, sflag, sflag + NS, (size_t)NS, ctr + C_SEED_SLOTS);
-  const Rows rows{c->d_row_gate.p, c->d_gates.p, c->d_gconsts.p, d, R, ngc};
   uint32_t *row_ops = rcnt, *row_new = rcnt + n, *op_off = rcnt + 2 * n, *new_off = rcnt + 3 * n;
-  hipLaunchKernelGGL(plan_rows_count_kernel, dim3(grid_for(n)), dim3(TPB), 0, st, rows, cell_slot, row_ops, row_new);
-  PT(scan(row_ops, op_off, n), "scan (ops)");
-  PT(scan(row_new, new_off, n), "scan (slots)");
+  hipLaunchKernelGGL(plan_rows_count_kernel, dim3(grid_for(n)), dim3(TPB), 0, st, rows(), cell_slot, row_ops, row_new);
+  if (!ok(S.exclusive_scan(row_ops, op_off, n, st), "scan (ops)")) return P2GPU_E_DEVICE;
+  if (!ok(S.exclusive_scan(row_new, new_off, n, st), "scan (slots)")) return P2GPU_E_DEVICE;
   hipLaunchKernelGGL(plan_total_kernel, dim3(1), dim3(1), 0, st, (const unsigned long long *)nullptr, row_ops, op_off, n, ctr + C_ROW_OPS);
   hipLaunchKernelGGL(plan_total_kernel, dim3(1), dim3(1), 0, st, ctr + C_SEED_SLOTS, row_new, new_off, n, ctr + C_SLOTS);
-  PT(hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st), "read the counts");
-  PT(hipStreamSynchronize(st), "count");
+  if (!ok(hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st), "read the counts")) return P2GPU_E_DEVICE;
+  if (!ok(hipStreamSynchronize(st), "count")) return P2GPU_E_DEVICE;
   mark("class slots, seeds, row count");
   const unsigned long long slots64 = h[C_SLOTS], ops64 = (unsigned long long)NS + h[C_ROW_OPS];
-  if (slots64 >= WRITER || ops64 >= (1ull << 32)) { set_err("p2gpu_witness_plan_create: circuit too large"); return P2GPU_E_ARG; }
-  const uint32_t slots = (uint32_t)slots64, NO = (uint32_t)ops64;
+  if (slots64 >= WRITER || ops64 >= (1ull << 32)) return refuse(PLAN_TOO_LARGE, 0);
+  slots = (uint32_t)slots64, NO = (uint32_t)ops64;
   if (slots > tot) { set_err("p2gpu_witness_plan_build: internal error (slot count)"); return P2GPU_E_DEVICE; }
   // per op and per slot
-  OpRec *recs = S.alloc<OpRec>(NO), *ordered = S.alloc<OpRec>(NO);
-  uint32_t *pending = S.alloc<uint32_t>(NO), *queue = S.alloc<uint32_t>(2 * (size_t)NO), *level_off = S.alloc<uint32_t>((size_t)NO + 2);
-  int32_t *level = S.alloc<int32_t>(NO), *slot_level = S.alloc<int32_t>(slots);
-  unsigned long long *twin_min = S.alloc<unsigned long long>(NO), *slot_min = S.alloc<unsigned long long>(slots);
-  unsigned long long *keys = S.alloc<unsigned long long>(2 * (size_t)NO);
+  recs = S.alloc<OpRec>(NO);
+  ordered = S.alloc<OpRec>(NO);
+  uint32_t *pending = S.alloc<uint32_t>(NO), *queue = S.alloc<uint32_t>(2 * (size_t)NO);
+  level_off = S.alloc<uint32_t>((size_t)NO + 2);
+  level = S.alloc<int32_t>(NO), slot_level = S.alloc<int32_t>(slots);
+  unsigned long long *twin_min = S.alloc<unsigned long long>(NO);
+  slot_min = S.alloc<unsigned long long>(slots);
+  keys = S.alloc<unsigned long long>(2 * (size_t)NO);
   uint8_t *state = S.alloc<uint8_t>(NO);
   uint32_t *use_cnt = S.alloc<uint32_t>((size_t)slots + 1), *use_off = S.alloc<uint32_t>((size_t)slots + 1);
   uint32_t *res = S.alloc<uint32_t>(S_COUNT);
   uint32_t *users = parent;  // (the classes are numbered: every routed cell is an input of one op at most, so <= tot entries)
   if (!recs || !ordered || !pending || !queue || !level_off || !level || !slot_level || !twin_min || !slot_min || !keys || !state || !use_cnt ||
       !use_off || !res)
-    return dev_fail("scratch (schedule)", hipErrorOutOfMemory);
+    return fail("scratch (schedule)", hipErrorOutOfMemory);
   if (NS) hipLaunchKernelGGL(plan_seed_ops_kernel, dim3((NS + TPB - 1) / TPB), dim3(TPB), 0, st, NS, recs);
-  hipLaunchKernelGGL(plan_rows_fill_kernel, dim3(grid_for(n)), dim3(TPB), 0, st, rows, cell_slot, op_off, new_off, NS, ctr + C_SEED_SLOTS, recs, NO);
-  const OpView view{rows, recs, d_seeds, cell_slot};
-  PT(hipMemsetAsync(use_cnt, 0, 4 * ((size_t)slots + 1), st), "scratch");
-  PT(hipMemsetAsync(level, 0xFF, 4 * (size_t)std::max(1u, NO), st), "scratch");
-  PT(hipMemsetAsync(slot_level, 0xFF, 4 * (size_t)std::max(1u, slots), st), "scratch");
-  PT(hipMemsetAsync(twin_min, 0xFF, 8 * (size_t)std::max(1u, NO), st), "scratch");
-  PT(hipMemsetAsync(slot_min, 0xFF, 8 * (size_t)std::max(1u, slots), st), "scratch");
-  PT(hipMemsetAsync(res, 0, 4 * S_COUNT, st), "scratch");
-  hipLaunchKernelGGL(plan_users_count_kernel, dim3(grid_for(NO)), dim3(TPB), 0, st, view, NO, pending, use_cnt);
-  PT(scan(use_cnt, use_off, (size_t)slots + 1), "scan (users)");
-  PT(hipMemcpyAsync(use_cnt, use_off, 4 * ((size_t)slots + 1), hipMemcpyDeviceToDevice, st), "scratch");  // (the fill pointers)
-  hipLaunchKernelGGL(plan_users_fill_kernel, dim3(grid_for(NO)), dim3(TPB), 0, st, view, NO, use_cnt, users, tot, pending, queue, ctr + C_READY);
-  PT(hipMemcpyAsync(h + C_READY, ctr + C_READY, 8, hipMemcpyDeviceToHost, st), "read the ready ops");
-  PT(hipStreamSynchronize(st), "ops");
+  hipLaunchKernelGGL(plan_rows_fill_kernel, dim3(grid_for(n)), dim3(TPB), 0, st, rows(), cell_slot, op_off, new_off, NS, ctr + C_SEED_SLOTS, recs, NO);
+  if (!ok(hipMemsetAsync(use_cnt, 0, 4 * ((size_t)slots + 1), st), "scratch")) return P2GPU_E_DEVICE;
+  if (!ok(hipMemsetAsync(level, 0xFF, 4 * (size_t)std::max(1u, NO), st), "scratch")) return P2GPU_E_DEVICE;
+  if (!ok(hipMemsetAsync(slot_level, 0xFF, 4 * (size_t)std::max(1u, slots), st), "scratch")) return P2GPU_E_DEVICE;
+  if (!ok(hipMemsetAsync(twin_min, 0xFF, 8 * (size_t)std::max(1u, NO), st), "scratch")) return P2GPU_E_DEVICE;
+  if (!ok(hipMemsetAsync(slot_min, 0xFF, 8 * (size_t)std::max(1u, slots), st), "scratch")) return P2GPU_E_DEVICE;
+  if (!ok(hipMemsetAsync(res, 0, 4 * S_COUNT, st), "scratch")) return P2GPU_E_DEVICE;
+  hipLaunchKernelGGL(plan_users_count_kernel, dim3(grid_for(NO)), dim3(TPB), 0, st, view(), NO, pending, use_cnt);
+  if (!ok(S.exclusive_scan(use_cnt, use_off, (size_t)slots + 1, st), "scan (users)")) return P2GPU_E_DEVICE;
+  if (!ok(hipMemcpyAsync(use_cnt, use_off, 4 * ((size_t)slots + 1), hipMemcpyDeviceToDevice, st), "scratch")) return P2GPU_E_DEVICE;  // (the fill pointers)
+  hipLaunchKernelGGL(plan_users_fill_kernel, dim3(grid_for(NO)), dim3(TPB), 0, st, view(), NO, use_cnt, users, tot, pending, queue, ctr + C_READY);
+  if (!ok(hipMemcpyAsync(h + C_READY, ctr + C_READY, 8, hipMemcpyDeviceToHost, st), "read the ready ops")) return P2GPU_E_DEVICE;
+  if (!ok(hipStreamSynchronize(st), "ops")) return P2GPU_E_DEVICE;
   mark("ops, users");
   if (h[C_READY] > NO) { set_err("p2gpu_witness_plan_build: internal error (ready ops)"); return P2GPU_E_DEVICE; }
-  // ---- 4. levels ----
-  SchedArgs a;
-  a.v = view; a.cell_slot = cell_slot; a.level = level; a.pending = pending; a.slot_level = slot_level; a.slot_min = slot_min;
+  a.v = view(); a.cell_slot = cell_slot; a.level = level; a.pending = pending; a.slot_level = slot_level; a.slot_min = slot_min;
   a.twin_min = twin_min; a.use_off = use_off; a.users = users; a.queue[0] = queue; a.queue[1] = queue + NO; a.state = state;
   a.level_off = level_off; a.res = res; a.n_ops = NO; a.ready = (uint32_t)h[C_READY];
+  return P2GPU_OK;
+}
+
+// ---- 4. levels, and the ops in their order ----
+int PlanCtx::levels() {
+  const SchedArgs &a = sched;
   hipLaunchKernelGGL(plan_schedule_kernel, dim3(1), dim3(SCHED_TPB), 0, st, a);
-  uint32_t hres[S_COUNT];
-  PT(hipMemcpyAsync(hres, res, sizeof hres, hipMemcpyDeviceToHost, st), "read the schedule");
-  PT(hipStreamSynchronize(st), "levels");
+  if (!ok(hipMemcpyAsync(hres, a.res, sizeof hres, hipMemcpyDeviceToHost, st), "read the schedule")) return P2GPU_E_DEVICE;
+  if (!ok(hipStreamSynchronize(st), "levels")) return P2GPU_E_DEVICE;
   mark("levels");
   if (hres[S_ERROR] || hres[S_DONE] > NO || hres[S_LEVELS] > (unsigned long long)NO + 1) {
     set_err("p2gpu_witness_plan_build: internal error (the level walk stopped at its cap, code %u)", hres[S_ERROR]);
     return P2GPU_E_DEVICE;
   }
-  const uint32_t n_done = hres[S_DONE];
+  n_done = hres[S_DONE];
   hipLaunchKernelGGL(plan_order_keys_kernel, dim3(grid_for(NO)), dim3(TPB), 0, st, level, NO, keys);
   if (NO) {
-    size_t bytes = 0;
-    PT(rocprim::radix_sort_keys(nullptr, bytes, keys, keys + NO, NO, 0u, 64u, st), "sort (size)");
-    if (!need_tmp(bytes)) return dev_fail("scratch (sort)", hipErrorOutOfMemory);
-    PT(rocprim::radix_sort_keys(tmp, tmp_cap, keys, keys + NO, NO, 0u, 64u, st), "sort");
+    const auto sort = S.radix_sort_keys(keys, keys + NO, NO, 0u, 64u, st);
+    if (!ok(sort.e, sort.step)) return P2GPU_E_DEVICE;
   }
   hipLaunchKernelGGL(plan_order_gather_kernel, dim3(grid_for(n_done)), dim3(TPB), 0, st, keys + NO, n_done, recs, ordered);
-  // ---- 5. what the schedule did not reach ----
+  return P2GPU_OK;
+}
+
+// ---- 5. what the schedule did not reach ----
+int PlanCtx::unreached() {
   uint32_t *producer = (uint32_t *)slot_min;
-  PT(hipMemsetAsync(producer, 0, 4 * (size_t)std::max(1u, slots), st), "scratch");
-  hipLaunchKernelGGL(plan_producers_kernel, dim3(grid_for(NO)), dim3(TPB), 0, st, view, NO, producer);
+  if (!ok(hipMemsetAsync(producer, 0, 4 * (size_t)std::max(1u, slots), st), "scratch")) return P2GPU_E_DEVICE;
+  hipLaunchKernelGGL(plan_producers_kernel, dim3(grid_for(NO)), dim3(TPB), 0, st, view(), NO, producer);
   hipLaunchKernelGGL(plan_unreached_kernel, dim3(grid_for(tot)), dim3(TPB), 0, st, cell_slot, tot, slot_level, producer, ctr + C_NO_PRODUCER);
   static_assert(C_JOIN_ONLY == C_NO_PRODUCER + 1 && C_OTHER == C_NO_PRODUCER + 2, "three consecutive words");
-  PT(hipMemcpyAsync(h + C_NO_PRODUCER, ctr + C_NO_PRODUCER, 24, hipMemcpyDeviceToHost, st), "read the unreached cells");
-  PT(hipStreamSynchronize(st), "order");
-  PT(hipGetLastError(), "kernel launch");
+  if (!ok(hipMemcpyAsync(h + C_NO_PRODUCER, ctr + C_NO_PRODUCER, 24, hipMemcpyDeviceToHost, st), "read the unreached cells")) return P2GPU_E_DEVICE;
+  if (!ok(hipStreamSynchronize(st), "order")) return P2GPU_E_DEVICE;
+  if (!ok(hipGetLastError(), "kernel launch")) return P2GPU_E_DEVICE;
   mark("order, unreached cells");
-#undef PT
   const unsigned long long stuck = h[C_NO_PRODUCER] != UINT64_MAX ? h[C_NO_PRODUCER] : h[C_JOIN_ONLY];
-  if (stuck != UINT64_MAX) {
-    set_err("no seed, constant or generator reaches the copy class of cell (row %zu, column %zu): a seed is missing", (size_t)(stuck & (n - 1)),
-            (size_t)(stuck >> d));
-    return P2GPU_E_ARG;
-  }
-  if (h[C_OTHER] != UINT64_MAX) {
-    set_err("dependency cycle: the generator that derives cell (row %zu, column %zu) waits for its own output", (size_t)(h[C_OTHER] & (n - 1)),
-            (size_t)(h[C_OTHER] >> d));
-    return P2GPU_E_ARG;
-  }
-  out.cell_slot = cell_slot; out.ops = ordered; out.level_off = level_off;
-  out.levels = hres[S_LEVELS]; out.slots = slots; out.widest = hres[S_WIDEST]; out.n_ops = n_done;
+  if (stuck != UINT64_MAX) return refuse(PLAN_SEED_MISSING, stuck);
+  if (h[C_OTHER] != UINT64_MAX) return refuse(PLAN_CYCLE, h[C_OTHER]);
+  return P2GPU_OK;
+}
+
+}  // namespace
+
+namespace p2 {
+
+int plan_compile_device(p2gpu_circuit *c, const std::vector<PlanSeed> &seeds, classes::Scratch &S, PlanArrays &out) {
+  PlanCtx x(c, seeds, S);
+  if (x.d < 1 || x.tot >= UNSET) return x.refuse(PLAN_TOO_LARGE, 0);
+  x.ctr = S.alloc<unsigned long long>(C_COUNT);
+  if (!x.ctr) return x.fail("scratch", hipErrorOutOfMemory);
+  for (int i = 0; i < C_COUNT; i++) x.h[i] = 0;
+  x.h[C_BAD_SIGMA] = x.h[C_NO_PRODUCER] = x.h[C_JOIN_ONLY] = x.h[C_OTHER] = UINT64_MAX;
+  if (!x.ok(hipMemcpyAsync(x.ctr, x.h, sizeof x.h, hipMemcpyHostToDevice, x.st), "scratch")) return P2GPU_E_DEVICE;
+  if (int rc = x.decode()) return rc;
+  if (int rc = x.copy_classes()) return rc;
+  if (int rc = x.slots_ops()) return rc;
+  if (int rc = x.levels()) return rc;
+  if (int rc = x.unreached()) return rc;
+  out.cell_slot = x.cell_slot; out.ops = x.ordered; out.level_off = x.level_off;
+  out.levels = x.hres[S_LEVELS]; out.slots = x.slots; out.widest = x.hres[S_WIDEST]; out.n_ops = x.n_done;
   out.kind = hipMemcpyDeviceToDevice;
   return P2GPU_OK;
 }

@@ -1,18 +1,20 @@
-// genplan.hpp -- what the two plan compilers of the device witness share: the host one in genwit.hip (plan_compile, the
-// differential oracle) and the device one in genplan.hip (plan_compile_device).  Both hand the same three arrays to
-// genwit.hip's plan_finish.
+// genplan.hpp -- what the two plan compilers of the device witness share inside the library: the host one (planhost.hpp, run by
+// witplan.hip's plan_compile: the differential oracle) and the device one (genplan.hip, plan_compile_device).  Both hand the
+// same three arrays to witplan.hip's plan_finish and word their refusals through planhost.hpp's plan_refusal_text.
 #pragma once
 #include <vector>
-#include "devclasses.hpp"
-#include "genops.hpp"
+#include "planhost.hpp"
 #include "prover_internal.hpp"
 
 namespace p2 {
 
-constexpr uint32_t PLAN_UNSET = 0xFFFFFFFFu;   // cell without a slot
-constexpr uint32_t PLAN_WRITER = 0x80000000u;  // cell_slot bit: this cell's op writes the slot (every other one compares)
-// x: the row (OP_SEED: the seed's index), y: code | sub << 8 (the slot / copy inside the row)
+namespace classes {
+struct Scratch;  // devclasses.hpp
+}
+
+// x: the row (OP_SEED: the seed's index), y: code | sub << 8 (the slot / copy inside the row): HostPlan's 64-bit word
 typedef uint2 OpRec;
+static_assert(sizeof(PlanSeed) == sizeof(uint2), "the kernels read a seed cell as a uint2 (row, col)");
 
 // a compiled plan before it is attached to a handle: host memory (kind = hipMemcpyHostToDevice) or device memory
 struct PlanArrays {
@@ -24,9 +26,14 @@ struct PlanArrays {
   hipMemcpyKind kind = hipMemcpyHostToDevice;
 };
 
-// The plan of circuit c for `seeds` ((row, col), already checked against the matrix and each other), compiled on c->stream.
-// The arrays of `out` live in S, which the caller releases once plan_finish has copied them.  Refusals carry
-// p2gpu_witness_plan_create's codes and words.
-int plan_compile_device(p2gpu_circuit *c, const std::vector<uint2> &seeds, classes::Scratch &S, PlanArrays &out);
+// a refusal of either compiler as the call's result: p2gpu_last_error's text and the code
+inline int plan_refuse(const p2gpu_circuit *c, const PlanRefusal &r) {
+  set_err("%s", plan_refusal_text(r, c->d, c->W).c_str());
+  return P2GPU_E_ARG;
+}
+
+// The plan of circuit c for `seeds` (already through plan_seeds), compiled on c->stream.  The arrays of `out` live in S,
+// which the caller releases once plan_finish has copied them.  Refusals carry p2gpu_witness_plan_create's codes and words.
+int plan_compile_device(p2gpu_circuit *c, const std::vector<PlanSeed> &seeds, classes::Scratch &S, PlanArrays &out);
 
 }  // namespace p2

@@ -1,0 +1,332 @@
+// planhost.hpp -- the witness plan compiled on the host: plain C++ over five arrays, no HIP in it (g++ compiles it:
+// csrc/tests/planhost_print.cpp, tests/test_witness_plan_host.py).  It is the statement of the plan's rules that the device
+// compiler (genplan.hip) is compared with, and the one place where the refusals of both compilers are worded.
+//   classes   sigma is decoded (sigma[x] = k_is[col'] * w^row': the coset of the value names col', the subgroup element
+//             row'); the cycles become compact class ids.
+//   slots     one value slot per class, and one per routed cell outside every class that a seed names or an op writes.
+//   ops       the closed registry of genops.hpp, per slot / copy / row as DESIGN 6b lists them; an op none of whose
+//             cells has a slot produces nothing (fill_witness derives such rows from zeros afterwards).
+//   levels    level 0 = seeds, ConstantGate rows and ops without inputs; an op runs one level above its latest input.
+//             The first op (by level, then creation order) that reaches a slot WRITES it -- its cell carries the
+//             writer bit -- every other op that derives the same slot COMPARES, one level above the writer at least.
+//             A BaseSum row runs in the direction the schedule reaches first.
+#pragma once
+#include <algorithm>
+#include <cstdio>
+#include <string>
+#include <unordered_map>
+#include <vector>
+#include "genops.hpp"
+#include "gl.hpp"
+
+namespace p2 {
+
+constexpr uint32_t PLAN_UNSET = 0xFFFFFFFFu;   // cell without a slot
+constexpr uint32_t PLAN_WRITER = 0x80000000u;  // cell_slot bit: this cell's op writes the slot (every other one compares)
+
+struct PlanSeed {
+  uint32_t row, col;
+};
+
+// the circuit as both compilers read it
+struct PlanInput {
+  uint32_t d, R, W, ngc;
+  const gl_t *sigma;        // [R][n]
+  const gl_t *gconsts;      // [ngc][n]
+  const uint8_t *row_gate;  // [n]
+  const GateDesc *gates;
+  const gl_t *k_is;         // [R]
+};
+
+// cell_slot [R][n]; ops by (level, creation order), one 64-bit word each: row | (code | sub << 8) << 32 (OP_SEED: the seed's
+// index for the row); level_off [levels + 1]
+struct HostPlan {
+  std::vector<uint32_t> cell_slot, level_off;
+  std::vector<uint64_t> ops;
+  uint32_t levels = 0, slots = 0, widest = 0;
+};
+
+enum PlanRefusalKind { PLAN_OK = 0, PLAN_SEED_OUTSIDE, PLAN_SEED_TWICE, PLAN_BAD_SIGMA, PLAN_TOO_LARGE, PLAN_SEED_MISSING, PLAN_CYCLE };
+
+// why a plan is refused: the cell, and for the seed checks the seeds that name it
+struct PlanRefusal {
+  PlanRefusalKind kind = PLAN_OK;
+  uint64_t row = 0, col = 0;
+  size_t seed = 0, seed2 = 0;
+  explicit operator bool() const { return kind != PLAN_OK; }
+  // a cell by its key, col << d | row
+  static PlanRefusal at(PlanRefusalKind kind, uint64_t key, uint32_t d) {
+    PlanRefusal r;
+    r.kind = kind; r.row = key & (((uint64_t)1 << d) - 1); r.col = key >> d;
+    return r;
+  }
+};
+
+// p2gpu_last_error's text of a refusal of a circuit with 2^d rows and W wires
+inline std::string plan_refusal_text(const PlanRefusal &r, uint32_t d, uint32_t W) {
+  char buf[256];
+  const unsigned long long row = r.row, col = r.col;
+  switch (r.kind) {
+  case PLAN_SEED_OUTSIDE:
+    snprintf(buf, sizeof buf, "seed %zu names cell (row %llu, column %llu) outside the %zu x %u wire matrix", r.seed, row, col, (size_t)1 << d, W);
+    break;
+  case PLAN_SEED_TWICE: snprintf(buf, sizeof buf, "cell (row %llu, column %llu) is seeded twice (seeds %zu and %zu)", row, col, r.seed, r.seed2); break;
+  case PLAN_BAD_SIGMA:
+    snprintf(buf, sizeof buf, "p2gpu_witness_plan_create: sigma of cell (row %llu, column %llu) names no routed cell", row, col);
+    break;
+  case PLAN_TOO_LARGE: snprintf(buf, sizeof buf, "p2gpu_witness_plan_create: circuit too large"); break;
+  case PLAN_SEED_MISSING:
+    snprintf(buf, sizeof buf, "no seed, constant or generator reaches the copy class of cell (row %llu, column %llu): a seed is missing", row, col);
+    break;
+  case PLAN_CYCLE:
+    snprintf(buf, sizeof buf, "dependency cycle: the generator that derives cell (row %llu, column %llu) waits for its own output", row, col);
+    break;
+  default: buf[0] = 0; break;
+  }
+  return buf;
+}
+
+// the seed checks of both compilers: every seed inside the matrix, no cell twice.  seed_cells: (row, col) pairs
+inline PlanRefusal plan_seeds(uint32_t d, uint32_t W, const uint32_t *seed_cells, size_t n_seeds, std::vector<PlanSeed> &out) {
+  const size_t n = (size_t)1 << d;
+  std::unordered_map<uint64_t, size_t> seen;
+  for (size_t i = 0; i < n_seeds; i++) {
+    const uint32_t row = seed_cells[2 * i], col = seed_cells[2 * i + 1];
+    PlanRefusal r;
+    r.row = row; r.col = col; r.seed = r.seed2 = i;
+    if (row >= n || col >= W) {
+      r.kind = PLAN_SEED_OUTSIDE;
+      return r;
+    }
+    if (!seen.emplace(((uint64_t)row << 32) | col, i).second) {
+      r.kind = PLAN_SEED_TWICE;
+      r.seed = seen[((uint64_t)row << 32) | col];
+      return r;
+    }
+    out.push_back(PlanSeed{row, col});
+  }
+  return PlanRefusal();
+}
+
+namespace planhost {
+
+constexpr uint32_t UNSET = PLAN_UNSET, WRITER = PLAN_WRITER;
+
+struct HostOp {
+  uint32_t code, row, sub;
+  uint32_t in0, in1, out0, out1;  // ranges in Compiler::cols
+  uint32_t pending = 0, twin = UNSET;
+  int level = -1;
+  bool dead = false;
+};
+
+struct Compiler {
+  const PlanInput &c;
+  size_t n;
+  uint32_t R, d, ngc;
+  std::vector<uint32_t> cell_slot;  // [R][n]; classes first, then the lone cells
+  std::vector<uint32_t> cols;       // input / output columns of the ops
+  std::vector<HostOp> ops;
+  uint32_t slots = 0;
+
+  explicit Compiler(const PlanInput &in) : c(in), n((size_t)1 << in.d), R(in.R), d(in.d), ngc(in.ngc) {}
+
+  size_t key(uint32_t row, uint32_t col) const { return ((size_t)col << d) + row; }
+
+  // sigma -> class ids of the cells on a cycle of length > 1
+  PlanRefusal classes() {
+    gl_t w = GL_ROOT_2_32;
+    for (uint32_t i = d; i < 32; i++) w = gl_sqr(w);
+    std::vector<gl_t> wp(n);
+    std::unordered_map<gl_t, uint32_t> row_of, col_of;
+    row_of.reserve(2 * n);
+    gl_t x = 1;
+    for (size_t r = 0; r < n; r++, x = gl_mul(x, w)) wp[r] = x, row_of[x] = (uint32_t)r;
+    std::vector<gl_t> kinv(R);
+    for (uint32_t col = 0; col < R; col++) {
+      gl_t t = c.k_is[col];
+      for (uint32_t i = 0; i < d; i++) t = gl_sqr(t);
+      col_of[t] = col;
+      kinv[col] = gl_inv(c.k_is[col]);
+    }
+    const size_t tot = (size_t)R * n;
+    std::vector<uint32_t> parent(tot, UNSET);
+    auto find = [&](uint32_t v) {
+      uint32_t r = v;
+      while (parent[r] != r) r = parent[r];
+      while (parent[v] != r) { const uint32_t nx = parent[v]; parent[v] = r; v = nx; }
+      return r;
+    };
+    for (uint32_t col = 0; col < R; col++)
+      for (size_t row = 0; row < n; row++) {
+        const gl_t s = c.sigma[key(row, col)];
+        if (s == gl_mul(c.k_is[col], wp[row])) continue;
+        gl_t t = s;
+        for (uint32_t i = 0; i < d; i++) t = gl_sqr(t);
+        const auto ci = col_of.find(t);
+        const auto ri = ci == col_of.end() ? row_of.end() : row_of.find(gl_mul(s, kinv[ci->second]));
+        if (s >= GL_P || ri == row_of.end()) return PlanRefusal::at(PLAN_BAD_SIGMA, key(row, col), d);
+        const uint32_t a = (uint32_t)key(row, col), b = (uint32_t)key(ri->second, ci->second);
+        if (parent[a] == UNSET) parent[a] = a;
+        if (parent[b] == UNSET) parent[b] = b;
+        const uint32_t ra = find(a), rb = find(b);
+        if (ra != rb) parent[std::max(ra, rb)] = std::min(ra, rb);
+      }
+    cell_slot.assign(tot, UNSET);
+    for (size_t v = 0; v < tot; v++)
+      if (parent[v] != UNSET) {
+        const uint32_t r = find((uint32_t)v);
+        if (cell_slot[r] == UNSET) cell_slot[r] = slots++;  // (r <= v: the root is numbered first)
+        cell_slot[v] = cell_slot[r];
+      }
+    return PlanRefusal();
+  }
+
+  // an op of the row (genops.hpp lists its input columns and the columns its generator sets; routed ones only count); kept when
+  // one of its cells has a slot, and then every output cell gets one
+  uint32_t add_op(uint32_t row, const OpCols &oc) {
+    bool active = false;
+    auto has_slot = [&](uint32_t col) { active |= col < R && cell_slot[key(row, col)] != UNSET; };
+    for_cols(oc.in, has_slot);
+    for_cols(oc.out, has_slot);
+    if (!active) return UNSET;
+    HostOp op;
+    op.code = oc.code; op.row = row; op.sub = oc.sub;
+    op.in0 = (uint32_t)cols.size();
+    for_cols(oc.in, [&](uint32_t col) { if (col < R && cell_slot[key(row, col)] != UNSET) cols.push_back(col); });  // a cell without a slot reads as zero
+    op.in1 = op.out0 = (uint32_t)cols.size();
+    for_cols(oc.out, [&](uint32_t col) {
+      if (col >= R) return;
+      uint32_t &s = cell_slot[key(row, col)];
+      if (s == UNSET) s = slots++;
+      cols.push_back(col);
+    });
+    op.out1 = (uint32_t)cols.size();
+    ops.push_back(op);
+    return (uint32_t)ops.size() - 1;
+  }
+
+  void row_ops(uint32_t row) {
+    const GateDesc &g = c.gates[c.row_gate[row]];
+    auto LC = [&](uint32_t i) { return i < ngc ? c.gconsts[(size_t)i * n + row] : (gl_t)0; };
+    const gl_t c0 = LC(0), c1 = LC(1);
+    if (g.kind == G_BASE_SUM) {
+      // every cell is an input of one direction and an output of the other: all of them get their slot before either op
+      // lists its inputs
+      bool active = false;
+      for (uint32_t col = 0; col <= g.p[1] && col < R; col++) active |= cell_slot[key(row, col)] != UNSET;
+      if (!active) return;
+      for (uint32_t col = 0; col <= g.p[1] && col < R; col++)
+        if (cell_slot[key(row, col)] == UNSET) cell_slot[key(row, col)] = slots++;
+      const uint32_t a = add_op(row, row_op(g, 0, c0, c1)), b = add_op(row, row_op(g, 1, c0, c1));
+      if (a != UNSET) ops[a].twin = b, ops[b].twin = a;  // (both see the same cells: kept or dropped together)
+      return;
+    }
+    for (uint32_t k = 0, m = row_num_ops(g); k < m; k++) add_op(row, row_op(g, k, c0, c1));
+  }
+  // seeds first, then the rows in order; levels; what the schedule did not reach.  order: the ops by (level, creation order)
+  PlanRefusal schedule(const std::vector<PlanSeed> &seeds, std::vector<uint32_t> &order, std::vector<uint32_t> &level_off) {
+    const size_t tot = (size_t)R * n;
+    // ---- ops: seeds first, then the rows in order ----
+    for (size_t i = 0; i < seeds.size(); i++) {
+      const PlanSeed cell = seeds[i];
+      HostOp op;
+      op.code = OP_SEED; op.row = (uint32_t)i; op.sub = 0;
+      op.in0 = op.in1 = op.out0 = (uint32_t)cols.size();
+      if (cell.col < R) {
+        uint32_t &s = cell_slot[key(cell.row, cell.col)];
+        if (s == UNSET) s = slots++;
+        cols.push_back(cell.col);
+      }
+      op.out1 = (uint32_t)cols.size();
+      ops.push_back(op);
+    }
+    for (size_t row = 0; row < n; row++) row_ops((uint32_t)row);
+    if (slots >= WRITER || ops.size() >= ((size_t)1 << 32)) {
+      PlanRefusal r;
+      r.kind = PLAN_TOO_LARGE;
+      return r;
+    }
+    // ---- levels ----
+    auto op_row = [&](const HostOp &o) { return o.code == OP_SEED ? seeds[o.row].row : o.row; };
+    auto slot_of = [&](const HostOp &o, uint32_t k) -> uint32_t & { return cell_slot[key(op_row(o), cols[k])]; };
+    std::vector<uint32_t> use_off(slots + 1, 0);
+    for (auto &o : ops) {
+      o.pending = o.in1 - o.in0;
+      for (uint32_t k = o.in0; k < o.in1; k++) use_off[slot_of(o, k) + 1]++;
+    }
+    for (uint32_t s = 0; s < slots; s++) use_off[s + 1] += use_off[s];
+    std::vector<uint32_t> users(use_off[slots]), fillp(use_off.begin(), use_off.end() - 1);
+    for (uint32_t i = 0; i < ops.size(); i++)
+      for (uint32_t k = ops[i].in0; k < ops[i].in1; k++) users[fillp[slot_of(ops[i], k)]++] = i;
+    std::vector<int> slot_level(slots, -1);
+    std::vector<uint32_t> cur, next, fresh;
+    order.clear();
+    level_off.assign(1, 0);
+    for (uint32_t i = 0; i < ops.size(); i++) if (!ops[i].pending) cur.push_back(i);
+    for (int lvl = 0; !cur.empty(); lvl++) {
+      next.clear(); fresh.clear();
+      for (uint32_t i : cur) {
+        HostOp &o = ops[i];
+        if (o.dead) continue;
+        bool wait = false;  // an earlier op of this level writes one of the outputs: compare one level later
+        for (uint32_t k = o.out0; k < o.out1; k++) wait |= slot_level[slot_of(o, k) & ~WRITER] == lvl;
+        if (wait) { next.push_back(i); continue; }
+        o.level = lvl;
+        if (o.twin != UNSET) ops[o.twin].dead = true;
+        for (uint32_t k = o.out0; k < o.out1; k++) {
+          uint32_t &s = slot_of(o, k);
+          if (slot_level[s & ~WRITER] < 0) { slot_level[s & ~WRITER] = lvl; fresh.push_back(s & ~WRITER); s |= WRITER; }
+        }
+        order.push_back(i);
+      }
+      level_off.push_back((uint32_t)order.size());
+      for (uint32_t s : fresh)
+        for (uint32_t u = use_off[s]; u < use_off[s + 1]; u++) if (--ops[users[u]].pending == 0) next.push_back(users[u]);
+      std::sort(next.begin(), next.end());
+      cur.swap(next);
+    }
+    // ---- what the schedule did not reach ----
+    // producers of every slot: 1 = some op, 2 = only the limbs -> sum direction of BaseSum rows (whose limbs wait for the sum)
+    std::vector<uint8_t> producer(slots, 0);
+    for (auto &o : ops)
+      for (uint32_t k = o.out0; k < o.out1; k++) {
+        uint8_t &f = producer[slot_of(o, k) & ~WRITER];
+        f = o.code == OP_BASE_JOIN ? (f ? f : 2) : 1;
+      }
+    size_t stuck = SIZE_MAX, join_only = SIZE_MAX, cyc = SIZE_MAX;
+    for (size_t v = 0; v < tot && stuck == SIZE_MAX; v++) {
+      const uint32_t s = cell_slot[v];
+      if (s == UNSET || slot_level[s & ~WRITER] >= 0) continue;
+      const uint8_t f = producer[s & ~WRITER];
+      if (!f) stuck = v;
+      else if (f == 2 && join_only == SIZE_MAX) join_only = v;
+      else if (cyc == SIZE_MAX) cyc = v;
+    }
+    if (stuck == SIZE_MAX) stuck = join_only;
+    if (stuck != SIZE_MAX) return PlanRefusal::at(PLAN_SEED_MISSING, stuck, d);
+    if (cyc != SIZE_MAX) return PlanRefusal::at(PLAN_CYCLE, cyc, d);
+    return PlanRefusal();
+  }
+};
+
+}  // namespace planhost
+
+// the plan of circuit `in` for `seeds` (already through plan_seeds)
+inline PlanRefusal plan_compile_host(const PlanInput &in, const std::vector<PlanSeed> &seeds, HostPlan &out) {
+  planhost::Compiler K(in);
+  if (PlanRefusal r = K.classes()) return r;
+  std::vector<uint32_t> order;
+  if (PlanRefusal r = K.schedule(seeds, order, out.level_off)) return r;
+  out.ops.clear();
+  out.ops.reserve(order.size());
+  for (uint32_t i : order) out.ops.push_back((uint64_t)K.ops[i].row | ((uint64_t)(K.ops[i].code | (K.ops[i].sub << 8)) << 32));
+  out.cell_slot.swap(K.cell_slot);
+  out.levels = (uint32_t)out.level_off.size() - 1;
+  out.slots = K.slots;
+  out.widest = 0;
+  for (uint32_t l = 0; l < out.levels; l++) out.widest = std::max(out.widest, out.level_off[l + 1] - out.level_off[l]);
+  return PlanRefusal();
+}
+
+}  // namespace p2

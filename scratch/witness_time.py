@@ -8,6 +8,7 @@ Many witnesses in one walk (p2gpu_generate_witness_batch): `batch_sha256` -- one
 whole call, B = 1 .. 64 -- and `inflight4_sha256.with_batch8` -- the four resident proofs in flight with a fifth handle
 walking batches of 8 beside them.
 usage: witness_time.py [runs] [inflight_seconds] [--only SECTION,...] [--tree DIR] [--against DIR] [--compile host|device]
+       [--batch-sizes B,...]
   -- one JSON line on stdout.  SECTIONs: plans, sha_plan (the SHA-256 plan alone), lone, batch, inflight; default: all but
   sha_plan.
   --tree DIR     measure the package of another checkout of this repository (built there), with this script: an older
@@ -17,7 +18,8 @@ usage: witness_time.py [runs] [inflight_seconds] [--only SECTION,...] [--tree DI
   --compile HOW  which plan compiler makes every plan: host (p2gpu_witness_plan_create, the default) or device
                  (p2gpu_witness_plan_build).  `plans.*.compile_ms` is that compiler's time; for five alternating runs in fresh
                  processes call `--only sha_plan` (or `plans`) once per run and compiler.  P2GPU_TRACE=1 prints the device
-                 compiler's per-phase marks on stderr."""
+                 compiler's per-phase marks on stderr.
+  --batch-sizes  the B of `batch` (default 1,2,4,8,16,32,64)."""
 import json
 import os
 import statistics
@@ -30,7 +32,7 @@ HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 argv, opts = [], {}
 it = iter(sys.argv[1:])
 for arg in it:
-    if arg in ("--only", "--tree", "--against", "--compile"):
+    if arg in ("--only", "--tree", "--against", "--compile", "--batch-sizes"):
         opts[arg] = next(it)
     else:
         argv.append(arg)
@@ -148,7 +150,7 @@ def members(B):
 
 if "batch" in only:
     res["batch_sha256"] = {}
-    for B in (1, 2, 4, 8, 16, 32, 64):
+    for B in [int(b) for b in opts.get("--batch-sizes", "1,2,4,8,16,32,64").split(",")]:
         vals = members(B)
         fig = {k: [] for k in ("batch_walk_ms", "batch_call_ms", "lone_walk_ms", "lone_call_ms")}
         for i in range(runs + 1):

@@ -17,9 +17,11 @@ import device_build_inputs as dbi  # noqa: E402
 import gen_proof_digests as gen  # noqa: E402
 import witness_gen_inputs as wgi  # noqa: E402
 import witness_plan_inputs as wpi  # noqa: E402
+import witness_plan_recorded as wpr  # noqa: E402
 
 E_ARG = -7
 COUNTS = ("ops", "levels", "widest_level", "slots", "seeds")
+RECORDED = wpr.load(GOLDEN)
 
 
 @pytest.fixture(scope="module")
@@ -35,14 +37,17 @@ def _matrix(t):
     return t.cpu().numpy().view(np.uint64)
 
 
-def _same_plan(cd, cells, keep=False):
-    """Both compilers on one handle: every exported array and every count equal.  Returns the device plan when `keep`."""
+def _same_plan(cd, cells, keep=False, recorded=None):
+    """Both compilers on one handle: every exported array and every count equal; the host compiler's also equal the plan
+    recorded under the name `recorded` (tests/witness_plan_recorded.py).  Returns the device plan when `keep`."""
     host, dev = cd.witness_plan(cells), cd.witness_plan(cells, compile="device")
     try:
         ih, idv = host.info(), dev.info()
         assert {k: ih[k] for k in COUNTS} == {k: idv[k] for k in COUNTS}
         assert idv["compile_ms"] > 0
         eh, ed = host.export(), dev.export()
+        if recorded is not None:
+            wpr.compare(recorded, RECORDED[recorded], [ih[k] for k in COUNTS], eh)
         for name, a, b in zip(("cell_slot", "ops", "level_off"), eh, ed):
             assert a.shape == b.shape and a.dtype == b.dtype, name
             bad = np.argwhere(a != b)
@@ -82,7 +87,7 @@ def _bitwise(pkg):
 def test_hand_built(pkg, gpu, name):
     kw, cells = wpi.HAND_BUILT[name]()
     cd = pkg.CircuitData.build(**kw)
-    _same_plan(cd, cells)
+    _same_plan(cd, cells, recorded=name)
     cd.close()
 
 
@@ -124,13 +129,14 @@ def test_twins_and_contenders_levels(pkg, gpu):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("prog", [wgi.FIBONACCI, wgi.QUADRATIC], ids=["fibonacci", "quadratic"])
-def test_assert_zero_programs(pkg, gpu, prog):
+@pytest.mark.parametrize("name", ["fibonacci", "quadratic"])
+def test_assert_zero_programs(pkg, gpu, name):
+    prog = {"fibonacci": wgi.FIBONACCI, "quadratic": wgi.QUADRATIC}[name]
     cb = wgi.translated(pkg, prog)
     blob, wires = cb.build(prog["witness"])
     cells, values = wgi.seeds_from_wires(cb, wires)
     cd = pkg.CircuitData(blob)
-    _same_plan(cd, cells)
+    _same_plan(cd, cells, recorded=name)
     cd.close()
 
 
@@ -140,7 +146,7 @@ def test_bitwise_blob_and_built_handles(pkg, gpu, hasher):
     cb, blob, wires, cells, values = _bitwise(pkg)
     a = pkg.CircuitData(dbi.with_hasher(blob, hasher))
     b = pkg.CircuitData.build(hasher=hasher, **dbi.decompose(pkg, blob))
-    (pa, ea), (pb, eb) = _same_plan(a, cells, keep=True), _same_plan(b, cells, keep=True)
+    (pa, ea), (pb, eb) = _same_plan(a, cells, keep=True, recorded="bitwise"), _same_plan(b, cells, keep=True, recorded="bitwise")
     for x, y in zip(ea, eb):
         assert np.array_equal(x, y)
     assert np.array_equal(_matrix(pa.generate(values)), wires) and np.array_equal(_matrix(pb.generate(values)), wires)
@@ -153,7 +159,7 @@ def test_bitwise_blob_and_built_handles(pkg, gpu, hasher):
 def test_custom_gate_chain(pkg, gpu):
     kw, cells, values, want = wgi.custom_gate_chain()
     cd = pkg.CircuitData.build(**kw)
-    plan, _ = _same_plan(cd, cells, keep=True)
+    plan, _ = _same_plan(cd, cells, keep=True, recorded="custom_gate_chain")
     got = _matrix(plan.generate(values))
     bad = np.argwhere(got != want)
     assert bad.size == 0, [(int(c), int(r), int(got[c, r]), int(want[c, r])) for c, r in bad[:8]]
@@ -170,7 +176,7 @@ def test_reference_programs(pkg, gpu, name):
     prog = test_translate._reference_programs()[name]
     cb = wgi.translated(pkg, prog, num_wires=135, public_parameters=prog["public"], private_parameters=prog["private"])
     cd = pkg.CircuitData(cb.blob())
-    _same_plan(cd, cb.builder.seed_cells())
+    _same_plan(cd, cb.builder.seed_cells(), recorded=name)
     cd.close()
 
 
@@ -187,7 +193,9 @@ def test_sha256_compression(pkg, gpu):
     ih, idv = host.info(), dev.info()
     print("sha256 plan: host", ih, "device", idv)
     assert idv["levels"] > 6000 and {k: ih[k] for k in COUNTS} == {k: idv[k] for k in COUNTS}
-    for name, a, b in zip(("cell_slot", "ops", "level_off"), host.export(), dev.export()):
+    eh = host.export()
+    wpr.compare("sha256_compression", RECORDED["sha256_compression"], [ih[k] for k in COUNTS], eh)
+    for name, a, b in zip(("cell_slot", "ops", "level_off"), eh, dev.export()):
         assert np.array_equal(a, b), name
     assert np.array_equal(_matrix(dev.generate(values)), _matrix(host.generate(values)))
     host.close()
