@@ -24,6 +24,8 @@ modulo p, assert_zero_translator.rs:118-121).
 The serialisers at the bottom are the inverse functions (what nargo does, not the backend); the tests use them
 to make files, in place of the compiled artefacts the tree lacks.
 
+``to_translator_opcodes`` hands the opcodes ``translate.py`` restates to it; MemoryInit / MemoryOp with ``memory=True``.
+
 Host-side Python by design, like ``translate.py``: runs once per program, off the hot path.
 """
 import base64
@@ -277,14 +279,34 @@ def deserialize_witnesses_within_file_path(path):
         return deserialize_witnesses(f.read())
 
 
-def to_translator_opcodes(circuit):
+def _memory_operand(e, constant):
+    """An expression of a MemoryOp as the translator's tuples carry it: the constant (the operation) or the witness index
+    (index, value) when it is one, and otherwise the expression itself -- (mul_terms, linear_combinations, q_c) -- for
+    the translator to refuse in its own words."""
+    if constant and not e["mul_terms"] and not e["linear_combinations"]:
+        return e["q_c"]
+    if not constant and not e["mul_terms"] and len(e["linear_combinations"]) == 1 and e["linear_combinations"][0][0] % P == 1 and e["q_c"] % P == 0:
+        return e["linear_combinations"][0][1]
+    return (e["mul_terms"], e["linear_combinations"], e["q_c"])
+
+
+def to_translator_opcodes(circuit, memory=False):
     """The opcode list ``translate.CircuitBuilderFromAcirToPlonky2.translate_circuit`` takes, for the opcodes it
     restates (AssertZero, RANGE, AND, XOR, Sha256Compression); BrilligCall and Directive are dropped as the
-    reference drops them (mod.rs:98-104); anything else raises NotImplementedError naming the opcode."""
+    reference drops them (mod.rs:98-104); anything else raises NotImplementedError naming the opcode.
+    ``memory=True``: MemoryInit / MemoryOp become ("memory_init", block_id, [witnesses]) and ("memory_op", block_id,
+    operation, index_witness, value_witness) (mod.rs:105-117; the predicate is dropped as the reference drops it);
+    off by default, where they are refused like any other opcode the list does not carry."""
     out = []
     for kind, body in circuit["opcodes"]:
         if kind == "AssertZero":
             out.append(("assert_zero", body["mul_terms"], body["linear_combinations"], body["q_c"]))
+        elif memory and kind == "MemoryInit":
+            out.append(("memory_init", body["block_id"], list(body["init"])))
+        elif memory and kind == "MemoryOp":
+            op = body["op"]
+            out.append(("memory_op", body["block_id"], _memory_operand(op["operation"], True), _memory_operand(op["index"], False),
+                        _memory_operand(op["value"], False)))
         elif kind in ("BrilligCall", "Directive"):
             continue
         elif kind == "BlackBoxFuncCall":

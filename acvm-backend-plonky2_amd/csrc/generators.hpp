@@ -64,6 +64,15 @@ __device__ __forceinline__ void gen_random_access_consts(A &a, const GateDesc &g
   for (uint32_t i = 0; i < extra; i++) a.set((2 + vec) * copies + i, a.lc(i));
 }
 
+// EqualityGenerator (gadgets/arithmetic.rs `is_equal`): no gate's own -- its accessor numbers the generator's four cells
+// x, y, equal, inv instead of a row's columns.  gl_inv(0) = 0 is the equal case.
+template <class A>
+__device__ __forceinline__ void gen_equality(A &a) {
+  const gl_t diff = gl_sub(a.get(0), a.get(1));
+  a.set(2, diff == 0 ? 1 : 0);
+  a.set(3, gl_inv(diff));
+}
+
 // prc: the 360 round constants (wave-uniform index -> scalar loads)
 template <class A>
 __device__ __forceinline__ void gen_poseidon(A &a, const gl_t *prc) {

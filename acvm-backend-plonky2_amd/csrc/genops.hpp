@@ -8,8 +8,12 @@ namespace p2 {
 
 enum : uint32_t {
   OP_SEED = 0, OP_CONSTANT, OP_ARITHMETIC, OP_BASE_SPLIT, OP_BASE_JOIN, OP_RA_COPY, OP_RA_CONSTS, OP_POSEIDON, OP_U32_ARITHMETIC,
-  OP_U32_ADD_MANY, OP_U32_SUBTRACTION, OP_U32_RANGE_CHECK, OP_COMPARISON
+  OP_U32_ADD_MANY, OP_U32_SUBTRACTION, OP_U32_RANGE_CHECK, OP_COMPARISON,
+  // the generators that are no gate's own (planhost.hpp): no row holds them and row_op does not list them; their cells come
+  // from the plan's generator table
+  OP_EQUALITY
 };
+static_assert(OP_EQUALITY == 13, "appended: the recorded plans keep their codes");
 
 // The columns of one op: `in` then `out`, each the concatenation of two half-open ranges [a0, b0) ++ [a1, b1) in the order the
 // schedule lists them (an empty range has a == b).  Columns >= R are gate-internal: the compilers skip them.

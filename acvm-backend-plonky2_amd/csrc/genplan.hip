@@ -8,7 +8,9 @@
 //                key whose value is >= p or names no routed cell is refused (atomicMin), as the host's first one in its loop.
 //   2. classes   devclasses.hpp's touch / hook / jump over the pairs (x, partner[x]): parent[x] = the smallest key of the class.
 //                The host numbers a class when it meets its root, the smallest key: slot = rank of the root among roots.
-//   3. slots/ops seeds first (a routed seed cell without a slot takes the next one, in seed order), then the rows top to
+//   3. slots/ops seeds first (a routed seed cell without a slot takes the next one, in seed order), then the generators that are
+//                no gate's own (a cell one of them names, without a slot, takes the next one at its FIRST naming, by generator
+//                and cell position: an atomicMin of the naming's index per cell, flags, a scan), then the rows top to
 //                bottom, ops left to right.  The ops of a row touch only that row's cells and no two ops of a row share a cell
 //                (the BaseSum twins aside, whose cells all get their slots first), so one lane per row runs genops.hpp's
 //                enumerator twice: count (ops kept, new slots), exclusive scans over the rows, fill.  For the same reason the
@@ -31,7 +33,7 @@ constexpr uint32_t UNSET = PLAN_UNSET, WRITER = PLAN_WRITER;
 constexpr uint32_t SCHED_TPB = 512;
 constexpr int32_t LEVEL_DEAD = -2;  // level[] of an op whose twin ran (-1: not scheduled, or not yet)
 // counters on the device, read back in one copy
-enum { C_BAD_SIGMA = 0, C_TOUCHED, C_CLASSES, C_SEED_SLOTS, C_SLOTS, C_ROW_OPS, C_READY, C_NO_PRODUCER, C_JOIN_ONLY, C_OTHER, C_COUNT };
+enum { C_BAD_SIGMA = 0, C_TOUCHED, C_CLASSES, C_SEED_SLOTS, C_GEN_SLOTS, C_SLOTS, C_ROW_OPS, C_READY, C_NO_PRODUCER, C_JOIN_ONLY, C_OTHER, C_COUNT };
 // plan_schedule_kernel's result words
 enum { S_LEVELS = 0, S_WIDEST, S_ERROR, S_DONE, S_COUNT };
 
@@ -126,6 +128,30 @@ __global__ void plan_seed_slots_kernel(const uint2 *seeds, uint32_t S, uint32_t 
   cell_slot[((size_t)c.y << d) + c.x] = (uint32_t)*base + scan[i];
 }
 
+// the generators that are no gate's own: entry e = generator * 4 + cell position names cell gkeys[e].  first[key] = the smallest
+// entry that names a cell without a slot (cleared for exactly the named cells: nothing else of `first` is read)
+__global__ void plan_gen_clear_kernel(const uint32_t *gkeys, uint32_t NE, uint32_t *first) {
+  const uint32_t e = blockIdx.x * TPB + threadIdx.x;
+  if (e < NE) first[gkeys[e]] = UNSET;
+}
+__global__ void plan_gen_first_kernel(const uint32_t *gkeys, uint32_t NE, const uint32_t *cell_slot, uint32_t *first) {
+  const uint32_t e = blockIdx.x * TPB + threadIdx.x;
+  if (e < NE && cell_slot[gkeys[e]] == UNSET) atomicMin(&first[gkeys[e]], e);
+}
+__global__ void plan_gen_flags_kernel(const uint32_t *gkeys, uint32_t NE, const uint32_t *cell_slot, const uint32_t *first, uint32_t *flag) {
+  const uint32_t e = blockIdx.x * TPB + threadIdx.x;
+  if (e < NE) flag[e] = cell_slot[gkeys[e]] == UNSET && first[gkeys[e]] == e ? 1u : 0u;
+}
+__global__ void plan_gen_slots_kernel(const uint32_t *gkeys, uint32_t NE, const uint32_t *flag, const uint32_t *scan,
+                                      const unsigned long long *base, uint32_t *cell_slot) {
+  const uint32_t e = blockIdx.x * TPB + threadIdx.x;
+  if (e < NE && flag[e]) cell_slot[gkeys[e]] = (uint32_t)*base + scan[e];
+}
+__global__ void plan_gen_ops_kernel(uint32_t S, uint32_t G, OpRec *recs) {
+  const uint32_t i = blockIdx.x * TPB + threadIdx.x;
+  if (i < G) recs[S + i] = make_uint2(i, OP_EQUALITY);
+}
+
 // what the compilers read of the circuit
 struct Rows {
   const uint8_t *row_gate;
@@ -198,16 +224,23 @@ __global__ void plan_seed_ops_kernel(uint32_t S, OpRec *recs) {
   if (i < S) recs[i] = make_uint2(i, OP_SEED);
 }
 
-// the cells of op i as the schedule sees them: f(key) over the routed input cells that have a slot / over the routed output cells
+// the cells of op i as the schedule sees them: f(key) over the routed input cells that have a slot / f(key, word) over the
+// routed output cells, `word` the generator-table word that takes the writer bit of a generator's cell (null: cell_slot[key] does)
 struct OpView {
   Rows x;
   const OpRec *recs;
   const uint2 *seeds;
   const uint32_t *cell_slot;
+  const uint32_t *gkeys;  // [generators][4] cell keys
+  uint32_t *gen_table;    // [generators][4] the same with the writer bits the schedule sets
   template <class F> __device__ __forceinline__ void ins(uint32_t i, F &&f) const {
     const OpRec r = recs[i];
     const uint32_t code = r.y & 0xFF;
     if (code == OP_SEED) return;
+    if (code == OP_EQUALITY) {  // (every cell a generator names has a slot)
+      for (uint32_t k = 0; k < PLAN_GEN_INS; k++) f((size_t)gkeys[PLAN_GEN_CELLS * r.x + k]);
+      return;
+    }
     const GateDesc g = x.gates[x.row_gate[r.x]];
     const OpCols o = row_op(g, op_index_in_row(g, code, r.y >> 8), x.lc(0, r.x), x.lc(1, r.x));
     for_cols(o.in, [&](uint32_t col) {
@@ -219,13 +252,17 @@ struct OpView {
     const uint32_t code = r.y & 0xFF;
     if (code == OP_SEED) {
       const uint2 c = seeds[r.x];
-      if (c.y < x.R) f(x.key(c.x, c.y));
+      if (c.y < x.R) f(x.key(c.x, c.y), (uint32_t *)nullptr);
+      return;
+    }
+    if (code == OP_EQUALITY) {
+      for (uint32_t k = PLAN_GEN_INS; k < PLAN_GEN_CELLS; k++) f((size_t)gkeys[PLAN_GEN_CELLS * r.x + k], gen_table + PLAN_GEN_CELLS * r.x + k);
       return;
     }
     const GateDesc g = x.gates[x.row_gate[r.x]];
     const OpCols o = row_op(g, op_index_in_row(g, code, r.y >> 8), 0, 0);  // (the constants decide inputs only)
     for_cols(o.out, [&](uint32_t col) {
-      if (col < x.R) f(x.key(r.x, col));
+      if (col < x.R) f(x.key(r.x, col), (uint32_t *)nullptr);
     });
   }
 };
@@ -320,13 +357,13 @@ __global__ __launch_bounds__(SCHED_TPB) void plan_schedule_kernel(SchedArgs a) {
         const uint32_t i = ld_shared(cur + k);
         if (ld_shared(a.level + i) == LEVEL_DEAD) { a.state[k] = 1; continue; }
         bool wait = false;
-        a.v.outs(i, [&](size_t key) { wait |= ld_shared(a.slot_level + (a.cell_slot[key] & ~WRITER)) == (int32_t)lvl; });
+        a.v.outs(i, [&](size_t key, uint32_t *) { wait |= ld_shared(a.slot_level + (a.cell_slot[key] & ~WRITER)) == (int32_t)lvl; });
         if (wait) {
           a.state[k] = 1;
           push(next, i);
           continue;
         }
-        a.v.outs(i, [&](size_t key) {
+        a.v.outs(i, [&](size_t key, uint32_t *) {
           const uint32_t s = a.cell_slot[key] & ~WRITER;
           if (ld_shared(a.slot_level + s) < 0) atomicMin(a.slot_min + s, tag | i);
         });
@@ -342,7 +379,7 @@ __global__ __launch_bounds__(SCHED_TPB) void plan_schedule_kernel(SchedArgs a) {
         const uint32_t i = ld_shared(cur + k);
         const unsigned long long mine = tag | i;
         bool ok = true;
-        a.v.outs(i, [&](size_t key) {
+        a.v.outs(i, [&](size_t key, uint32_t *) {
           const unsigned long long m = ld_shared(a.slot_min + (a.cell_slot[key] & ~WRITER));
           ok &= (m >> 32) != (tag >> 32) || m == mine;  // (a word nobody contended for in this round: claimed in an earlier level)
         });
@@ -358,10 +395,11 @@ __global__ __launch_bounds__(SCHED_TPB) void plan_schedule_kernel(SchedArgs a) {
         st_shared(a.level + i, (int32_t)lvl);
         atomicAdd(&s_took, 1u);
         if (twin != UNSET) st_shared(a.level + twin, LEVEL_DEAD);
-        a.v.outs(i, [&](size_t key) {
+        a.v.outs(i, [&](size_t key, uint32_t *gen_word) {
           const uint32_t s = a.cell_slot[key] & ~WRITER;
           if (atomicCAS(a.slot_level + s, -1, (int32_t)lvl) != -1) return;
-          a.cell_slot[key] = s | WRITER;
+          if (gen_word) *gen_word = (uint32_t)key | WRITER;  // (a generator's writer bit lives in its own table word)
+          else a.cell_slot[key] = s | WRITER;
           for (uint32_t u = a.use_off[s], e = a.use_off[s + 1]; u < e; u++) {
             const uint32_t user = a.users[u];
             if (atomicSub(a.pending + user, 1u) == 1u) push(next, user);
@@ -410,7 +448,7 @@ __global__ void plan_producers_kernel(OpView v, uint32_t n_ops, uint32_t *produc
   const size_t step = (size_t)gridDim.x * TPB;
   for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < n_ops; i += step) {
     const uint32_t bit = (v.recs[i].y & 0xFF) == OP_BASE_JOIN ? 2u : 1u;
-    v.outs((uint32_t)i, [&](size_t key) { atomicOr(&producer[v.cell_slot[key] & ~WRITER], bit); });
+    v.outs((uint32_t)i, [&](size_t key, uint32_t *) { atomicOr(&producer[v.cell_slot[key] & ~WRITER], bit); });
   }
 }
 // the smallest unreached cell without a producer / with joins only / with any other producer
@@ -430,13 +468,15 @@ struct PlanCtx {
   p2gpu_circuit *c;
   classes::Scratch &S;
   const std::vector<PlanSeed> &seeds;
+  const std::vector<PlanGenerator> &gens;
   hipStream_t st;
   size_t n, tot;
-  uint32_t R, d, ngc, NS;
+  uint32_t R, d, ngc, NS, NG;
   double t0;
   unsigned long long h[C_COUNT];  // the counters as last read back
   unsigned long long *ctr = nullptr;
   uint2 *d_seeds = nullptr;
+  uint32_t *gkeys = nullptr, *gen_table = nullptr;
   uint32_t *partner = nullptr, *parent = nullptr, *cell_slot = nullptr;
   unsigned long long *list = nullptr;
   uint32_t slots = 0, NO = 0, n_done = 0;
@@ -447,11 +487,11 @@ struct PlanCtx {
   uint32_t hres[S_COUNT];
   SchedArgs sched;
 
-  PlanCtx(p2gpu_circuit *c_, const std::vector<PlanSeed> &seeds_, classes::Scratch &S_)
-      : c(c_), S(S_), seeds(seeds_), st(c_->stream), n(c_->n), tot((size_t)c_->R * c_->n), R(c_->R), d(c_->d),
-        ngc(c_->NC - c_->num_selectors), NS((uint32_t)seeds_.size()), t0(now_ms()) {}
+  PlanCtx(p2gpu_circuit *c_, const std::vector<PlanSeed> &seeds_, const std::vector<PlanGenerator> &gens_, classes::Scratch &S_)
+      : c(c_), S(S_), seeds(seeds_), gens(gens_), st(c_->stream), n(c_->n), tot((size_t)c_->R * c_->n), R(c_->R), d(c_->d),
+        ngc(c_->NC - c_->num_selectors), NS((uint32_t)seeds_.size()), NG((uint32_t)gens_.size()), t0(now_ms()) {}
   Rows rows() const { return Rows{c->d_row_gate.p, c->d_gates.p, c->d_gconsts.p, d, R, ngc}; }
-  OpView view() const { return OpView{rows(), recs, d_seeds, cell_slot}; }
+  OpView view() const { return OpView{rows(), recs, d_seeds, cell_slot, gkeys, gen_table}; }
   void mark(const char *label) const {
     if (!trace_on()) return;
     (void)hipStreamSynchronize(st);
@@ -522,7 +562,7 @@ int PlanCtx::copy_classes() {
   return P2GPU_OK;
 }
 
-// ---- 3. slots and ops: the seeds, then the rows; the users of every slot ----
+// ---- 3. slots and ops: the seeds, then the generators that are no gate's own, then the rows; the users of every slot ----
 // Leaves the schedule's arguments in `sched` (everything but the ready count is scratch of this phase and the next).
 int PlanCtx::slots_ops() {
   SchedArgs &a = sched;
@@ -535,16 +575,39 @@ int PlanCtx::slots_ops() {
                        cell_slot);
   }
   hipLaunchKernelGGL(plan_total_kernel, dim3(1), dim3(1), 0, st, ctr + C_CLASSES, sflag, sflag + NS, (size_t)NS, ctr + C_SEED_SLOTS);
+  // the generators' cells: keys from the checked list (every cell inside [n] x [R]), slots behind the seeds'
+  const uint32_t NE = PLAN_GEN_CELLS * NG;
+  uint32_t *gflag = S.alloc<uint32_t>(2 * (size_t)NE);
+  gkeys = S.alloc<uint32_t>(NE);
+  gen_table = S.alloc<uint32_t>(NE);
+  if (!gflag || !gkeys || !gen_table) return fail("scratch (generators)", hipErrorOutOfMemory);
+  if (NE) {
+    std::vector<uint32_t> hkeys(NE);
+    for (uint32_t e = 0; e < NE; e++)
+      hkeys[e] = (gens[e / PLAN_GEN_CELLS].cells[e % PLAN_GEN_CELLS][1] << d) + gens[e / PLAN_GEN_CELLS].cells[e % PLAN_GEN_CELLS][0];
+    // (pageable memory: the copy has left hkeys when the call returns)
+    if (!ok(hipMemcpyAsync(gkeys, hkeys.data(), 4 * (size_t)NE, hipMemcpyHostToDevice, st), "copy the generator cells")) return P2GPU_E_DEVICE;
+    if (!ok(hipStreamSynchronize(st), "copy the generator cells")) return P2GPU_E_DEVICE;
+    if (!ok(hipMemcpyAsync(gen_table, gkeys, 4 * (size_t)NE, hipMemcpyDeviceToDevice, st), "scratch")) return P2GPU_E_DEVICE;
+    const dim3 gg((NE + TPB - 1) / TPB);
+    uint32_t *first = partner;  // (the decoded partners are done with once the classes stand)
+    hipLaunchKernelGGL(plan_gen_clear_kernel, gg, dim3(TPB), 0, st, gkeys, NE, first);
+    hipLaunchKernelGGL(plan_gen_first_kernel, gg, dim3(TPB), 0, st, gkeys, NE, cell_slot, first);
+    hipLaunchKernelGGL(plan_gen_flags_kernel, gg, dim3(TPB), 0, st, gkeys, NE, cell_slot, first, gflag);
+    if (!ok(S.exclusive_scan(gflag, gflag + NE, NE, st), "scan (generators)")) return P2GPU_E_DEVICE;
+    hipLaunchKernelGGL(plan_gen_slots_kernel, gg, dim3(TPB), 0, st, gkeys, NE, gflag, gflag + NE, ctr + C_SEED_SLOTS, cell_slot);
+  }
+  hipLaunchKernelGGL(plan_total_kernel, dim3(1), dim3(1), 0, st, ctr + C_SEED_SLOTS, gflag, gflag + NE, (size_t)NE, ctr + C_GEN_SLOTS);
   uint32_t *row_ops = rcnt, *row_new = rcnt + n, *op_off = rcnt + 2 * n, *new_off = rcnt + 3 * n;
   hipLaunchKernelGGL(plan_rows_count_kernel, dim3(grid_for(n)), dim3(TPB), 0, st, rows(), cell_slot, row_ops, row_new);
   if (!ok(S.exclusive_scan(row_ops, op_off, n, st), "scan (ops)")) return P2GPU_E_DEVICE;
   if (!ok(S.exclusive_scan(row_new, new_off, n, st), "scan (slots)")) return P2GPU_E_DEVICE;
   hipLaunchKernelGGL(plan_total_kernel, dim3(1), dim3(1), 0, st, (const unsigned long long *)nullptr, row_ops, op_off, n, ctr + C_ROW_OPS);
-  hipLaunchKernelGGL(plan_total_kernel, dim3(1), dim3(1), 0, st, ctr + C_SEED_SLOTS, row_new, new_off, n, ctr + C_SLOTS);
+  hipLaunchKernelGGL(plan_total_kernel, dim3(1), dim3(1), 0, st, ctr + C_GEN_SLOTS, row_new, new_off, n, ctr + C_SLOTS);
   if (!ok(hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st), "read the counts")) return P2GPU_E_DEVICE;
   if (!ok(hipStreamSynchronize(st), "count")) return P2GPU_E_DEVICE;
-  mark("class slots, seeds, row count");
-  const unsigned long long slots64 = h[C_SLOTS], ops64 = (unsigned long long)NS + h[C_ROW_OPS];
+  mark("class slots, seeds, generators, row count");
+  const unsigned long long slots64 = h[C_SLOTS], ops64 = (unsigned long long)NS + NG + h[C_ROW_OPS];
   if (slots64 >= WRITER || ops64 >= (1ull << 32)) return refuse(PLAN_TOO_LARGE, 0);
   slots = (uint32_t)slots64, NO = (uint32_t)ops64;
   if (slots > tot) { set_err("p2gpu_witness_plan_build: internal error (slot count)"); return P2GPU_E_DEVICE; }
@@ -560,12 +623,16 @@ int PlanCtx::slots_ops() {
   uint8_t *state = S.alloc<uint8_t>(NO);
   uint32_t *use_cnt = S.alloc<uint32_t>((size_t)slots + 1), *use_off = S.alloc<uint32_t>((size_t)slots + 1);
   uint32_t *res = S.alloc<uint32_t>(S_COUNT);
-  uint32_t *users = parent;  // (the classes are numbered: every routed cell is an input of one op at most, so <= tot entries)
+  // the classes are numbered: parent is free.  Every routed cell is an input of one row op at most and of any number of
+  // generators, two inputs each: <= tot + 2 NG entries
+  const size_t users_cap = tot + (size_t)PLAN_GEN_INS * NG;
+  uint32_t *users = NG ? S.alloc<uint32_t>(users_cap) : parent;
   if (!recs || !ordered || !pending || !queue || !level_off || !level || !slot_level || !twin_min || !slot_min || !keys || !state || !use_cnt ||
-      !use_off || !res)
+      !use_off || !res || !users)
     return fail("scratch (schedule)", hipErrorOutOfMemory);
   if (NS) hipLaunchKernelGGL(plan_seed_ops_kernel, dim3((NS + TPB - 1) / TPB), dim3(TPB), 0, st, NS, recs);
-  hipLaunchKernelGGL(plan_rows_fill_kernel, dim3(grid_for(n)), dim3(TPB), 0, st, rows(), cell_slot, op_off, new_off, NS, ctr + C_SEED_SLOTS, recs, NO);
+  if (NG) hipLaunchKernelGGL(plan_gen_ops_kernel, dim3((NG + TPB - 1) / TPB), dim3(TPB), 0, st, NS, NG, recs);
+  hipLaunchKernelGGL(plan_rows_fill_kernel, dim3(grid_for(n)), dim3(TPB), 0, st, rows(), cell_slot, op_off, new_off, NS + NG, ctr + C_GEN_SLOTS, recs, NO);
   if (!ok(hipMemsetAsync(use_cnt, 0, 4 * ((size_t)slots + 1), st), "scratch")) return P2GPU_E_DEVICE;
   if (!ok(hipMemsetAsync(level, 0xFF, 4 * (size_t)std::max(1u, NO), st), "scratch")) return P2GPU_E_DEVICE;
   if (!ok(hipMemsetAsync(slot_level, 0xFF, 4 * (size_t)std::max(1u, slots), st), "scratch")) return P2GPU_E_DEVICE;
@@ -575,7 +642,7 @@ int PlanCtx::slots_ops() {
   hipLaunchKernelGGL(plan_users_count_kernel, dim3(grid_for(NO)), dim3(TPB), 0, st, view(), NO, pending, use_cnt);
   if (!ok(S.exclusive_scan(use_cnt, use_off, (size_t)slots + 1, st), "scan (users)")) return P2GPU_E_DEVICE;
   if (!ok(hipMemcpyAsync(use_cnt, use_off, 4 * ((size_t)slots + 1), hipMemcpyDeviceToDevice, st), "scratch")) return P2GPU_E_DEVICE;  // (the fill pointers)
-  hipLaunchKernelGGL(plan_users_fill_kernel, dim3(grid_for(NO)), dim3(TPB), 0, st, view(), NO, use_cnt, users, tot, pending, queue, ctr + C_READY);
+  hipLaunchKernelGGL(plan_users_fill_kernel, dim3(grid_for(NO)), dim3(TPB), 0, st, view(), NO, use_cnt, users, users_cap, pending, queue, ctr + C_READY);
   if (!ok(hipMemcpyAsync(h + C_READY, ctr + C_READY, 8, hipMemcpyDeviceToHost, st), "read the ready ops")) return P2GPU_E_DEVICE;
   if (!ok(hipStreamSynchronize(st), "ops")) return P2GPU_E_DEVICE;
   mark("ops, users");
@@ -628,9 +695,10 @@ int PlanCtx::unreached() {
 
 namespace p2 {
 
-int plan_compile_device(p2gpu_circuit *c, const std::vector<PlanSeed> &seeds, classes::Scratch &S, PlanArrays &out) {
-  PlanCtx x(c, seeds, S);
-  if (x.d < 1 || x.tot >= UNSET) return x.refuse(PLAN_TOO_LARGE, 0);
+int plan_compile_device(p2gpu_circuit *c, const std::vector<PlanSeed> &seeds, const std::vector<PlanGenerator> &gens, classes::Scratch &S,
+                        PlanArrays &out) {
+  PlanCtx x(c, seeds, gens, S);
+  if (x.d < 1 || x.tot >= UNSET || (x.NG && x.tot >= WRITER)) return x.refuse(PLAN_TOO_LARGE, 0);  // (a table word: the key below the writer bit)
   x.ctr = S.alloc<unsigned long long>(C_COUNT);
   if (!x.ctr) return x.fail("scratch", hipErrorOutOfMemory);
   for (int i = 0; i < C_COUNT; i++) x.h[i] = 0;
@@ -641,7 +709,7 @@ int plan_compile_device(p2gpu_circuit *c, const std::vector<PlanSeed> &seeds, cl
   if (int rc = x.slots_ops()) return rc;
   if (int rc = x.levels()) return rc;
   if (int rc = x.unreached()) return rc;
-  out.cell_slot = x.cell_slot; out.ops = x.ordered; out.level_off = x.level_off;
+  out.cell_slot = x.cell_slot; out.ops = x.ordered; out.level_off = x.level_off; out.gen_table = x.gen_table; out.n_gens = x.NG;
   out.levels = x.hres[S_LEVELS]; out.slots = x.slots; out.widest = x.hres[S_WIDEST]; out.n_ops = x.n_done;
   out.kind = hipMemcpyDeviceToDevice;
   return P2GPU_OK;

@@ -29,13 +29,14 @@ struct WalkArgs {
   const uint32_t *level_off;  // [levels + 1]
   uint32_t levels;
   const uint32_t *cell_slot;  // [R][n]
+  const uint32_t *gen_table;  // [generators][4]: cell key | WRITER
   gl_t *val;                  // [slots][B]
   const uint2 *seed_cells;    // (row, col)
   const gl_t *seed_vals;      // [seeds][B]
   const uint8_t *row_gate;
   const GateDesc *gates;
   const gl_t *gconsts, *prc;
-  unsigned long long *err;    // [B]: per witness, the smallest (op position << 8 | column) that contradicts
+  unsigned long long *err;    // [B]: per witness, the smallest (op position << 8 | column, or a generator's cell position) that contradicts
   uint32_t d, R, ngc, B;
 };
 
@@ -62,6 +63,23 @@ struct RowSlots {
   __device__ __forceinline__ void reject(uint32_t col) { atomicMin(a.err + b, ((unsigned long long)pos << 8) | col); }
 };
 
+// a generator that is no gate's own as the level walk sees it: witness b's slot values behind its four cells, which the plan's
+// table names (every one has a slot); the writer bits are the table words', not cell_slot's
+struct GenSlots {
+  const WalkArgs &a;
+  const uint32_t *words;  // the generator's row of the table
+  uint32_t pos;           // of the op in the schedule
+  uint32_t b;             // witness of the batch
+  __device__ __forceinline__ gl_t &slot(uint32_t s) const { return a.val[(size_t)s * a.B + b]; }
+  __device__ __forceinline__ uint32_t slot_of(uint32_t i) const { return a.cell_slot[words[i] & ~WRITER] & ~WRITER; }
+  __device__ __forceinline__ gl_t get(uint32_t i) const { return slot(slot_of(i)); }
+  __device__ __forceinline__ void set(uint32_t i, gl_t v) {
+    if (words[i] & WRITER) slot(slot_of(i)) = v;
+    else if (slot(slot_of(i)) != v) reject(i);
+  }
+  __device__ __forceinline__ void reject(uint32_t i) { atomicMin(a.err + b, ((unsigned long long)pos << 8) | i); }
+};
+
 __device__ __forceinline__ void run_op(const WalkArgs &a, uint32_t pos, uint32_t b) {
   const OpRec op = a.ops[pos];
   const uint32_t code = op.y & 0xFF, sub = op.y >> 8;
@@ -71,6 +89,11 @@ __device__ __forceinline__ void run_op(const WalkArgs &a, uint32_t pos, uint32_t
     RowSlots w{a, cell.x, pos, b};
     if (v >= GL_P) w.reject(cell.y);
     else w.set(cell.y, v);
+    return;
+  }
+  if (code == OP_EQUALITY) {
+    GenSlots w{a, a.gen_table + (size_t)PLAN_GEN_CELLS * op.x, pos, b};
+    gen_equality(w);
     return;
   }
   RowSlots w{a, op.x, pos, b};
@@ -143,7 +166,7 @@ int walk_and_scatter(p2gpu_witness_plan *p, uint32_t B, gl_t *wires) {
   if (n_vals) HIP_TRY(hipMemcpyAsync(p->seed_vals.p, p->pin, 8 * n_vals, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemsetAsync(p->err.p, 0xFF, 8 * (size_t)B, st));
   WalkArgs a;
-  a.ops = p->ops.p; a.level_off = p->level_off.p; a.levels = p->levels; a.cell_slot = p->cell_slot.p; a.val = p->val.p;
+  a.ops = p->ops.p; a.level_off = p->level_off.p; a.levels = p->levels; a.cell_slot = p->cell_slot.p; a.gen_table = p->gen_table.p; a.val = p->val.p;
   a.seed_cells = p->seed_cells.p; a.seed_vals = p->seed_vals.p; a.row_gate = c->d_row_gate.p; a.gates = c->d_gates.p;
   a.gconsts = c->d_gconsts.p; a.prc = c->d_prc.p; a.err = p->err.p; a.d = c->d; a.R = c->R; a.ngc = ngc; a.B = B;
   HIP_TRY(hipEventRecord(p->ev0, st));
@@ -181,6 +204,15 @@ int name_contradiction(const p2gpu_witness_plan *p, uint64_t e, const uint64_t *
   const uint32_t col = (uint32_t)(e & 0xFF);
   if (pos >= p->h_ops.size()) { set_err("p2gpu_generate_witness: internal error (contradiction word)"); return P2GPU_E_DEVICE; }
   const OpRec op = p->h_ops[pos];
+  if ((op.y & 0xFF) == OP_EQUALITY) {  // (the low byte is the generator's cell position, not a column)
+    const size_t at = (size_t)PLAN_GEN_CELLS * op.x + col;
+    if (col >= PLAN_GEN_CELLS || at >= p->h_gen_table.size()) { set_err("p2gpu_generate_witness: internal error (contradiction word)"); return P2GPU_E_DEVICE; }
+    const uint32_t key = p->h_gen_table[at] & ~WRITER;
+    cell[0] = key & (uint32_t)(p->c->n - 1);
+    cell[1] = key >> p->c->d;
+    set_err("%sunsatisfiable: generator %u: cell (row %u, column %u) already has another value", who, op.x, cell[0], cell[1]);
+    return P2GPU_E_UNSATISFIED;
+  }
   const bool seed = (op.y & 0xFF) == OP_SEED;
   cell[0] = seed ? p->h_seed_cells[op.x].row : op.x;
   cell[1] = col;

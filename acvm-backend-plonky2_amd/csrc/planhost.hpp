@@ -10,6 +10,23 @@
 //             The first op (by level, then creation order) that reaches a slot WRITES it -- its cell carries the
 //             writer bit -- every other op that derives the same slot COMPARES, one level above the writer at least.
 //             A BaseSum row runs in the direction the schedule reaches first.
+//   generators that are no gate's own (PlanGenerator; the equality generator of plonky2's `is_equal` is the first): their
+//             cells lie in other gates' rows, anywhere among the routed cells.
+//             creation order  seeds, then the generators in list order, then the rows; a generator's op record is
+//                             list index | (OP_EQUALITY | 0 << 8) << 32.
+//             slots           classes, then seeds, then every cell a generator names that has no slot yet -- by (generator,
+//                             cell position); a cell named again already has its slot -- then the rows.  So a row op created
+//                             afterwards sees these cells as cells with a slot, and the inputs an op lists when it is created
+//                             stay those that have a slot in the end.  A generator is always kept.  An input of a generator
+//                             that nothing writes is an unreached slot: "a seed is missing", with that cell.
+//             writer bits     a generator's live in ITS OWN table word (gen_table [generators][4]: cell key | bit 31), not in
+//                             cell_slot, whose bit keeps meaning "the row op (or seed) that has this cell as an output writes
+//                             it": a cell that is a generator's output and a row op's output has one writer.  The level rule
+//                             is unchanged: the first by (level, creation order) writes, every other op that derives the slot
+//                             -- another generator, a seed, a row op -- compares, one level above at least.
+//             refusals        before anything indexes with the cells: an unknown kind, a cell outside [n] x [R].
+//             sizes           the generators count among the ops; a cell can be an input of a row op and of generators, so
+//                             the `users` lists hold up to R n + 2 generators entries; a table word keeps the key in 31 bits.
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -28,6 +45,14 @@ struct PlanSeed {
   uint32_t row, col;
 };
 
+// a generator that is no gate's own: p2gpu.h's p2gpu_generator, word for word
+constexpr uint32_t PLAN_GEN_EQUALITY = 0;  // cells: x, y (read), equal, inv (set)
+constexpr uint32_t PLAN_GEN_CELLS = 4, PLAN_GEN_INS = 2;
+struct PlanGenerator {
+  uint32_t kind;
+  uint32_t cells[PLAN_GEN_CELLS][2];  // (row, col), routed columns only
+};
+
 // the circuit as both compilers read it
 struct PlanInput {
   uint32_t d, R, W, ngc;
@@ -39,16 +64,19 @@ struct PlanInput {
 };
 
 // cell_slot [R][n]; ops by (level, creation order), one 64-bit word each: row | (code | sub << 8) << 32 (OP_SEED: the seed's
-// index for the row); level_off [levels + 1]
+// index for the row, OP_EQUALITY: the generator's); level_off [levels + 1]; gen_table [generators][4]: cell key (col << d | row)
+// | PLAN_WRITER = this generator writes the cell's slot
 struct HostPlan {
-  std::vector<uint32_t> cell_slot, level_off;
+  std::vector<uint32_t> cell_slot, level_off, gen_table;
   std::vector<uint64_t> ops;
   uint32_t levels = 0, slots = 0, widest = 0;
 };
 
-enum PlanRefusalKind { PLAN_OK = 0, PLAN_SEED_OUTSIDE, PLAN_SEED_TWICE, PLAN_BAD_SIGMA, PLAN_TOO_LARGE, PLAN_SEED_MISSING, PLAN_CYCLE };
+enum PlanRefusalKind { PLAN_OK = 0, PLAN_SEED_OUTSIDE, PLAN_SEED_TWICE, PLAN_BAD_SIGMA, PLAN_TOO_LARGE, PLAN_SEED_MISSING, PLAN_CYCLE, PLAN_GEN_KIND, PLAN_GEN_OUTSIDE,
+                       PLAN_GEN_NULL };
 
-// why a plan is refused: the cell, and for the seed checks the seeds that name it
+// why a plan is refused: the cell, and for the seed checks the seeds that name it (the generator checks: seed = the generator's
+// index, seed2 = its kind)
 struct PlanRefusal {
   PlanRefusalKind kind = PLAN_OK;
   uint64_t row = 0, col = 0;
@@ -62,8 +90,8 @@ struct PlanRefusal {
   }
 };
 
-// p2gpu_last_error's text of a refusal of a circuit with 2^d rows and W wires
-inline std::string plan_refusal_text(const PlanRefusal &r, uint32_t d, uint32_t W) {
+// p2gpu_last_error's text of a refusal of a circuit with 2^d rows and W wires, R of them routed
+inline std::string plan_refusal_text(const PlanRefusal &r, uint32_t d, uint32_t W, uint32_t R = 0) {
   char buf[256];
   const unsigned long long row = r.row, col = r.col;
   switch (r.kind) {
@@ -81,6 +109,11 @@ inline std::string plan_refusal_text(const PlanRefusal &r, uint32_t d, uint32_t 
   case PLAN_CYCLE:
     snprintf(buf, sizeof buf, "dependency cycle: the generator that derives cell (row %llu, column %llu) waits for its own output", row, col);
     break;
+  case PLAN_GEN_KIND: snprintf(buf, sizeof buf, "generator %zu has the unknown kind %zu", r.seed, r.seed2); break;
+  case PLAN_GEN_OUTSIDE:
+    snprintf(buf, sizeof buf, "generator %zu names cell (row %llu, column %llu) outside the %zu x %u routed cells", r.seed, row, col, (size_t)1 << d, R);
+    break;
+  case PLAN_GEN_NULL: snprintf(buf, sizeof buf, "generators are counted but the list is a null pointer"); break;
   default: buf[0] = 0; break;
   }
   return buf;
@@ -108,13 +141,39 @@ inline PlanRefusal plan_seeds(uint32_t d, uint32_t W, const uint32_t *seed_cells
   return PlanRefusal();
 }
 
+// the generator checks of both compilers: a known kind, every cell a routed one.  Nothing indexes with a cell before this
+inline PlanRefusal plan_generators(uint32_t d, uint32_t R, const PlanGenerator *gens, size_t n_gens, std::vector<PlanGenerator> &out) {
+  const size_t n = (size_t)1 << d;
+  PlanRefusal r;
+  if (n_gens && !gens) {
+    r.kind = PLAN_GEN_NULL;
+    return r;
+  }
+  for (size_t i = 0; i < n_gens; i++) {
+    r.seed = i; r.seed2 = gens[i].kind;
+    if (gens[i].kind != PLAN_GEN_EQUALITY) {
+      r.kind = PLAN_GEN_KIND;
+      return r;
+    }
+    for (uint32_t k = 0; k < PLAN_GEN_CELLS; k++) {
+      r.row = gens[i].cells[k][0]; r.col = gens[i].cells[k][1];
+      if (r.row >= n || r.col >= R) {
+        r.kind = PLAN_GEN_OUTSIDE;
+        return r;
+      }
+    }
+    out.push_back(gens[i]);
+  }
+  return PlanRefusal();
+}
+
 namespace planhost {
 
 constexpr uint32_t UNSET = PLAN_UNSET, WRITER = PLAN_WRITER;
 
 struct HostOp {
-  uint32_t code, row, sub;
-  uint32_t in0, in1, out0, out1;  // ranges in Compiler::cols
+  uint32_t code, row, sub;        // row: the seed's / the generator's index for those
+  uint32_t in0, in1, out0, out1;  // ranges in Compiler::cells
   uint32_t pending = 0, twin = UNSET;
   int level = -1;
   bool dead = false;
@@ -125,7 +184,8 @@ struct Compiler {
   size_t n;
   uint32_t R, d, ngc;
   std::vector<uint32_t> cell_slot;  // [R][n]; classes first, then the lone cells
-  std::vector<uint32_t> cols;       // input / output columns of the ops
+  std::vector<uint32_t> cells;      // input / output cells of the ops, by key: an op's cells need not lie in one row
+  std::vector<uint32_t> gen_table;  // [generators][4]
   std::vector<HostOp> ops;
   uint32_t slots = 0;
 
@@ -192,16 +252,16 @@ struct Compiler {
     if (!active) return UNSET;
     HostOp op;
     op.code = oc.code; op.row = row; op.sub = oc.sub;
-    op.in0 = (uint32_t)cols.size();
-    for_cols(oc.in, [&](uint32_t col) { if (col < R && cell_slot[key(row, col)] != UNSET) cols.push_back(col); });  // a cell without a slot reads as zero
-    op.in1 = op.out0 = (uint32_t)cols.size();
+    op.in0 = (uint32_t)cells.size();
+    for_cols(oc.in, [&](uint32_t col) { if (col < R && cell_slot[key(row, col)] != UNSET) cells.push_back((uint32_t)key(row, col)); });  // a cell without a slot reads as zero
+    op.in1 = op.out0 = (uint32_t)cells.size();
     for_cols(oc.out, [&](uint32_t col) {
       if (col >= R) return;
       uint32_t &s = cell_slot[key(row, col)];
       if (s == UNSET) s = slots++;
-      cols.push_back(col);
+      cells.push_back((uint32_t)key(row, col));
     });
-    op.out1 = (uint32_t)cols.size();
+    op.out1 = (uint32_t)cells.size();
     ops.push_back(op);
     return (uint32_t)ops.size() - 1;
   }
@@ -224,21 +284,42 @@ struct Compiler {
     }
     for (uint32_t k = 0, m = row_num_ops(g); k < m; k++) add_op(row, row_op(g, k, c0, c1));
   }
-  // seeds first, then the rows in order; levels; what the schedule did not reach.  order: the ops by (level, creation order)
-  PlanRefusal schedule(const std::vector<PlanSeed> &seeds, std::vector<uint32_t> &order, std::vector<uint32_t> &level_off) {
+  // seeds first, then the generators, then the rows in order; levels; what the schedule did not reach.  order: the ops by
+  // (level, creation order)
+  PlanRefusal schedule(const std::vector<PlanSeed> &seeds, const std::vector<PlanGenerator> &gens, std::vector<uint32_t> &order,
+                       std::vector<uint32_t> &level_off) {
     const size_t tot = (size_t)R * n;
-    // ---- ops: seeds first, then the rows in order ----
+    if (!gens.empty() && tot >= WRITER) {  // (a table word keeps the key below its writer bit)
+      PlanRefusal r;
+      r.kind = PLAN_TOO_LARGE;
+      return r;
+    }
+    // ---- ops: seeds first, then the generators, then the rows in order ----
     for (size_t i = 0; i < seeds.size(); i++) {
       const PlanSeed cell = seeds[i];
       HostOp op;
       op.code = OP_SEED; op.row = (uint32_t)i; op.sub = 0;
-      op.in0 = op.in1 = op.out0 = (uint32_t)cols.size();
+      op.in0 = op.in1 = op.out0 = (uint32_t)cells.size();
       if (cell.col < R) {
         uint32_t &s = cell_slot[key(cell.row, cell.col)];
         if (s == UNSET) s = slots++;
-        cols.push_back(cell.col);
+        cells.push_back((uint32_t)key(cell.row, cell.col));
       }
-      op.out1 = (uint32_t)cols.size();
+      op.out1 = (uint32_t)cells.size();
+      ops.push_back(op);
+    }
+    for (size_t i = 0; i < gens.size(); i++) {
+      HostOp op;
+      op.code = OP_EQUALITY; op.row = (uint32_t)i; op.sub = 0;
+      op.in0 = (uint32_t)cells.size();
+      for (uint32_t k = 0; k < PLAN_GEN_CELLS; k++) {
+        const uint32_t v = (uint32_t)key(gens[i].cells[k][0], gens[i].cells[k][1]);
+        if (cell_slot[v] == UNSET) cell_slot[v] = slots++;
+        cells.push_back(v);
+        gen_table.push_back(v);
+      }
+      op.in1 = op.out0 = op.in0 + PLAN_GEN_INS;
+      op.out1 = (uint32_t)cells.size();
       ops.push_back(op);
     }
     for (size_t row = 0; row < n; row++) row_ops((uint32_t)row);
@@ -248,8 +329,11 @@ struct Compiler {
       return r;
     }
     // ---- levels ----
-    auto op_row = [&](const HostOp &o) { return o.code == OP_SEED ? seeds[o.row].row : o.row; };
-    auto slot_of = [&](const HostOp &o, uint32_t k) -> uint32_t & { return cell_slot[key(op_row(o), cols[k])]; };
+    auto slot_of = [&](const HostOp &, uint32_t k) -> uint32_t & { return cell_slot[cells[k]]; };
+    // where op o keeps the writer bit of its output cell k: a generator in its table word, every other op in cell_slot
+    auto writer_word = [&](const HostOp &o, uint32_t k) -> uint32_t & {
+      return o.code == OP_EQUALITY ? gen_table[(size_t)PLAN_GEN_CELLS * o.row + (k - o.in0)] : cell_slot[cells[k]];
+    };
     std::vector<uint32_t> use_off(slots + 1, 0);
     for (auto &o : ops) {
       o.pending = o.in1 - o.in0;
@@ -275,8 +359,8 @@ struct Compiler {
         o.level = lvl;
         if (o.twin != UNSET) ops[o.twin].dead = true;
         for (uint32_t k = o.out0; k < o.out1; k++) {
-          uint32_t &s = slot_of(o, k);
-          if (slot_level[s & ~WRITER] < 0) { slot_level[s & ~WRITER] = lvl; fresh.push_back(s & ~WRITER); s |= WRITER; }
+          const uint32_t s = slot_of(o, k) & ~WRITER;
+          if (slot_level[s] < 0) { slot_level[s] = lvl; fresh.push_back(s); writer_word(o, k) |= WRITER; }
         }
         order.push_back(i);
       }
@@ -312,16 +396,18 @@ struct Compiler {
 
 }  // namespace planhost
 
-// the plan of circuit `in` for `seeds` (already through plan_seeds)
-inline PlanRefusal plan_compile_host(const PlanInput &in, const std::vector<PlanSeed> &seeds, HostPlan &out) {
+// the plan of circuit `in` for `seeds` (already through plan_seeds) and `gens` (already through plan_generators)
+inline PlanRefusal plan_compile_host(const PlanInput &in, const std::vector<PlanSeed> &seeds, const std::vector<PlanGenerator> &gens,
+                                     HostPlan &out) {
   planhost::Compiler K(in);
   if (PlanRefusal r = K.classes()) return r;
   std::vector<uint32_t> order;
-  if (PlanRefusal r = K.schedule(seeds, order, out.level_off)) return r;
+  if (PlanRefusal r = K.schedule(seeds, gens, order, out.level_off)) return r;
   out.ops.clear();
   out.ops.reserve(order.size());
   for (uint32_t i : order) out.ops.push_back((uint64_t)K.ops[i].row | ((uint64_t)(K.ops[i].code | (K.ops[i].sub << 8)) << 32));
   out.cell_slot.swap(K.cell_slot);
+  out.gen_table.swap(K.gen_table);
   out.levels = (uint32_t)out.level_off.size() - 1;
   out.slots = K.slots;
   out.widest = 0;

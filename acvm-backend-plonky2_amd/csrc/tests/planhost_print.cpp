@@ -7,6 +7,8 @@
 // first), sigma.  SEEDS: (row, col) pairs of 32-bit words.  OUT: one text line, then for a plan the three arrays as they are:
 //   plan <ops> <levels> <widest> <slots> <seeds>\n   cell_slot [R][n] u32, ops [ops] u64, level_off [levels + 1] u32
 //   refused <p2gpu_last_error's text>\n
+// With a third argument GENERATORS -- the generators that are no gate's own, p2gpu_generator records of nine 32-bit words
+// (kind, then four (row, col) pairs) -- the plan's generator table [generators][4] u32 follows level_off.
 #include <cstdio>
 #include <cstring>
 #include "../planhost.hpp"
@@ -33,7 +35,7 @@ template <class T> static std::vector<T> words(const std::vector<uint8_t> &b, si
 }
 
 int main(int argc, char **argv) {
-  if (argc != 3) { std::fprintf(stderr, "usage: planhost_print BLOB SEEDS\n"); return 2; }
+  if (argc != 3 && argc != 4) { std::fprintf(stderr, "usage: planhost_print BLOB SEEDS [GENERATORS]\n"); return 2; }
   const std::vector<uint8_t> blob = read_file(argv[1]), seed_bytes = read_file(argv[2]);
   const std::vector<uint32_t> h = words<uint32_t>(blob, 0, 64);
   const uint32_t d = h[2], W = h[3], R = h[4], NC = h[5], nsel = h[6], ng = h[23];
@@ -60,17 +62,26 @@ int main(int argc, char **argv) {
   }
   const std::vector<uint32_t> seed_words = words<uint32_t>(seed_bytes, 0, seed_bytes.size() / 4);
   const PlanInput in{d, R, W, NC - nsel, sigma.data(), consts.data() + (size_t)nsel * n, row_gate.data(), gates.data(), k_is.data()};
+  static_assert(sizeof(PlanGenerator) == 36, "nine words");
+  std::vector<PlanGenerator> gen_records, gens;
+  if (argc == 4) {
+    const std::vector<uint8_t> gen_bytes = read_file(argv[3]);
+    if (gen_bytes.size() % sizeof(PlanGenerator)) { std::fprintf(stderr, "unsupported generator file\n"); return 2; }
+    gen_records = words<PlanGenerator>(gen_bytes, 0, gen_bytes.size() / sizeof(PlanGenerator));
+  }
   std::vector<PlanSeed> seeds;
   HostPlan plan;
   PlanRefusal r = plan_seeds(d, W, seed_words.data(), seed_words.size() / 2, seeds);
-  if (!r) r = plan_compile_host(in, seeds, plan);
+  if (!r) r = plan_generators(d, R, gen_records.data(), gen_records.size(), gens);
+  if (!r) r = plan_compile_host(in, seeds, gens, plan);
   if (r) {
-    std::printf("refused %s\n", plan_refusal_text(r, d, W).c_str());
+    std::printf("refused %s\n", plan_refusal_text(r, d, W, R).c_str());
     return 0;
   }
   std::printf("plan %zu %u %u %u %zu\n", plan.ops.size(), plan.levels, plan.widest, plan.slots, seeds.size());
   std::fwrite(plan.cell_slot.data(), 4, plan.cell_slot.size(), stdout);
   std::fwrite(plan.ops.data(), 8, plan.ops.size(), stdout);
   std::fwrite(plan.level_off.data(), 4, plan.level_off.size(), stdout);
+  if (!plan.gen_table.empty()) std::fwrite(plan.gen_table.data(), 4, plan.gen_table.size(), stdout);
   return std::fflush(stdout) == 0 ? 0 : 2;
 }

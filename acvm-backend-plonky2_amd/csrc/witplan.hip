@@ -3,6 +3,8 @@
 //   p2gpu_witness_plan_create   the host compiler (planhost.hpp) over the circuit's tables as the device holds them -- a handle
 //                               from a blob and one from p2gpu_circuit_build hold the same sigma, hence give the same plan;
 //   p2gpu_witness_plan_build    the same plan compiled on the device (genplan.hip); the host one is its differential oracle.
+//   ..._create_gen / _build_gen the same two routines with a list of generators that are no gate's own (planhost.hpp states the
+//                               rules); the entry points above are their case of an empty list.
 // genwit.hip runs a plan.
 #include <chrono>
 #include "devclasses.hpp"
@@ -14,7 +16,7 @@ namespace {
 
 double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// The tail of both compilers: the plan's own buffers, filled from the three arrays (an upload for the host compiler, a copy
+// The tail of both compilers: the plan's own buffers, filled from the three arrays and the generator table (an upload for the host compiler, a copy
 // inside HBM and ONE read-back -- the op records name_contradiction needs -- for the device one).
 int plan_finish(p2gpu_witness_plan *p, const PlanArrays &a) {
   p2gpu_circuit *c = p->c;
@@ -24,6 +26,13 @@ int plan_finish(p2gpu_witness_plan *p, const PlanArrays &a) {
   HIP_TRY(p->level_off.alloc((size_t)a.levels + 1));
   HIP_TRY(p->cell_slot.alloc(tot));
   HIP_TRY(p->seed_cells.alloc(std::max<size_t>(1, n_seeds)));
+  HIP_TRY(p->gen_table.alloc(std::max<size_t>(1, PLAN_GEN_CELLS * a.n_gens)));
+  p->h_gen_table.resize(PLAN_GEN_CELLS * a.n_gens);
+  if (a.n_gens) {
+    HIP_TRY(hipMemcpyAsync(p->gen_table.p, a.gen_table, 4 * p->h_gen_table.size(), a.kind, c->stream));
+    if (a.kind == hipMemcpyHostToDevice) memcpy(p->h_gen_table.data(), a.gen_table, 4 * p->h_gen_table.size());
+    else HIP_TRY(hipMemcpyAsync(p->h_gen_table.data(), a.gen_table, 4 * p->h_gen_table.size(), hipMemcpyDeviceToHost, c->stream));
+  }
   if (int rc = plan_reserve(p, 1)) return rc;
   HIP_TRY(hipEventCreate(&p->ev0));
   HIP_TRY(hipEventCreate(&p->ev1));
@@ -54,10 +63,11 @@ int plan_compile(p2gpu_witness_plan *p) {
   HIP_TRY(hipStreamSynchronize(c->stream));
   const PlanInput in{c->d, c->R, c->W, ngc, sigma.data(), gconsts.data(), row_gate.data(), c->gates.data(), c->k_is.data()};
   HostPlan plan;
-  if (PlanRefusal r = plan_compile_host(in, p->h_seed_cells, plan)) return plan_refuse(c, r);
+  if (PlanRefusal r = plan_compile_host(in, p->h_seed_cells, p->h_gens, plan)) return plan_refuse(c, r);
   PlanArrays a;
   a.cell_slot = plan.cell_slot.data(); a.ops = reinterpret_cast<const OpRec *>(plan.ops.data()); a.level_off = plan.level_off.data();
   a.levels = plan.levels; a.slots = plan.slots; a.widest = plan.widest; a.n_ops = plan.ops.size();
+  a.gen_table = plan.gen_table.data(); a.n_gens = p->h_gens.size();
   return plan_finish(p, a);
 }
 
@@ -65,14 +75,16 @@ int plan_compile(p2gpu_witness_plan *p) {
 int plan_build(p2gpu_witness_plan *p) {
   classes::Scratch S;
   PlanArrays a;
-  if (int rc = plan_compile_device(p->c, p->h_seed_cells, S, a)) return rc;
+  if (int rc = plan_compile_device(p->c, p->h_seed_cells, p->h_gens, S, a)) return rc;
   return plan_finish(p, a);  // (S goes out of scope behind it: the plan holds what a host-compiled one holds)
 }
 
-// the front checks, the seed checks and the ownership of a half-made plan, for either compiler
-int plan_new(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, p2gpu_witness_plan **out, int (*compile)(p2gpu_witness_plan *)) {
+// the front checks, the seed and generator checks and the ownership of a half-made plan, for either compiler
+int plan_new(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, const p2gpu_generator *generators, size_t n_generators,
+             p2gpu_witness_plan **out, int (*compile)(p2gpu_witness_plan *)) {
+  static_assert(sizeof(p2gpu_generator) == sizeof(PlanGenerator) && P2GPU_GEN_EQUALITY == PLAN_GEN_EQUALITY, "planhost.hpp restates the record");
   if (out) *out = nullptr;
-  if (!c || !out || (n_seeds && !seed_cells)) return P2GPU_E_ARG;
+  if (!c || !out || (n_seeds && !seed_cells) || n_generators >= ((size_t)1 << 32)) return P2GPU_E_ARG;
   if (int rc = prover_handle(c)) return rc;
   if (!c->group.empty()) {
     set_err("p2gpu_witness_plan_create: a device group takes a wire matrix (every rank of a sharded proof reads all of it)");
@@ -86,7 +98,8 @@ int plan_new(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, p2gpu
   p->n_seeds = (uint32_t)n_seeds;
   int rc;
   try {
-    const PlanRefusal r = plan_seeds(c->d, c->W, seed_cells, n_seeds, p->h_seed_cells);
+    PlanRefusal r = plan_seeds(c->d, c->W, seed_cells, n_seeds, p->h_seed_cells);
+    if (!r) r = plan_generators(c->d, c->R, reinterpret_cast<const PlanGenerator *>(generators), n_generators, p->h_gens);
     rc = r ? plan_refuse(c, r) : compile(p);
   } catch (...) {
     p->release();
@@ -124,11 +137,32 @@ int plan_reserve(p2gpu_witness_plan *p, size_t batch) {
 extern "C" {
 
 int p2gpu_witness_plan_create(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, p2gpu_witness_plan **out) try {
-  return plan_new(c, seed_cells, n_seeds, out, plan_compile);
+  return plan_new(c, seed_cells, n_seeds, nullptr, 0, out, plan_compile);
 } P2GPU_CATCH
 
 int p2gpu_witness_plan_build(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, p2gpu_witness_plan **out) try {
-  return plan_new(c, seed_cells, n_seeds, out, plan_build);
+  return plan_new(c, seed_cells, n_seeds, nullptr, 0, out, plan_build);
+} P2GPU_CATCH
+
+int p2gpu_witness_plan_create_gen(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, const p2gpu_generator *generators,
+                                  size_t n_generators, p2gpu_witness_plan **out) try {
+  return plan_new(c, seed_cells, n_seeds, generators, n_generators, out, plan_compile);
+} P2GPU_CATCH
+
+int p2gpu_witness_plan_build_gen(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, const p2gpu_generator *generators,
+                                 size_t n_generators, p2gpu_witness_plan **out) try {
+  return plan_new(c, seed_cells, n_seeds, generators, n_generators, out, plan_build);
+} P2GPU_CATCH
+
+int p2gpu_witness_plan_export_generators(const p2gpu_witness_plan *p, uint32_t *table, size_t *n_generators) try {
+  if (!p || !n_generators) return P2GPU_E_ARG;
+  *n_generators = p->h_gens.size();
+  if (!table || p->h_gens.empty()) return P2GPU_OK;
+  const p2gpu_circuit *c = p->c;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(table, p->gen_table.p, 4 * (size_t)PLAN_GEN_CELLS * p->h_gens.size(), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return P2GPU_OK;
 } P2GPU_CATCH
 
 int p2gpu_witness_plan_export(const p2gpu_witness_plan *p, uint32_t *cell_slot, uint64_t *ops, uint32_t *level_off, size_t sizes[3]) try {

@@ -95,6 +95,9 @@ def load_library():
     lib.p2gpu_witness_plan_create.argtypes = [vp, vp, sz, ctypes.POINTER(vp)]
     lib.p2gpu_witness_plan_build.argtypes = [vp, vp, sz, ctypes.POINTER(vp)]
     lib.p2gpu_witness_plan_export.argtypes = [vp, vp, vp, vp, vp]
+    lib.p2gpu_witness_plan_create_gen.argtypes = [vp, vp, sz, vp, sz, ctypes.POINTER(vp)]
+    lib.p2gpu_witness_plan_build_gen.argtypes = [vp, vp, sz, vp, sz, ctypes.POINTER(vp)]
+    lib.p2gpu_witness_plan_export_generators.argtypes = [vp, vp, ctypes.POINTER(sz)]
     lib.p2gpu_witness_plan_destroy.argtypes = [vp]
     lib.p2gpu_witness_plan_destroy.restype = None
     lib.p2gpu_witness_plan_info.argtypes = [vp, vp, vp]
@@ -430,11 +433,14 @@ class CircuitData:
         _check(self._lib.p2gpu_fill_witness(self._h, ctypes.c_void_p(wires_dev.data_ptr())))
         return wires_dev
 
-    def witness_plan(self, seed_cells, compile="host"):
+    def witness_plan(self, seed_cells, compile="host", generators=None):
         """``p2gpu_witness_plan_create``: the plan that turns the values of `seed_cells` ([(row, col)]: the cells the
         caller assigns per proof, ``pw.set_target`` on the Rust side) into the whole witness on the GPU.
-        ``compile="device"``: the same plan through ``p2gpu_witness_plan_build``, compiled on the GPU."""
-        return WitnessPlan(self, seed_cells, compile=compile)
+        ``compile="device"``: the same plan through ``p2gpu_witness_plan_build``, compiled on the GPU.
+        ``generators``: the generators that are no gate's own, [("equality", (cell_x, cell_y, cell_equal, cell_inv))] with
+        (row, col) cells (``translate.CircuitBuilder.generators()``); the plan then comes from
+        ``p2gpu_witness_plan_create_gen`` / ``_build_gen``."""
+        return WitnessPlan(self, seed_cells, compile=compile, generators=generators)
 
     def prove_routed(self, routed, public_inputs=()):
         """Prove from the routed columns only ([num_routed_wires][degree], host): gate-internal
@@ -512,7 +518,9 @@ class WitnessPlan:
     """Witness generation on the GPU for one circuit and one set of seed cells (``p2gpu_witness_plan``).  Close it before
     the circuit."""
 
-    def __init__(self, circuit, seed_cells, compile="host"):
+    GENERATOR_KINDS = {"equality": 0}   # p2gpu.h P2GPU_GEN_EQUALITY
+
+    def __init__(self, circuit, seed_cells, compile="host", generators=None):
         if compile not in ("host", "device"):
             raise P2GpuError(-7, f'compile must be "host" or "device", not {compile!r}')
         self._cd, self._lib = circuit, circuit._lib
@@ -522,8 +530,21 @@ class WitnessPlan:
         cells = cells.astype(np.uint32)
         self.num_seeds = len(cells)
         self._h = ctypes.c_void_p()
-        make = self._lib.p2gpu_witness_plan_build if compile == "device" else self._lib.p2gpu_witness_plan_create
-        _check(make(circuit._h, cells.ctypes.data if cells.size else None, len(cells), ctypes.byref(self._h)))
+        if generators is None:
+            make = self._lib.p2gpu_witness_plan_build if compile == "device" else self._lib.p2gpu_witness_plan_create
+            _check(make(circuit._h, cells.ctypes.data if cells.size else None, len(cells), ctypes.byref(self._h)))
+            return
+        # p2gpu_generator records: kind, then four (row, col) pairs; a kind may be given by its number
+        recs = np.zeros((len(generators), 9), dtype=np.int64)
+        for i, (kind, gcells) in enumerate(generators):
+            recs[i, 0] = self.GENERATOR_KINDS.get(kind, kind) if isinstance(kind, str) else kind
+            recs[i, 1:] = np.array(list(gcells), dtype=np.int64).reshape(8)
+        if recs.size and (recs.min() < 0 or recs.max() >= 1 << 32):
+            raise P2GpuError(-7, "a generator is a kind and four (row, col) cells of unsigned 32-bit numbers")
+        recs = np.ascontiguousarray(recs.astype(np.uint32))
+        make = self._lib.p2gpu_witness_plan_build_gen if compile == "device" else self._lib.p2gpu_witness_plan_create_gen
+        _check(make(circuit._h, cells.ctypes.data if cells.size else None, len(cells), recs.ctypes.data if recs.size else None, len(recs),
+                    ctypes.byref(self._h)))
 
     def _values(self, values):
         v = _u64(np.array([int(x) for x in values], dtype=np.uint64))
@@ -549,6 +570,16 @@ class WitnessPlan:
         level_off = np.zeros(sizes[2], dtype=np.uint32)
         _check(self._lib.p2gpu_witness_plan_export(self._h, cell_slot.ctypes.data, ops.ctypes.data, level_off.ctypes.data, sizes))
         return cell_slot.reshape(self._cd.num_routed_wires, self._cd.degree), ops[:sizes[1]], level_off
+
+    def export_generators(self):
+        """``p2gpu_witness_plan_export_generators``: the plan's generator table [generators][4] uint32, cell key
+        (col << degree_bits | row) | bit 31 = this generator writes the cell's slot."""
+        count = ctypes.c_size_t()
+        _check(self._lib.p2gpu_witness_plan_export_generators(self._h, None, ctypes.byref(count)))
+        table = np.zeros((count.value, 4), dtype=np.uint32)
+        if count.value:
+            _check(self._lib.p2gpu_witness_plan_export_generators(self._h, table.ctypes.data, ctypes.byref(count)))
+        return table
 
     def generate(self, values):
         """``p2gpu_generate_witness``: the wire matrix [num_wires][degree] as an int64 tensor on the circuit's GPU."""

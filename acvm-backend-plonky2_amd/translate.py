@@ -5,13 +5,17 @@ Mirrors, with the reference's names:
   * ``CircuitBuilderFromAcirToPlonky2`` (plonky2-backend/src/circuit_translation/mod.rs:37-330):
     `translate_circuit`, `binary_number_target_for_witness/_constant`, `convert_binary_number_to_number`;
   * ``AssertZeroTranslator`` (assert_zero_translator.rs:25-38, 60-115);
+  * ``MemoryOperationsTranslator`` (memory_translator.rs:11-171): MemoryInit, MemoryOp reads (RandomAccessGate) and
+    writes (`is_equal` + `_if` per position), the <= check on the index;
   * ``Sha256CompressionTranslator`` (sha256_translator.rs:61-273) and ``BinaryDigitsTarget``
     (binary_digits_target.rs: rotate_right 19-41, shift_right 43-64, choose 66-83, majority 85-106, xor/and
     121-149, bit_xor 181-187, add_module_32_bits 189-224);
   * the part of plonky2 0.2.2's ``CircuitBuilder`` those reach (gadgets/arithmetic.rs `arithmetic` with its
     constant-folding special cases, `mul/add/sub/mul_sub/mul_add/mul_const_add`, `and/or/not/select`,
     `assert_bool`, gadgets/split_join.rs `split_le` / `le_sum` with BaseSumGate<2>, constants in ConstantGates,
-    the PublicInputGate row of `build()`, Noop padding) -- recollection of an un-vendored crate, checked by what
+    the PublicInputGate row of `build()`, Noop padding; for the memory opcodes `is_equal` with its EqualityGenerator,
+    `_if`, `random_access` with RandomAccessGate rows and their extra constants -- these UNPINNED, see their docstrings)
+    -- recollection of an un-vendored crate, checked by what
     can be checked here: every circuit it emits is satisfiable only by the right values (the reference's own
     SHA-256 compression vector, tests/test_sha256_internal.rs:481-549, comes out of it), and the oracle and the
     GPU prove it to identical bytes.
@@ -19,7 +23,8 @@ Mirrors, with the reference's names:
 What it is NOT: an ACIR *reader*.  The reference deserialises gzip + bincode `Program` bytes through the acvm
 crate (noir_and_plonky2_serialization.rs:42-64); no compiled program exists in the tree to test a reader on, so
 programs are given as Python data: [("assert_zero", mul_terms, linear, q_c), ("sha256_compression", inputs16,
-hash8, outputs8), ("range", w, num_bits), ("and" | "xor", lhs, rhs, output, num_bits)] (mod.rs:131-155).  Public parameters (which add PoseidonGate rows in `build()`) are not supported here.
+hash8, outputs8), ("range", w, num_bits), ("and" | "xor", lhs, rhs, output, num_bits), ("memory_init", block_id, [witnesses]),
+("memory_op", block_id, operation, index_witness, value_witness)] (mod.rs:105-155).  Public parameters (which add PoseidonGate rows in `build()`) are not supported here.
 
 Host-side Python by design: translation runs once per circuit, off the hot path (north_star keeps this layer in
 Rust; this file exists so that the named SHA256 circuit can be built and proved without it).
@@ -31,7 +36,9 @@ from .synth import poseidon_gate_row
 
 P = 0xFFFFFFFF00000001
 NUM_WIRES, NUM_ROUTED, NUM_OPS, BASE_SUM_LIMBS = 234, 80, 20, 63
-G_NOOP, G_CONSTANT, G_PUBLIC_INPUT, G_ARITHMETIC, G_BASE_SUM, G_POSEIDON = 0, 1, 2, 3, 4, 6
+G_NOOP, G_CONSTANT, G_PUBLIC_INPUT, G_ARITHMETIC, G_BASE_SUM, G_RANDOM_ACCESS, G_POSEIDON = 0, 1, 2, 3, 4, 5, 6
+NUM_CONSTANTS = 2            # CircuitConfig::num_constants of both configurations
+GEN_EQUALITY = 0             # p2gpu.h P2GPU_GEN_EQUALITY
 
 
 class CircuitBuilder:
@@ -49,6 +56,7 @@ class CircuitBuilder:
         self.free_arith = {}      # (c0, c1) -> row with a free slot
         self.arith_results = {}   # (c0, c1, m0, m1, addend) -> output target of the identical earlier operation
         self.events = []          # witness generators in creation order
+        self.free_ra = {}         # bits -> RandomAccess row with a free copy
         self.rng = np.random.default_rng(seed)
         self._lay = None          # what _layout() made
 
@@ -183,6 +191,50 @@ class CircuitBuilder:
     def select(self, b, x, y):
         return self.mul_sub(b, x, self.mul_sub(b, y, y))
 
+    def _if(self, b, x, y):
+        return self.select(b, x, y)
+
+    def is_equal(self, x, y):
+        """gadgets/arithmetic.rs `is_equal` -- UNPINNED: the order of its steps is a recollection of plonky2 0.2.2.  The
+        EqualityGenerator it registers belongs to no gate row: its four targets lie in ArithmeticGate rows (event "equal")."""
+        zero = self.zero()
+        equal = self.add_virtual_target()              # add_virtual_bool_target_unsafe
+        not_equal = self.not_(equal)
+        inv = self.add_virtual_target()
+        self.events.append(("equal", x, y, equal, inv))
+        diff = self.sub(x, y)
+        not_equal_check = self.mul(diff, inv)
+        diff_normalized = self.mul(diff, equal)
+        self.connect(diff_normalized, zero)
+        self.connect(not_equal, not_equal_check)
+        return equal
+
+    # -- gadgets/random_access.rs, gates/random_access.rs ------------------------------------------
+    def _ra_shape(self, bits):
+        """RandomAccessGate::new_from_config -- UNPINNED (recollection): (copies, extra constants)."""
+        vec = 1 << bits
+        copies = min(NUM_ROUTED // (2 + vec), self.num_wires // (2 + vec + bits))
+        return copies, min(NUM_ROUTED - (2 + vec) * copies, NUM_CONSTANTS)
+
+    def random_access(self, index, v):
+        """UNPINNED (recollection of plonky2 0.2.2): a copy of a RandomAccessGate row shared per `bits` until it is full
+        (find_slot); a fresh virtual target, connected to the claimed-element wire, is returned."""
+        v = list(v)
+        bits = (len(v) - 1).bit_length()
+        assert len(v) == 1 << bits, "random_access: the list's length must be a power of two"
+        if len(v) == 1:
+            return v[0]
+        r = self.free_ra.get(bits)
+        copies, extra = self._ra_shape(bits)
+        if r is None or len(self.rows[r]["copies"]) == copies:
+            r = len(self.rows)
+            self.rows.append({"kind": "ra", "bits": bits, "num_copies": copies, "extra": extra, "copies": []})
+            self.free_ra[bits] = r
+        claimed = self.add_virtual_target()
+        self.rows[r]["copies"].append((index, claimed, v))
+        self.events.append(("ra", index, v, claimed))
+        return claimed
+
     # -- gadgets/split_join.rs ----------------------------------------------------------------------
     def _base_sum_row(self, num_limbs):
         row = {"kind": "basesum", "L": num_limbs, "sum": self.add_virtual_target(),
@@ -229,6 +281,15 @@ class CircuitBuilder:
         if self._lay is not None:
             return self._lay
         zero = self.zero()
+        # fill_batched_gates: the unused copies of a RandomAccess row read position `zero` of a list of `zero`s into a fresh
+        # claimed element
+        for g in self.rows:
+            if g["kind"] == "ra":
+                while len(g["copies"]) < g["num_copies"]:
+                    claimed = self.add_virtual_target()
+                    lst = [zero] * (1 << g["bits"])
+                    g["copies"].append((zero, claimed, lst))
+                    self.events.append(("ra", zero, lst, claimed))
         # circuit_builder.rs build(): the public inputs are hashed IN CIRCUIT -- hash_n_to_hash_no_pad::<PoseidonHash>, an
         # overwrite-mode sponge: one PoseidonGate row per 8 inputs, swap wire tied to zero, the state starts as twelve copies of
         # `zero` -- and the first four outputs are routed to a PublicInputGate added right behind; no public inputs: the hash is
@@ -246,16 +307,21 @@ class CircuitBuilder:
         pi_row = len(rows)
         # ConstantGate rows: plonky2 walks constants_to_targets sorted by the constant's canonical value, two per gate (both
         # reference circuits: 0, 1 | 2^63, p - 1 and 0, 1 | p - 1, -)
+        # UNPINNED (recollected rule of build()): in that order the constants go first to the extra-constant wires of the gates
+        # that have some (RandomAccessGate), rows in creation order, and only the rest to ConstantGate rows
         const_list = sorted(self.consts.items())
+        extra_wires = [(r, i) for r, g in enumerate(rows) if g["kind"] == "ra" for i in range(g["extra"])]
+        extra_consts, const_list = const_list[:len(extra_wires)], const_list[len(extra_wires):]
         const_rows = (len(const_list) + 1) // 2
         used = pi_row + 1 + const_rows
         d = max(2, (used - 1).bit_length())
         n = 1 << d
         # gate set, sorted by (degree, id) like CommonCircuitData.gates
         kinds = {("noop",)} if used < n else set()
-        kinds |= {("const",), ("pi",)}
+        kinds |= {("const",), ("pi",)} if const_rows else {("pi",)}
         for r in rows:
-            kinds.add(("arith",) if r["kind"] == "arith" else ("poseidon",) if r["kind"] == "poseidon" else ("basesum", r["L"]))
+            kinds.add(("arith",) if r["kind"] == "arith" else ("poseidon",) if r["kind"] == "poseidon" else
+                      ("ra", r["bits"]) if r["kind"] == "ra" else ("basesum", r["L"]))
         spec = {("noop",): (0, "NoopGate", (G_NOOP, (0, 0, 0, 0), 0, 0)),
                 ("const",): (1, "ConstantGate { num_consts: 2 }", (G_CONSTANT, (2, 0, 0, 0), 1, 2)),
                 ("pi",): (1, "PublicInputGate", (G_PUBLIC_INPUT, (0, 0, 0, 0), 1, 0)),
@@ -265,6 +331,12 @@ class CircuitBuilder:
         for k in kinds:
             if k[0] == "basesum":
                 spec[k] = (2, "BaseSumGate { num_limbs: %d } + Base: 2" % k[1], (G_BASE_SUM, (2, k[1], 0, 0), 2, 0))
+            elif k[0] == "ra":
+                # UNPINNED: the id as plonky2 0.2.2 prints it, format!("{self:?}<D={D}>"), as recollected
+                copies, extra = self._ra_shape(k[1])
+                spec[k] = (k[1] + 1, "RandomAccessGate { bits: %d, num_copies: %d, num_extra_constants: %d, _phantom: "
+                           "PhantomData<plonky2_field::goldilocks_field::GoldilocksField> }<D=2>" % (k[1], copies, extra),
+                           (G_RANDOM_ACCESS, (k[1], copies, extra, 0), k[1] + 1, extra))
         order = sorted(kinds, key=lambda k: (spec[k][0], spec[k][1]))
         index = {k: i for i, k in enumerate(order)}
         gates = [spec[k][2] for k in order]
@@ -290,6 +362,15 @@ class CircuitBuilder:
                 for j, t in enumerate(g["out"]):
                     put(t, r, 12 + j)
                 put(g["swap"], r, 24)
+            elif g["kind"] == "ra":
+                row_gate[r] = index[("ra", g["bits"])]
+                g["row"] = r
+                vec = 1 << g["bits"]
+                for k, (idx, claimed, lst) in enumerate(g["copies"]):
+                    put(idx, r, (2 + vec) * k)
+                    put(claimed, r, (2 + vec) * k + 1)
+                    for j, t in enumerate(lst):
+                        put(t, r, (2 + vec) * k + 2 + j)
             else:
                 row_gate[r] = index[("basesum", g["L"])]
                 put(g["sum"], r, 0)
@@ -298,6 +379,9 @@ class CircuitBuilder:
         row_gate[pi_row] = index[("pi",)]
         for i in range(4):                          # (no public inputs: four copies of `zero`)
             put(pi_hash[i], pi_row, i)
+        for (c, t), (r, i) in zip(extra_consts, extra_wires):
+            row_consts[i, r] = c
+            put(t, r, (2 + (1 << rows[r]["bits"])) * rows[r]["num_copies"] + i)
         for i, (c, t) in enumerate(const_list):
             r = pi_row + 1 + i // 2
             row_gate[r] = index[("const",)]
@@ -314,7 +398,7 @@ class CircuitBuilder:
         blob = build_blob(d, gates, row_gate, row_consts, np.array(copies, dtype=np.uint32).reshape(-1, 4),
                           num_public_inputs=len(self.public_inputs), num_wires=self.num_wires)
         self.pi_row = pi_row
-        self._lay = (blob, rows, pi_row, const_list, cells, n)
+        self._lay = (blob, rows, pi_row, extra_consts + const_list, cells, n)
         return self._lay
 
     def build(self, witness_values):
@@ -351,6 +435,23 @@ class CircuitBuilder:
                     ev[1]["wires"] = poseidon_gate_row(ins)
                     for j, t in enumerate(ev[1]["out"]):
                         self._set(val, t, int(ev[1]["wires"][12 + j]))
+                elif ev[0] == "equal":
+                    _, x, y, equal, inv = ev
+                    a, b = val.get(self.find(x)), val.get(self.find(y))
+                    if a is None or b is None:
+                        rest.append(ev)
+                        continue
+                    self._set(val, equal, 1 if a == b else 0)
+                    self._set(val, inv, pow((a - b) % P, P - 2, P))      # (0 when they are equal)
+                elif ev[0] == "ra":
+                    _, idx, lst, claimed = ev
+                    vs = [val.get(self.find(t)) for t in [idx] + lst]
+                    if any(v is None for v in vs):
+                        rest.append(ev)
+                        continue
+                    if vs[0] >= len(lst):
+                        raise ValueError("unsatisfiable: a random access reads position %d of %d" % (vs[0], len(lst)))
+                    self._set(val, claimed, vs[1 + vs[0]])
                 elif ev[0] == "split":
                     v = val.get(self.find(ev[1]))
                     if v is None:
@@ -383,6 +484,13 @@ class CircuitBuilder:
                 raise ValueError("a wire has no value")
             for (r, c) in cl:
                 wires[c, r] = v
+        for g in rows:                              # RandomAccessGenerator: the index bits, in the non-routed wires
+            if g["kind"] == "ra":
+                bits, vec = g["bits"], 1 << g["bits"]
+                routed = (2 + vec) * g["num_copies"] + g["extra"]
+                for k, (idx, _, _) in enumerate(g["copies"]):
+                    for i in range(bits):
+                        wires[routed + k * bits + i, g["row"]] = (val[self.find(idx)] >> i) & 1
         # circuit_builder.rs randomize_unused_pi_wires: every wire of the PublicInputGate row after the hash, routed
         # or not, gets a random value (so no wire column of a real witness is zero in every row)
         wires[4:NUM_ROUTED, pi_row] = self.rng.integers(0, P, size=NUM_ROUTED - 4, dtype=np.uint64)
@@ -402,6 +510,10 @@ class CircuitBuilder:
                 derived.add(self.find(ev[6]))
             elif ev[0] == "poseidon":
                 derived.update(self.find(t) for t in ev[1]["out"])
+            elif ev[0] == "equal":
+                derived.update((self.find(ev[3]), self.find(ev[4])))
+            elif ev[0] == "ra":
+                derived.add(self.find(ev[3]))
             elif ev[0] == "split":
                 assert len(ev[2]) == 1, "a split over several BaseSum rows spans rows: not a gate-local generator"
                 derived.update(self.find(t) for t in ev[2][0]["limbs"])
@@ -431,6 +543,19 @@ class CircuitBuilder:
         out = [given[rt] for rt in roots]
         out += [int(x) for x in self.rng.integers(0, P, size=NUM_ROUTED - 4, dtype=np.uint64)]
         out += [int(x) for x in self.rng.integers(0, P, size=self.num_wires - NUM_ROUTED, dtype=np.uint64)]
+        return out
+
+    def generators(self):
+        """The generators that are no gate's own, for CircuitData.witness_plan(..., generators=): [("equality", (cell_x, cell_y,
+        cell_equal, cell_inv))] in creation order; a target's cell is the first cell of its copy class."""
+        _, _, _, _, cells, _ = self._layout()
+        out = []
+        for ev in self.events:
+            if ev[0] == "equal":
+                cl = [cells.get(self.find(t)) for t in ev[1:]]
+                if any(c is None for c in cl):
+                    raise ValueError("is_equal: a target of the equality generator lies in no gate row")
+                out.append(("equality", tuple(c[0] for c in cl)))
         return out
 
     def _set(self, val, t, v):
@@ -517,12 +642,80 @@ SHA256_K = [
     0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2]
 
 
+class MemoryOperationsTranslator:
+    """memory_translator.rs:11-171, quirks kept: the block is padded with `zero` to a power of two and its real length kept
+    beside it; the `predicate` of a MemoryOp is ignored; a write replaces EVERY position of the padded block."""
+
+    def __init__(self, builder, witness_target_map, memory_blocks):
+        self.builder, self.witness_target_map, self.memory_blocks = builder, witness_target_map, memory_blocks
+
+    def _target(self, w):
+        if w not in self.witness_target_map:
+            self.witness_target_map[w] = self.builder.add_virtual_target()
+        return self.witness_target_map[w]
+
+    @staticmethod
+    def _single_witness(e, what):
+        """Expression::to_witness (the reference unwraps its None): `e` is a witness index, or an expression (mul_terms,
+        linear, q_c) that is one witness with coefficient one and no constant term."""
+        if isinstance(e, (int, np.integer)):
+            return int(e)
+        mul_terms, linear, q_c = e
+        if mul_terms or len(linear) != 1 or linear[0][0] % P != 1 or q_c % P != 0:
+            raise ValueError("memory operation: the %s is not a single witness" % what)
+        return linear[0][1]
+
+    # memory_translator.rs:128-151
+    def translate_memory_init(self, init, block_id):
+        targets = [self._target(w) for w in init]
+        real = len(targets)
+        padded = 1 << (real - 1).bit_length() if real else 0
+        targets += [self.builder.zero() for _ in range(padded - real)]
+        self.memory_blocks[block_id] = (targets, real)
+
+    # memory_translator.rs:55-83
+    @staticmethod
+    def add_restrictions_to_assert_target_is_less_or_equal_to(max_allowed_value, target_index, builder):
+        binary = [int(c) for c in format(max_allowed_value, "b")]
+        bits = list(reversed(builder.split_le(target_index, len(binary))))
+        acc = builder.one()
+        for bound_bit, bit in zip(binary, bits):
+            if bound_bit == 0:
+                builder.assert_zero(builder.mul(bit, acc))
+            else:
+                acc = builder.mul(acc, bit)
+
+    # memory_translator.rs:30-51
+    def translate_memory_op(self, block_id, operation, index, value):
+        wi, wv = self._single_witness(index, "index"), self._single_witness(value, "value")
+        self._target(wi)
+        self._target(wv)
+        if isinstance(operation, tuple):
+            if operation[0] or operation[1]:
+                raise ValueError("memory operation: the operation is not a constant")
+            operation = operation[2]
+        if not isinstance(operation, (int, np.integer)):
+            raise ValueError("memory operation: the operation is not a constant")
+        block, real = self.memory_blocks[block_id]
+        self.add_restrictions_to_assert_target_is_less_or_equal_to(real - 1, self._target(wi), self.builder)
+        if operation % P == 0:      # :115-125
+            self.witness_target_map[wv] = self.builder.random_access(self._target(wi), list(block))
+        elif operation % P == 1:    # :89-112
+            b = self.builder
+            for position in range(len(block)):
+                here = b.is_equal(self._target(wi), b.constant(position))
+                block[position] = b._if(here, self._target(wv), block[position])
+        else:
+            raise ValueError("Backend encountered unknown memory operation code (nor 0 or 1)")
+
+
 class CircuitBuilderFromAcirToPlonky2:
     """mod.rs:37-330, for programs given as Python data (see the module docstring)."""
 
     def __init__(self, num_wires=NUM_WIRES):
         self.builder = CircuitBuilder(num_wires=num_wires)
         self.witness_target_map = {}
+        self.memory_blocks = {}     # block id -> ([targets, padded to a power of two], real length)  (mod.rs:47)
 
     def _target(self, w):
         if w not in self.witness_target_map:
@@ -619,6 +812,10 @@ class CircuitBuilderFromAcirToPlonky2:
                 self.translate_range(*op[1:])
             elif op[0] in ("and", "xor"):
                 self.translate_bitwise(*op[1:], xor=op[0] == "xor")
+            elif op[0] == "memory_init":
+                MemoryOperationsTranslator(self.builder, self.witness_target_map, self.memory_blocks).translate_memory_init(op[2], op[1])
+            elif op[0] == "memory_op":
+                MemoryOperationsTranslator(self.builder, self.witness_target_map, self.memory_blocks).translate_memory_op(*op[1:])
             else:
                 raise NotImplementedError(op[0])
 
@@ -637,6 +834,11 @@ class CircuitBuilderFromAcirToPlonky2:
         _, roots = b._seed_classes()
         roots = set(roots)
         return b.seed_cells(), b.seed_values({t: v for t, v in vals.items() if b.find(t) in roots})
+
+    def witness_generators(self):
+        """The generators that are no gate's own (the equality generators of the memory writes), for
+        CircuitData.witness_plan(cells, generators=...) beside witness_seeds()."""
+        return self.builder.generators()
 
     def blob(self):
         """The circuit blob alone (build() without the witness)."""

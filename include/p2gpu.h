@@ -20,6 +20,10 @@
  *   p2gpu_witness_plan_create / p2gpu_witness_plan_build / p2gpu_generate_witness / p2gpu_prove_seeds
  *                          <- all of `generate_partial_witness` (plonky2 iop/generator.rs, called by `prove`): the caller
  *                             hands over the `pw.set_target` values only, generators and copy constraints run on the GPU
+ *   p2gpu_witness_plan_create_gen / p2gpu_witness_plan_build_gen
+ *                          <- the same plans for a circuit that holds generators which are no gate's own: the
+ *                             EqualityGenerators of `builder.is_equal` (gadgets/arithmetic.rs), which the memory writes of
+ *                             the ACIR translation are made of (circuit_translation/memory_translator.rs:89-112)
  *   p2gpu_generate_witness_batch
  *                          <- the same for many value sets of one circuit at once (the reference has no counterpart: it
  *                             calls `prove` once per witness)
@@ -182,6 +186,26 @@ int p2gpu_witness_plan_create(p2gpu_circuit *c, const uint32_t *seed_cells /* [n
  * either.  Nothing of the circuit is read back; the scratch is released before it returns. */
 int p2gpu_witness_plan_build(p2gpu_circuit *c, const uint32_t *seed_cells /* [n_seeds][2] = (row, col) */, size_t n_seeds,
                              p2gpu_witness_plan **out);
+/* ---- generators that are no gate's own ----
+ * plonky2's `is_equal` registers an EqualityGenerator whose four targets lie in other gates' rows (the memory writes of the ACIR
+ * translation are built from it); no gate row lists it, so the caller does: the Rust side passes the EqualityGenerators of
+ * `builder.generators`.  The two entry points above are the case n_generators == 0 of these two; every rule of
+ * the plan holds for a generator as for a row's op: it is created behind the seeds and in front of the rows, its
+ * cells get value slots, the first op by level and creation order that reaches a slot writes it and every other one compares.
+ * P2GPU_E_ARG, worded in p2gpu_last_error: an unknown kind, a cell outside [n] x [num_routed_wires] (with the generator's index
+ * and the cell), n_generators > 0 with a null list; an input cell that nothing writes is the "a seed is missing" refusal.  A
+ * contradiction of a generator at p2gpu_generate_witness reads "generator <i>: cell (row, column)".  Only the equality generator
+ * is built; the record has a kind and four cells so that a later one fits. */
+#define P2GPU_GEN_EQUALITY 0   /* cells: x, y (read), equal, inv (set): equal = (x == y), inv = x == y ? 0 : 1 / (x - y) */
+typedef struct { uint32_t kind; uint32_t cells[4][2]; /* (row, col), routed columns only */ } p2gpu_generator;
+int p2gpu_witness_plan_create_gen(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds,
+                                  const p2gpu_generator *generators, size_t n_generators, p2gpu_witness_plan **out);
+/* the same arguments: compiled on the device */
+int p2gpu_witness_plan_build_gen(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds,
+                                 const p2gpu_generator *generators, size_t n_generators, p2gpu_witness_plan **out);
+/* the plan's generator table, read back: [n_generators][4] words, cell key (col << d | row) | bit 31 = this generator writes the
+ * cell's slot (its writer bits live here, not in cell_slot).  *n_generators is always filled; with table NULL nothing else happens */
+int p2gpu_witness_plan_export_generators(const p2gpu_witness_plan *p, uint32_t *table, size_t *n_generators);
 /* The plan's three device arrays, read back: cell_slot [num_routed_wires][n] (the value slot of every routed cell, 0xFFFFFFFF:
  * none, bit 31: this cell's op writes the slot), ops [n_ops] (row | (code | sub << 8) << 32, by level and creation order),
  * level_off [levels + 1].  sizes = { num_routed_wires * n, n_ops, levels + 1 } is always filled; with all three pointers NULL
