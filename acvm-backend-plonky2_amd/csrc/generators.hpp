@@ -9,6 +9,7 @@
 // Restated generators: witness.hip's header lists their sources.  gen_base_sum_join is the one le_sum adds
 // (gadgets/split_join.rs: the sum is computed from the bits), every other body is what fill_witness_kernel always ran.
 #pragma once
+#include "bigdiv.hpp"
 #include "internal.hpp"
 #include "poseidon.hpp"
 
@@ -71,6 +72,34 @@ __device__ __forceinline__ void gen_equality(A &a) {
   const gl_t diff = gl_sub(a.get(0), a.get(1));
   a.set(2, diff == 0 ? 1 : 0);
   a.set(3, gl_inv(diff));
+}
+
+// BigUintDivRemGenerator (plonky2_ecdsa/biguint/biguint.rs:317-344, registered by `div_rem_biguint` :246): no gate's own either.
+// Its accessor numbers the cells a[0 .. la), b[0 .. lb) (read), div[0 .. ld), rem[0 .. lr) (set), least significant limb first;
+// shape = {la, lb, ld, lr} as the plan checked it (la <= 32, lb <= 16).  The limbs are folded as `get_biguint_target` folds them
+// (a limb >= 2^32 carries), divided by bigdiv.hpp, and written as 32-bit digits.  Where upstream panics the walk rejects: b = 0
+// on b's first cell; a quotient or remainder with more digits than its target has limbs on that target's top limb (the
+// quotient of a target without limbs: on a's first cell).  Not forced inline: its word arrays live in private memory, and the
+// caller keeps them out of the other generators' frames (genwit.hip).
+template <class A>
+__device__ void gen_biguint_divrem(A &a, const uint32_t shape[4]) {
+  const uint32_t la = shape[0], lb = shape[1], ld = shape[2], lr = shape[3];
+  BigDiv w;
+  for (uint32_t i = 0; i < la; i++) w.push_a(i, a.get(i));
+  w.finish_a(la);
+  for (uint32_t i = 0; i < lb; i++) w.push_b(i, a.get(la + i));
+  w.finish_b(lb);
+  if (!w.divide()) {
+    a.reject(la);
+    return;
+  }
+  for (uint32_t i = 0; i < ld; i++) a.set(la + lb + i, w.quotient_word(i));
+  for (uint32_t i = 0; i < lr; i++) a.set(la + lb + ld + i, w.remainder_word(i));
+  bool q_over = false, r_over = false;
+  for (uint32_t i = ld; i < w.nq; i++) q_over |= w.quotient_word(i) != 0;
+  for (uint32_t i = lr; i < w.nv; i++) r_over |= w.remainder_word(i) != 0;
+  if (q_over) a.reject(ld ? la + lb + ld - 1 : 0);
+  if (r_over) a.reject(la + lb + ld + lr - 1);
 }
 
 // prc: the 360 round constants (wave-uniform index -> scalar loads)

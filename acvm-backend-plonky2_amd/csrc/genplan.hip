@@ -128,7 +128,8 @@ __global__ void plan_seed_slots_kernel(const uint2 *seeds, uint32_t S, uint32_t 
   cell_slot[((size_t)c.y << d) + c.x] = (uint32_t)*base + scan[i];
 }
 
-// the generators that are no gate's own: entry e = generator * 4 + cell position names cell gkeys[e].  first[key] = the smallest
+// the generators that are no gate's own: entry e = the generator's offset + cell position names cell gkeys[e] (the flat list of
+// the checked generators, PlanGenList).  first[key] = the smallest
 // entry that names a cell without a slot (cleared for exactly the named cells: nothing else of `first` is read)
 __global__ void plan_gen_clear_kernel(const uint32_t *gkeys, uint32_t NE, uint32_t *first) {
   const uint32_t e = blockIdx.x * TPB + threadIdx.x;
@@ -147,9 +148,10 @@ __global__ void plan_gen_slots_kernel(const uint32_t *gkeys, uint32_t NE, const 
   const uint32_t e = blockIdx.x * TPB + threadIdx.x;
   if (e < NE && flag[e]) cell_slot[gkeys[e]] = (uint32_t)*base + scan[e];
 }
-__global__ void plan_gen_ops_kernel(uint32_t S, uint32_t G, OpRec *recs) {
+// gmeta[g] = input cells | op code << 16
+__global__ void plan_gen_ops_kernel(uint32_t S, uint32_t G, const uint32_t *gmeta, OpRec *recs) {
   const uint32_t i = blockIdx.x * TPB + threadIdx.x;
-  if (i < G) recs[S + i] = make_uint2(i, OP_EQUALITY);
+  if (i < G) recs[S + i] = make_uint2(i, gmeta[i] >> 16);
 }
 
 // what the compilers read of the circuit
@@ -231,14 +233,16 @@ struct OpView {
   const OpRec *recs;
   const uint2 *seeds;
   const uint32_t *cell_slot;
-  const uint32_t *gkeys;  // [generators][4] cell keys
-  uint32_t *gen_table;    // [generators][4] the same with the writer bits the schedule sets
+  const uint32_t *gkeys;  // the generators' cell keys, generator g's from goff[g] on: its gmeta[g] & 0xFFFF inputs, then its outputs
+  uint32_t *gen_table;    // the same with the writer bits the schedule sets
+  const uint32_t *goff;   // [generators + 1]
+  const uint32_t *gmeta;  // [generators] input cells | op code << 16
   template <class F> __device__ __forceinline__ void ins(uint32_t i, F &&f) const {
     const OpRec r = recs[i];
     const uint32_t code = r.y & 0xFF;
     if (code == OP_SEED) return;
-    if (code == OP_EQUALITY) {  // (every cell a generator names has a slot)
-      for (uint32_t k = 0; k < PLAN_GEN_INS; k++) f((size_t)gkeys[PLAN_GEN_CELLS * r.x + k]);
+    if (op_is_listed_generator(code)) {  // (every cell a generator names has a slot)
+      for (uint32_t e = goff[r.x], end = e + (gmeta[r.x] & 0xFFFF); e < end; e++) f((size_t)gkeys[e]);
       return;
     }
     const GateDesc g = x.gates[x.row_gate[r.x]];
@@ -255,8 +259,8 @@ struct OpView {
       if (c.y < x.R) f(x.key(c.x, c.y), (uint32_t *)nullptr);
       return;
     }
-    if (code == OP_EQUALITY) {
-      for (uint32_t k = PLAN_GEN_INS; k < PLAN_GEN_CELLS; k++) f((size_t)gkeys[PLAN_GEN_CELLS * r.x + k], gen_table + PLAN_GEN_CELLS * r.x + k);
+    if (op_is_listed_generator(code)) {
+      for (uint32_t e = goff[r.x] + (gmeta[r.x] & 0xFFFF), end = goff[r.x + 1]; e < end; e++) f((size_t)gkeys[e], gen_table + e);
       return;
     }
     const GateDesc g = x.gates[x.row_gate[r.x]];
@@ -468,7 +472,7 @@ struct PlanCtx {
   p2gpu_circuit *c;
   classes::Scratch &S;
   const std::vector<PlanSeed> &seeds;
-  const std::vector<PlanGenerator> &gens;
+  const PlanGenList &gens;
   hipStream_t st;
   size_t n, tot;
   uint32_t R, d, ngc, NS, NG;
@@ -476,7 +480,7 @@ struct PlanCtx {
   unsigned long long h[C_COUNT];  // the counters as last read back
   unsigned long long *ctr = nullptr;
   uint2 *d_seeds = nullptr;
-  uint32_t *gkeys = nullptr, *gen_table = nullptr;
+  uint32_t *gkeys = nullptr, *gen_table = nullptr, *goff = nullptr, *gmeta = nullptr;
   uint32_t *partner = nullptr, *parent = nullptr, *cell_slot = nullptr;
   unsigned long long *list = nullptr;
   uint32_t slots = 0, NO = 0, n_done = 0;
@@ -487,11 +491,11 @@ struct PlanCtx {
   uint32_t hres[S_COUNT];
   SchedArgs sched;
 
-  PlanCtx(p2gpu_circuit *c_, const std::vector<PlanSeed> &seeds_, const std::vector<PlanGenerator> &gens_, classes::Scratch &S_)
+  PlanCtx(p2gpu_circuit *c_, const std::vector<PlanSeed> &seeds_, const PlanGenList &gens_, classes::Scratch &S_)
       : c(c_), S(S_), seeds(seeds_), gens(gens_), st(c_->stream), n(c_->n), tot((size_t)c_->R * c_->n), R(c_->R), d(c_->d),
         ngc(c_->NC - c_->num_selectors), NS((uint32_t)seeds_.size()), NG((uint32_t)gens_.size()), t0(now_ms()) {}
   Rows rows() const { return Rows{c->d_row_gate.p, c->d_gates.p, c->d_gconsts.p, d, R, ngc}; }
-  OpView view() const { return OpView{rows(), recs, d_seeds, cell_slot, gkeys, gen_table}; }
+  OpView view() const { return OpView{rows(), recs, d_seeds, cell_slot, gkeys, gen_table, goff, gmeta}; }
   void mark(const char *label) const {
     if (!trace_on()) return;
     (void)hipStreamSynchronize(st);
@@ -576,17 +580,22 @@ int PlanCtx::slots_ops() {
   }
   hipLaunchKernelGGL(plan_total_kernel, dim3(1), dim3(1), 0, st, ctr + C_CLASSES, sflag, sflag + NS, (size_t)NS, ctr + C_SEED_SLOTS);
   // the generators' cells: keys from the checked list (every cell inside [n] x [R]), slots behind the seeds'
-  const uint32_t NE = PLAN_GEN_CELLS * NG;
+  const uint32_t NE = gens.n_cells();
   uint32_t *gflag = S.alloc<uint32_t>(2 * (size_t)NE);
   gkeys = S.alloc<uint32_t>(NE);
   gen_table = S.alloc<uint32_t>(NE);
-  if (!gflag || !gkeys || !gen_table) return fail("scratch (generators)", hipErrorOutOfMemory);
+  goff = S.alloc<uint32_t>((size_t)NG + 1);
+  gmeta = S.alloc<uint32_t>(NG);
+  if (!gflag || !gkeys || !gen_table || !goff || !gmeta) return fail("scratch (generators)", hipErrorOutOfMemory);
+  size_t gen_ins = 0;  // the input cells of all generators
   if (NE) {
-    std::vector<uint32_t> hkeys(NE);
-    for (uint32_t e = 0; e < NE; e++)
-      hkeys[e] = (gens[e / PLAN_GEN_CELLS].cells[e % PLAN_GEN_CELLS][1] << d) + gens[e / PLAN_GEN_CELLS].cells[e % PLAN_GEN_CELLS][0];
-    // (pageable memory: the copy has left hkeys when the call returns)
+    std::vector<uint32_t> hkeys(NE), hmeta(NG);
+    for (uint32_t e = 0; e < NE; e++) hkeys[e] = (gens.cells[2 * (size_t)e + 1] << d) + gens.cells[2 * (size_t)e];
+    for (uint32_t g = 0; g < NG; g++) hmeta[g] = gens.ins(g) | gens.code(g) << 16, gen_ins += gens.ins(g);
+    // (pageable memory: the copies have left the vectors when the call returns)
     if (!ok(hipMemcpyAsync(gkeys, hkeys.data(), 4 * (size_t)NE, hipMemcpyHostToDevice, st), "copy the generator cells")) return P2GPU_E_DEVICE;
+    if (!ok(hipMemcpyAsync(goff, gens.off.data(), 4 * ((size_t)NG + 1), hipMemcpyHostToDevice, st), "copy the generator cells")) return P2GPU_E_DEVICE;
+    if (!ok(hipMemcpyAsync(gmeta, hmeta.data(), 4 * (size_t)NG, hipMemcpyHostToDevice, st), "copy the generator cells")) return P2GPU_E_DEVICE;
     if (!ok(hipStreamSynchronize(st), "copy the generator cells")) return P2GPU_E_DEVICE;
     if (!ok(hipMemcpyAsync(gen_table, gkeys, 4 * (size_t)NE, hipMemcpyDeviceToDevice, st), "scratch")) return P2GPU_E_DEVICE;
     const dim3 gg((NE + TPB - 1) / TPB);
@@ -624,14 +633,14 @@ int PlanCtx::slots_ops() {
   uint32_t *use_cnt = S.alloc<uint32_t>((size_t)slots + 1), *use_off = S.alloc<uint32_t>((size_t)slots + 1);
   uint32_t *res = S.alloc<uint32_t>(S_COUNT);
   // the classes are numbered: parent is free.  Every routed cell is an input of one row op at most and of any number of
-  // generators, two inputs each: <= tot + 2 NG entries
-  const size_t users_cap = tot + (size_t)PLAN_GEN_INS * NG;
+  // generators: <= tot + (the generators' input cells) entries
+  const size_t users_cap = tot + gen_ins;
   uint32_t *users = NG ? S.alloc<uint32_t>(users_cap) : parent;
   if (!recs || !ordered || !pending || !queue || !level_off || !level || !slot_level || !twin_min || !slot_min || !keys || !state || !use_cnt ||
       !use_off || !res || !users)
     return fail("scratch (schedule)", hipErrorOutOfMemory);
   if (NS) hipLaunchKernelGGL(plan_seed_ops_kernel, dim3((NS + TPB - 1) / TPB), dim3(TPB), 0, st, NS, recs);
-  if (NG) hipLaunchKernelGGL(plan_gen_ops_kernel, dim3((NG + TPB - 1) / TPB), dim3(TPB), 0, st, NS, NG, recs);
+  if (NG) hipLaunchKernelGGL(plan_gen_ops_kernel, dim3((NG + TPB - 1) / TPB), dim3(TPB), 0, st, NS, NG, gmeta, recs);
   hipLaunchKernelGGL(plan_rows_fill_kernel, dim3(grid_for(n)), dim3(TPB), 0, st, rows(), cell_slot, op_off, new_off, NS + NG, ctr + C_GEN_SLOTS, recs, NO);
   if (!ok(hipMemsetAsync(use_cnt, 0, 4 * ((size_t)slots + 1), st), "scratch")) return P2GPU_E_DEVICE;
   if (!ok(hipMemsetAsync(level, 0xFF, 4 * (size_t)std::max(1u, NO), st), "scratch")) return P2GPU_E_DEVICE;
@@ -695,8 +704,7 @@ int PlanCtx::unreached() {
 
 namespace p2 {
 
-int plan_compile_device(p2gpu_circuit *c, const std::vector<PlanSeed> &seeds, const std::vector<PlanGenerator> &gens, classes::Scratch &S,
-                        PlanArrays &out) {
+int plan_compile_device(p2gpu_circuit *c, const std::vector<PlanSeed> &seeds, const PlanGenList &gens, classes::Scratch &S, PlanArrays &out) {
   PlanCtx x(c, seeds, gens, S);
   if (x.d < 1 || x.tot >= UNSET || (x.NG && x.tot >= WRITER)) return x.refuse(PLAN_TOO_LARGE, 0);  // (a table word: the key below the writer bit)
   x.ctr = S.alloc<unsigned long long>(C_COUNT);
@@ -709,7 +717,7 @@ int plan_compile_device(p2gpu_circuit *c, const std::vector<PlanSeed> &seeds, co
   if (int rc = x.slots_ops()) return rc;
   if (int rc = x.levels()) return rc;
   if (int rc = x.unreached()) return rc;
-  out.cell_slot = x.cell_slot; out.ops = x.ordered; out.level_off = x.level_off; out.gen_table = x.gen_table; out.n_gens = x.NG;
+  out.cell_slot = x.cell_slot; out.ops = x.ordered; out.level_off = x.level_off; out.gen_table = x.gen_table; out.n_gen_cells = gens.n_cells();
   out.levels = x.hres[S_LEVELS]; out.slots = x.slots; out.widest = x.hres[S_WIDEST]; out.n_ops = x.n_done;
   out.kind = hipMemcpyDeviceToDevice;
   return P2GPU_OK;

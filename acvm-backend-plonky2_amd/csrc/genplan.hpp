@@ -12,7 +12,7 @@ namespace classes {
 struct Scratch;  // devclasses.hpp
 }
 
-// x: the row (OP_SEED: the seed's index, OP_EQUALITY: the generator's), y: code | sub << 8 (the slot / copy inside the row): HostPlan's 64-bit word
+// x: the row (OP_SEED: the seed's index, OP_EQUALITY / OP_BIGUINT_DIVREM: the generator's), y: code | sub << 8 (the slot / copy inside the row): HostPlan's 64-bit word
 typedef uint2 OpRec;
 static_assert(sizeof(PlanSeed) == sizeof(uint2), "the kernels read a seed cell as a uint2 (row, col)");
 
@@ -21,8 +21,8 @@ struct PlanArrays {
   const uint32_t *cell_slot = nullptr;  // [R][n]
   const OpRec *ops = nullptr;           // [n_ops], by (level, creation order)
   const uint32_t *level_off = nullptr;  // [levels + 1]
-  const uint32_t *gen_table = nullptr;  // [n_gens][4]
-  size_t n_gens = 0;
+  const uint32_t *gen_table = nullptr;  // [n_gen_cells]: one word per cell a generator names (the offsets are the checked list's)
+  size_t n_gen_cells = 0;
   uint32_t levels = 0, slots = 0, widest = 0;
   size_t n_ops = 0;
   hipMemcpyKind kind = hipMemcpyHostToDevice;
@@ -36,7 +36,6 @@ inline int plan_refuse(const p2gpu_circuit *c, const PlanRefusal &r) {
 
 // The plan of circuit c for `seeds` (already through plan_seeds) and `gens` (already through plan_generators), compiled on c->stream.  The arrays of `out` live in S,
 // which the caller releases once plan_finish has copied them.  Refusals carry p2gpu_witness_plan_create's codes and words.
-int plan_compile_device(p2gpu_circuit *c, const std::vector<PlanSeed> &seeds, const std::vector<PlanGenerator> &gens, classes::Scratch &S,
-                        PlanArrays &out);
+int plan_compile_device(p2gpu_circuit *c, const std::vector<PlanSeed> &seeds, const PlanGenList &gens, classes::Scratch &S, PlanArrays &out);
 
 }  // namespace p2

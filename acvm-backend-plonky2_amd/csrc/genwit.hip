@@ -29,7 +29,9 @@ struct WalkArgs {
   const uint32_t *level_off;  // [levels + 1]
   uint32_t levels;
   const uint32_t *cell_slot;  // [R][n]
-  const uint32_t *gen_table;  // [generators][4]: cell key | WRITER
+  const uint32_t *gen_table;  // one word per cell a generator names: cell key | WRITER; generator g's begin at gen_off[g]
+  const uint32_t *gen_off;    // [generators + 1]
+  const uint32_t *gen_shape;  // [generators] la | lb << 8 | ld << 16 | lr << 24
   gl_t *val;                  // [slots][B]
   const uint2 *seed_cells;    // (row, col)
   const gl_t *seed_vals;      // [seeds][B]
@@ -63,11 +65,12 @@ struct RowSlots {
   __device__ __forceinline__ void reject(uint32_t col) { atomicMin(a.err + b, ((unsigned long long)pos << 8) | col); }
 };
 
-// a generator that is no gate's own as the level walk sees it: witness b's slot values behind its four cells, which the plan's
-// table names (every one has a slot); the writer bits are the table words', not cell_slot's
+// a generator that is no gate's own as the level walk sees it: witness b's slot values behind its cells, numbered 0 .. cells - 1
+// as the plan's table names them from the generator's offset on (every one has a slot); the writer bits are the table words',
+// not cell_slot's
 struct GenSlots {
   const WalkArgs &a;
-  const uint32_t *words;  // the generator's row of the table
+  const uint32_t *words;  // the generator's words of the table
   uint32_t pos;           // of the op in the schedule
   uint32_t b;             // witness of the batch
   __device__ __forceinline__ gl_t &slot(uint32_t s) const { return a.val[(size_t)s * a.B + b]; }
@@ -80,6 +83,19 @@ struct GenSlots {
   __device__ __forceinline__ void reject(uint32_t i) { atomicMin(a.err + b, ((unsigned long long)pos << 8) | i); }
 };
 
+// The div-rem generator, called and not inlined: its word arrays (bigdiv.hpp, 53 words and the loop state) are private memory
+// of THIS frame.  A call in the kernel still costs every other arm (the SHA-256 walk 15.5 -> 23.8 ms: profiles/
+// device_witness.md), so the arm exists only in the walk kernel's DIVREM = true form, which runs the plans that list such a
+// generator; every other plan runs the form without it.  Lanes of one op run it with different trip counts.
+static_assert(BIGDIV_MAX_A == PLAN_DIVREM_MAX_A && BIGDIV_MAX_B == PLAN_DIVREM_MAX_B, "the plan admits the shapes the division's arrays hold");
+__device__ __noinline__ void run_biguint_divrem(const WalkArgs &a, uint32_t g, uint32_t pos, uint32_t b) {
+  const uint32_t sw = a.gen_shape[g];
+  const uint32_t shape[4] = {sw & 0xFF, (sw >> 8) & 0xFF, (sw >> 16) & 0xFF, sw >> 24};
+  GenSlots w{a, a.gen_table + a.gen_off[g], pos, b};
+  gen_biguint_divrem(w, shape);
+}
+
+template <bool DIVREM>
 __device__ __forceinline__ void run_op(const WalkArgs &a, uint32_t pos, uint32_t b) {
   const OpRec op = a.ops[pos];
   const uint32_t code = op.y & 0xFF, sub = op.y >> 8;
@@ -92,8 +108,12 @@ __device__ __forceinline__ void run_op(const WalkArgs &a, uint32_t pos, uint32_t
     return;
   }
   if (code == OP_EQUALITY) {
-    GenSlots w{a, a.gen_table + (size_t)PLAN_GEN_CELLS * op.x, pos, b};
+    GenSlots w{a, a.gen_table + a.gen_off[op.x], pos, b};
     gen_equality(w);
+    return;
+  }
+  if (DIVREM && code == OP_BIGUINT_DIVREM) {  // (a plan with such an op runs the DIVREM form: walk_and_scatter)
+    run_biguint_divrem(a, op.x, pos, b);
     return;
   }
   RowSlots w{a, op.x, pos, b};
@@ -120,6 +140,7 @@ __device__ __forceinline__ void run_op(const WalkArgs &a, uint32_t pos, uint32_t
 // witnesses' words only; the rest of the device stays free for the proofs in flight.  With 1 << sh the group's width rounded
 // up to a power of two, lane t takes witness t & mask of the group and the level's ops t >> sh, + 512 >> sh, ... (the lone
 // call: sh = 0, a lane per op).
+template <bool DIVREM>
 __global__ __launch_bounds__(WALK_TPB) void genwit_walk_kernel(WalkArgs a) {
   const uint32_t b0 = blockIdx.x * WALK_GROUP, gw = min(WALK_GROUP, a.B - b0);
   const uint32_t sh = gw > 1 ? 32 - __clz(gw - 1) : 0, lb = threadIdx.x & ((1u << sh) - 1);
@@ -127,7 +148,7 @@ __global__ __launch_bounds__(WALK_TPB) void genwit_walk_kernel(WalkArgs a) {
   for (uint32_t l = 0; l < a.levels; l++) {
     const uint32_t end = a.level_off[l + 1];
     if (lb < gw)
-      for (uint32_t pos = a.level_off[l] + first; pos < end; pos += step) run_op(a, pos, b0 + lb);
+      for (uint32_t pos = a.level_off[l] + first; pos < end; pos += step) run_op<DIVREM>(a, pos, b0 + lb);
     __syncthreads();
   }
 }
@@ -166,13 +187,15 @@ int walk_and_scatter(p2gpu_witness_plan *p, uint32_t B, gl_t *wires) {
   if (n_vals) HIP_TRY(hipMemcpyAsync(p->seed_vals.p, p->pin, 8 * n_vals, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemsetAsync(p->err.p, 0xFF, 8 * (size_t)B, st));
   WalkArgs a;
-  a.ops = p->ops.p; a.level_off = p->level_off.p; a.levels = p->levels; a.cell_slot = p->cell_slot.p; a.gen_table = p->gen_table.p; a.val = p->val.p;
+  a.ops = p->ops.p; a.level_off = p->level_off.p; a.levels = p->levels; a.cell_slot = p->cell_slot.p; a.gen_table = p->gen_table.p; a.gen_off = p->gen_off.p; a.gen_shape = p->gen_shape.p; a.val = p->val.p;
   a.seed_cells = p->seed_cells.p; a.seed_vals = p->seed_vals.p; a.row_gate = c->d_row_gate.p; a.gates = c->d_gates.p;
   a.gconsts = c->d_gconsts.p; a.prc = c->d_prc.p; a.err = p->err.p; a.d = c->d; a.R = c->R; a.ngc = ngc; a.B = B;
   HIP_TRY(hipEventRecord(p->ev0, st));
   {
     ProfScope ps("genwit_walk_kernel", 16.0 * (double)p->n_ops * B);
-    hipLaunchKernelGGL(genwit_walk_kernel, dim3((B + WALK_GROUP - 1) / WALK_GROUP), dim3(WALK_TPB), 0, st, a);
+    const dim3 grid((B + WALK_GROUP - 1) / WALK_GROUP);
+    if (p->has_divrem) hipLaunchKernelGGL(genwit_walk_kernel<true>, grid, dim3(WALK_TPB), 0, st, a);
+    else hipLaunchKernelGGL(genwit_walk_kernel<false>, grid, dim3(WALK_TPB), 0, st, a);
   }
   HIP_TRY(hipEventRecord(p->ev1, st));
   const size_t cells = (size_t)c->R * c->n, matrix = (size_t)c->W * c->n;
@@ -204,9 +227,10 @@ int name_contradiction(const p2gpu_witness_plan *p, uint64_t e, const uint64_t *
   const uint32_t col = (uint32_t)(e & 0xFF);
   if (pos >= p->h_ops.size()) { set_err("p2gpu_generate_witness: internal error (contradiction word)"); return P2GPU_E_DEVICE; }
   const OpRec op = p->h_ops[pos];
-  if ((op.y & 0xFF) == OP_EQUALITY) {  // (the low byte is the generator's cell position, not a column)
-    const size_t at = (size_t)PLAN_GEN_CELLS * op.x + col;
-    if (col >= PLAN_GEN_CELLS || at >= p->h_gen_table.size()) { set_err("p2gpu_generate_witness: internal error (contradiction word)"); return P2GPU_E_DEVICE; }
+  if (op_is_listed_generator(op.y & 0xFF)) {  // (the low byte is the generator's cell position, not a column)
+    const std::vector<uint32_t> &off = p->h_gens.off;
+    const size_t at = op.x < p->h_gens.size() ? (size_t)off[op.x] + col : SIZE_MAX;
+    if (op.x >= p->h_gens.size() || at >= off[op.x + 1] || at >= p->h_gen_table.size()) { set_err("p2gpu_generate_witness: internal error (contradiction word)"); return P2GPU_E_DEVICE; }
     const uint32_t key = p->h_gen_table[at] & ~WRITER;
     cell[0] = key & (uint32_t)(p->c->n - 1);
     cell[1] = key >> p->c->d;

@@ -89,7 +89,8 @@ const char *gate_validate(uint32_t kind, const uint32_t p[4], uint32_t W, uint32
     w = 38ull * p[0];
     break;
   case G_U32_ADD_MANY:
-    if (!in(p[0], 1, 16)) return "U32AddManyGate: num_addends must be 1..16";
+    // (0: what add_u32s_with_carry places for an empty column of mul_biguint, arithmetic_u32.rs:201-204 -- result = carry in)
+    if (!in(p[0], 0, 16)) return "U32AddManyGate: num_addends must be 0..16";
     if (!in(p[1], 1, 1024)) return "U32AddManyGate: num_ops out of range";
     w = ((uint64_t)p[0] + 3 + 18) * p[1];
     break;

@@ -26,7 +26,17 @@
 //                             -- another generator, a seed, a row op -- compares, one level above at least.
 //             refusals        before anything indexes with the cells: an unknown kind, a cell outside [n] x [R].
 //             sizes           the generators count among the ops; a cell can be an input of a row op and of generators, so
-//                             the `users` lists hold up to R n + 2 generators entries; a table word keeps the key in 31 bits.
+//                             the `users` lists hold up to R n + (the generators' input cells) entries; a table word keeps the
+//                             key in 31 bits.
+//             any number of cells  a generator is a kind and a shape, the cell counts of its four groups (PlanGeneratorV); its
+//                             cells follow each other in one flat list, and so do its table words: gen_off [generators + 1]
+//                             names where a generator's begin.  Equality is the shape {1, 1, 1, 1}; the div-rem generator of
+//                             `div_rem_biguint` has {la, lb, ld, lr}: the limbs of a and b (read), of div and rem (set); its
+//                             op record is list index | OP_BIGUINT_DIVREM << 32.  Every rule above holds per cell position: a
+//                             slot named by several input positions is that many entries of its `users` list and as many
+//                             counts of `pending`, hence one dependency; among the outputs the first position that names a
+//                             slot may take the writer bit, every later position of the same slot compares.  Further
+//                             refusals: a shape that is not the kind's, a cell count that is not the shapes' sum.
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -47,10 +57,31 @@ struct PlanSeed {
 
 // a generator that is no gate's own: p2gpu.h's p2gpu_generator, word for word
 constexpr uint32_t PLAN_GEN_EQUALITY = 0;  // cells: x, y (read), equal, inv (set)
-constexpr uint32_t PLAN_GEN_CELLS = 4, PLAN_GEN_INS = 2;
+constexpr uint32_t PLAN_GEN_CELLS = 4;
 struct PlanGenerator {
   uint32_t kind;
   uint32_t cells[PLAN_GEN_CELLS][2];  // (row, col), routed columns only
+};
+// a generator with any number of cells: p2gpu.h's p2gpu_generator_v, word for word.  shape: the cell counts of its four groups
+constexpr uint32_t PLAN_GEN_BIGUINT_DIVREM = 1;  // cells: a's limbs, b's (read), div's, rem's (set): shape {la, lb, ld, lr}
+constexpr uint32_t PLAN_DIVREM_MAX_A = 32, PLAN_DIVREM_MAX_B = 16;  // bigdiv.hpp's arrays; 32 + 16 + 17 + 16 = 81 cells at most
+struct PlanGeneratorV {
+  uint32_t kind;
+  uint32_t shape[4];
+};
+// the checked list of either ABI: generator g owns the cells [off[g], off[g + 1]) of the flat list
+struct PlanGenList {
+  std::vector<PlanGeneratorV> gens;
+  std::vector<uint32_t> off = {0};  // [gens + 1]
+  std::vector<uint32_t> cells;      // (row, col) per cell
+  size_t size() const { return gens.size(); }
+  bool empty() const { return gens.empty(); }
+  uint32_t n_cells() const { return off.back(); }
+  uint32_t ins(size_t g) const { return gens[g].shape[0] + gens[g].shape[1]; }
+  uint32_t code(size_t g) const { return gens[g].kind == PLAN_GEN_EQUALITY ? OP_EQUALITY : OP_BIGUINT_DIVREM; }
+  // la | lb << 8 | ld << 16 | lr << 24: what the walk reads of a generator beside its table words
+  uint32_t shape_word(size_t g) const { const uint32_t *s = gens[g].shape; return s[0] | s[1] << 8 | s[2] << 16 | s[3] << 24; }
+  bool four_cells_each() const { return (size_t)n_cells() == PLAN_GEN_CELLS * gens.size(); }
 };
 
 // the circuit as both compilers read it
@@ -64,23 +95,25 @@ struct PlanInput {
 };
 
 // cell_slot [R][n]; ops by (level, creation order), one 64-bit word each: row | (code | sub << 8) << 32 (OP_SEED: the seed's
-// index for the row, OP_EQUALITY: the generator's); level_off [levels + 1]; gen_table [generators][4]: cell key (col << d | row)
-// | PLAN_WRITER = this generator writes the cell's slot
+// index for the row, OP_EQUALITY / OP_BIGUINT_DIVREM: the generator's); level_off [levels + 1]; gen_off [generators + 1] and
+// gen_table [gen_off[generators]], one word per cell a generator names: cell key (col << d | row) | PLAN_WRITER = this naming
+// writes the cell's slot (four words per generator when all are equality generators: [generators][4])
 struct HostPlan {
-  std::vector<uint32_t> cell_slot, level_off, gen_table;
+  std::vector<uint32_t> cell_slot, level_off, gen_table, gen_off;
   std::vector<uint64_t> ops;
   uint32_t levels = 0, slots = 0, widest = 0;
 };
 
 enum PlanRefusalKind { PLAN_OK = 0, PLAN_SEED_OUTSIDE, PLAN_SEED_TWICE, PLAN_BAD_SIGMA, PLAN_TOO_LARGE, PLAN_SEED_MISSING, PLAN_CYCLE, PLAN_GEN_KIND, PLAN_GEN_OUTSIDE,
-                       PLAN_GEN_NULL };
+                       PLAN_GEN_NULL, PLAN_GEN_SHAPE, PLAN_GEN_COUNT, PLAN_GEN_FEW, PLAN_GEN_CELLS_NULL };
 
 // why a plan is refused: the cell, and for the seed checks the seeds that name it (the generator checks: seed = the generator's
-// index, seed2 = its kind)
+// index, seed2 = its kind, shape = its shape; the cell count: row = what the shapes name, col = what is given)
 struct PlanRefusal {
   PlanRefusalKind kind = PLAN_OK;
   uint64_t row = 0, col = 0;
   size_t seed = 0, seed2 = 0;
+  uint32_t shape[4] = {0, 0, 0, 0};
   explicit operator bool() const { return kind != PLAN_OK; }
   // a cell by its key, col << d | row
   static PlanRefusal at(PlanRefusalKind kind, uint64_t key, uint32_t d) {
@@ -114,6 +147,15 @@ inline std::string plan_refusal_text(const PlanRefusal &r, uint32_t d, uint32_t 
     snprintf(buf, sizeof buf, "generator %zu names cell (row %llu, column %llu) outside the %zu x %u routed cells", r.seed, row, col, (size_t)1 << d, R);
     break;
   case PLAN_GEN_NULL: snprintf(buf, sizeof buf, "generators are counted but the list is a null pointer"); break;
+  case PLAN_GEN_SHAPE:
+    snprintf(buf, sizeof buf, "generator %zu of kind %zu has the shape {%u, %u, %u, %u}, which is not a shape of its kind", r.seed, r.seed2, r.shape[0],
+             r.shape[1], r.shape[2], r.shape[3]);
+    break;
+  case PLAN_GEN_COUNT: snprintf(buf, sizeof buf, "the generators' shapes name %llu cells, %llu are given", row, col); break;
+  case PLAN_GEN_FEW:
+    snprintf(buf, sizeof buf, "the shapes of the generators up to generator %zu name %llu cells, %llu are given", r.seed, row, col);
+    break;
+  case PLAN_GEN_CELLS_NULL: snprintf(buf, sizeof buf, "generator cells are counted but the list is a null pointer"); break;
   default: buf[0] = 0; break;
   }
   return buf;
@@ -141,30 +183,92 @@ inline PlanRefusal plan_seeds(uint32_t d, uint32_t W, const uint32_t *seed_cells
   return PlanRefusal();
 }
 
-// the generator checks of both compilers: a known kind, every cell a routed one.  Nothing indexes with a cell before this
-inline PlanRefusal plan_generators(uint32_t d, uint32_t R, const PlanGenerator *gens, size_t n_gens, std::vector<PlanGenerator> &out) {
+// whether `shape` is one of kind `kind` (a known one)
+inline bool plan_generator_shape_ok(uint32_t kind, const uint32_t shape[4]) {
+  const uint32_t la = shape[0], lb = shape[1], ld = shape[2], lr = shape[3];
+  if (kind == PLAN_GEN_EQUALITY) return la == 1 && lb == 1 && ld == 1 && lr == 1;
+  // div_rem_biguint (biguint.rs:236-244): rem has b's limbs, div a_len - b_len + 1, or none when b_len > a_len + 1
+  return la >= 1 && la <= PLAN_DIVREM_MAX_A && lb >= 1 && lb <= PLAN_DIVREM_MAX_B && lr == lb && ld == (lb > la + 1 ? 0 : la - lb + 1);
+}
+
+// the generator checks of both compilers, generator by generator: a known kind, a shape of that kind, its cells inside the
+// list and every one a routed cell; then no cell left over.  Nothing indexes with a cell before this.  cells: (row, col) pairs
+inline PlanRefusal plan_generators_v(uint32_t d, uint32_t R, const PlanGeneratorV *gens, size_t n_gens, const uint32_t *cells, size_t n_cells,
+                                     PlanGenList &out) {
   const size_t n = (size_t)1 << d;
   PlanRefusal r;
   if (n_gens && !gens) {
     r.kind = PLAN_GEN_NULL;
     return r;
   }
+  if (n_cells && !cells) {
+    r.kind = PLAN_GEN_CELLS_NULL;
+    return r;
+  }
+  size_t at = 0;
   for (size_t i = 0; i < n_gens; i++) {
     r.seed = i; r.seed2 = gens[i].kind;
-    if (gens[i].kind != PLAN_GEN_EQUALITY) {
+    if (gens[i].kind != PLAN_GEN_EQUALITY && gens[i].kind != PLAN_GEN_BIGUINT_DIVREM) {
       r.kind = PLAN_GEN_KIND;
       return r;
     }
-    for (uint32_t k = 0; k < PLAN_GEN_CELLS; k++) {
-      r.row = gens[i].cells[k][0]; r.col = gens[i].cells[k][1];
+    for (int k = 0; k < 4; k++) r.shape[k] = gens[i].shape[k];
+    if (!plan_generator_shape_ok(gens[i].kind, gens[i].shape)) {
+      r.kind = PLAN_GEN_SHAPE;
+      return r;
+    }
+    const size_t count = (size_t)gens[i].shape[0] + gens[i].shape[1] + gens[i].shape[2] + gens[i].shape[3];
+    if (count > n_cells - at) {  // too few cells: the refusal counts the generators checked so far, this one included
+      r.kind = PLAN_GEN_FEW; r.row = at + count; r.col = n_cells;
+      return r;
+    }
+    for (size_t k = 0; k < count; k++) {
+      r.row = cells[2 * (at + k)]; r.col = cells[2 * (at + k) + 1];
       if (r.row >= n || r.col >= R) {
         r.kind = PLAN_GEN_OUTSIDE;
         return r;
       }
     }
-    out.push_back(gens[i]);
+    at += count;
+    out.gens.push_back(gens[i]);
+    out.off.push_back((uint32_t)at);
   }
+  if (at != n_cells) {
+    r.kind = PLAN_GEN_COUNT; r.row = at; r.col = n_cells;
+    return r;
+  }
+  out.cells.assign(cells, cells + 2 * n_cells);
   return PlanRefusal();
+}
+
+// the list of four-cell records (p2gpu_generator): the case of shapes {1, 1, 1, 1}.  The record form knows the equality
+// generator only, as it always did: any other kind is an unknown one here
+inline PlanRefusal plan_generators(uint32_t d, uint32_t R, const PlanGenerator *gens, size_t n_gens, PlanGenList &out) {
+  if (n_gens && !gens) {
+    PlanRefusal r;
+    r.kind = PLAN_GEN_NULL;
+    return r;
+  }
+  // (in list order, as the checks below: a generator's kind is looked at before the cells of the ones behind it)
+  size_t known = 0;
+  while (known < n_gens && gens[known].kind == PLAN_GEN_EQUALITY) known++;
+  if (known < n_gens) {
+    PlanGenList head;
+    if (PlanRefusal r = plan_generators(d, R, gens, known, head)) return r;
+    PlanRefusal r;
+    r.kind = PLAN_GEN_KIND; r.seed = known; r.seed2 = gens[known].kind;
+    return r;
+  }
+  std::vector<PlanGeneratorV> v(n_gens);
+  std::vector<uint32_t> cells(2 * PLAN_GEN_CELLS * n_gens);
+  for (size_t i = 0; i < n_gens; i++) {
+    v[i] = PlanGeneratorV{gens[i].kind, {1, 1, 1, 1}};
+    for (uint32_t k = 0; k < PLAN_GEN_CELLS; k++) {
+      cells[2 * (PLAN_GEN_CELLS * i + k)] = gens[i].cells[k][0];
+      cells[2 * (PLAN_GEN_CELLS * i + k) + 1] = gens[i].cells[k][1];
+    }
+  }
+  return plan_generators_v(d, R, v.data(), n_gens, cells.data(), PLAN_GEN_CELLS * n_gens, out);
 }
 
 namespace planhost {
@@ -185,7 +289,8 @@ struct Compiler {
   uint32_t R, d, ngc;
   std::vector<uint32_t> cell_slot;  // [R][n]; classes first, then the lone cells
   std::vector<uint32_t> cells;      // input / output cells of the ops, by key: an op's cells need not lie in one row
-  std::vector<uint32_t> gen_table;  // [generators][4]
+  std::vector<uint32_t> gen_table;  // one word per cell a generator names, in list order
+  const uint32_t *gen_off = nullptr;  // the list's offsets into it
   std::vector<HostOp> ops;
   uint32_t slots = 0;
 
@@ -286,7 +391,7 @@ struct Compiler {
   }
   // seeds first, then the generators, then the rows in order; levels; what the schedule did not reach.  order: the ops by
   // (level, creation order)
-  PlanRefusal schedule(const std::vector<PlanSeed> &seeds, const std::vector<PlanGenerator> &gens, std::vector<uint32_t> &order,
+  PlanRefusal schedule(const std::vector<PlanSeed> &seeds, const PlanGenList &gens, std::vector<uint32_t> &order,
                        std::vector<uint32_t> &level_off) {
     const size_t tot = (size_t)R * n;
     if (!gens.empty() && tot >= WRITER) {  // (a table word keeps the key below its writer bit)
@@ -308,17 +413,18 @@ struct Compiler {
       op.out1 = (uint32_t)cells.size();
       ops.push_back(op);
     }
+    gen_off = gens.off.data();
     for (size_t i = 0; i < gens.size(); i++) {
       HostOp op;
-      op.code = OP_EQUALITY; op.row = (uint32_t)i; op.sub = 0;
+      op.code = gens.code(i); op.row = (uint32_t)i; op.sub = 0;
       op.in0 = (uint32_t)cells.size();
-      for (uint32_t k = 0; k < PLAN_GEN_CELLS; k++) {
-        const uint32_t v = (uint32_t)key(gens[i].cells[k][0], gens[i].cells[k][1]);
+      for (uint32_t e = gens.off[i]; e < gens.off[i + 1]; e++) {
+        const uint32_t v = (uint32_t)key(gens.cells[2 * (size_t)e], gens.cells[2 * (size_t)e + 1]);
         if (cell_slot[v] == UNSET) cell_slot[v] = slots++;
         cells.push_back(v);
         gen_table.push_back(v);
       }
-      op.in1 = op.out0 = op.in0 + PLAN_GEN_INS;
+      op.in1 = op.out0 = op.in0 + gens.ins(i);
       op.out1 = (uint32_t)cells.size();
       ops.push_back(op);
     }
@@ -332,7 +438,7 @@ struct Compiler {
     auto slot_of = [&](const HostOp &, uint32_t k) -> uint32_t & { return cell_slot[cells[k]]; };
     // where op o keeps the writer bit of its output cell k: a generator in its table word, every other op in cell_slot
     auto writer_word = [&](const HostOp &o, uint32_t k) -> uint32_t & {
-      return o.code == OP_EQUALITY ? gen_table[(size_t)PLAN_GEN_CELLS * o.row + (k - o.in0)] : cell_slot[cells[k]];
+      return op_is_listed_generator(o.code) ? gen_table[(size_t)gen_off[o.row] + (k - o.in0)] : cell_slot[cells[k]];
     };
     std::vector<uint32_t> use_off(slots + 1, 0);
     for (auto &o : ops) {
@@ -397,8 +503,7 @@ struct Compiler {
 }  // namespace planhost
 
 // the plan of circuit `in` for `seeds` (already through plan_seeds) and `gens` (already through plan_generators)
-inline PlanRefusal plan_compile_host(const PlanInput &in, const std::vector<PlanSeed> &seeds, const std::vector<PlanGenerator> &gens,
-                                     HostPlan &out) {
+inline PlanRefusal plan_compile_host(const PlanInput &in, const std::vector<PlanSeed> &seeds, const PlanGenList &gens, HostPlan &out) {
   planhost::Compiler K(in);
   if (PlanRefusal r = K.classes()) return r;
   std::vector<uint32_t> order;
@@ -408,6 +513,7 @@ inline PlanRefusal plan_compile_host(const PlanInput &in, const std::vector<Plan
   for (uint32_t i : order) out.ops.push_back((uint64_t)K.ops[i].row | ((uint64_t)(K.ops[i].code | (K.ops[i].sub << 8)) << 32));
   out.cell_slot.swap(K.cell_slot);
   out.gen_table.swap(K.gen_table);
+  out.gen_off = gens.off;
   out.levels = (uint32_t)out.level_off.size() - 1;
   out.slots = K.slots;
   out.widest = 0;

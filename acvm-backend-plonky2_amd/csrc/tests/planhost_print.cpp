@@ -9,6 +9,9 @@
 //   refused <p2gpu_last_error's text>\n
 // With a third argument GENERATORS -- the generators that are no gate's own, p2gpu_generator records of nine 32-bit words
 // (kind, then four (row, col) pairs) -- the plan's generator table [generators][4] u32 follows level_off.
+// With four arguments, GENERATORS_V CELLS -- p2gpu_generator_v records of five 32-bit words (kind, shape[4]) and the flat list
+// of their cells, (row, col) pairs of 32-bit words -- the offsets [generators + 1] u32 and then the table, one word per cell,
+// follow level_off.
 #include <cstdio>
 #include <cstring>
 #include "../planhost.hpp"
@@ -35,7 +38,7 @@ template <class T> static std::vector<T> words(const std::vector<uint8_t> &b, si
 }
 
 int main(int argc, char **argv) {
-  if (argc != 3 && argc != 4) { std::fprintf(stderr, "usage: planhost_print BLOB SEEDS [GENERATORS]\n"); return 2; }
+  if (argc < 3 || argc > 5) { std::fprintf(stderr, "usage: planhost_print BLOB SEEDS [GENERATORS | GENERATORS_V CELLS]\n"); return 2; }
   const std::vector<uint8_t> blob = read_file(argv[1]), seed_bytes = read_file(argv[2]);
   const std::vector<uint32_t> h = words<uint32_t>(blob, 0, 64);
   const uint32_t d = h[2], W = h[3], R = h[4], NC = h[5], nsel = h[6], ng = h[23];
@@ -63,7 +66,17 @@ int main(int argc, char **argv) {
   const std::vector<uint32_t> seed_words = words<uint32_t>(seed_bytes, 0, seed_bytes.size() / 4);
   const PlanInput in{d, R, W, NC - nsel, sigma.data(), consts.data() + (size_t)nsel * n, row_gate.data(), gates.data(), k_is.data()};
   static_assert(sizeof(PlanGenerator) == 36, "nine words");
-  std::vector<PlanGenerator> gen_records, gens;
+  static_assert(sizeof(PlanGeneratorV) == 20, "five words");
+  std::vector<PlanGenerator> gen_records;
+  std::vector<PlanGeneratorV> genv_records;
+  std::vector<uint32_t> genv_cells;
+  PlanGenList gens;
+  if (argc == 5) {
+    const std::vector<uint8_t> gen_bytes = read_file(argv[3]), cell_bytes = read_file(argv[4]);
+    if (gen_bytes.size() % sizeof(PlanGeneratorV) || cell_bytes.size() % 8) { std::fprintf(stderr, "unsupported generator file\n"); return 2; }
+    genv_records = words<PlanGeneratorV>(gen_bytes, 0, gen_bytes.size() / sizeof(PlanGeneratorV));
+    genv_cells = words<uint32_t>(cell_bytes, 0, cell_bytes.size() / 4);
+  }
   if (argc == 4) {
     const std::vector<uint8_t> gen_bytes = read_file(argv[3]);
     if (gen_bytes.size() % sizeof(PlanGenerator)) { std::fprintf(stderr, "unsupported generator file\n"); return 2; }
@@ -72,7 +85,9 @@ int main(int argc, char **argv) {
   std::vector<PlanSeed> seeds;
   HostPlan plan;
   PlanRefusal r = plan_seeds(d, W, seed_words.data(), seed_words.size() / 2, seeds);
-  if (!r) r = plan_generators(d, R, gen_records.data(), gen_records.size(), gens);
+  if (!r)
+    r = argc == 5 ? plan_generators_v(d, R, genv_records.data(), genv_records.size(), genv_cells.data(), genv_cells.size() / 2, gens)
+                  : plan_generators(d, R, gen_records.data(), gen_records.size(), gens);
   if (!r) r = plan_compile_host(in, seeds, gens, plan);
   if (r) {
     std::printf("refused %s\n", plan_refusal_text(r, d, W, R).c_str());
@@ -82,6 +97,7 @@ int main(int argc, char **argv) {
   std::fwrite(plan.cell_slot.data(), 4, plan.cell_slot.size(), stdout);
   std::fwrite(plan.ops.data(), 8, plan.ops.size(), stdout);
   std::fwrite(plan.level_off.data(), 4, plan.level_off.size(), stdout);
+  if (argc == 5) std::fwrite(plan.gen_off.data(), 4, plan.gen_off.size(), stdout);
   if (!plan.gen_table.empty()) std::fwrite(plan.gen_table.data(), 4, plan.gen_table.size(), stdout);
   return std::fflush(stdout) == 0 ? 0 : 2;
 }

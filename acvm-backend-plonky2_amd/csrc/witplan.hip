@@ -3,10 +3,12 @@
 //   p2gpu_witness_plan_create   the host compiler (planhost.hpp) over the circuit's tables as the device holds them -- a handle
 //                               from a blob and one from p2gpu_circuit_build hold the same sigma, hence give the same plan;
 //   p2gpu_witness_plan_build    the same plan compiled on the device (genplan.hip); the host one is its differential oracle.
-//   ..._create_gen / _build_gen the same two routines with a list of generators that are no gate's own (planhost.hpp states the
-//                               rules); the entry points above are their case of an empty list.
+//   ..._create_genv / _build_genv the same two routines with a list of generators that are no gate's own, each a kind, a shape
+//                               and its cells in one flat list (planhost.hpp states the rules);
+//   ..._create_gen / _build_gen their case of four-cell records, and the entry points above the case of an empty list.
 // genwit.hip runs a plan.
 #include <chrono>
+#include <functional>
 #include "devclasses.hpp"
 #include "witplan.hpp"
 
@@ -26,9 +28,19 @@ int plan_finish(p2gpu_witness_plan *p, const PlanArrays &a) {
   HIP_TRY(p->level_off.alloc((size_t)a.levels + 1));
   HIP_TRY(p->cell_slot.alloc(tot));
   HIP_TRY(p->seed_cells.alloc(std::max<size_t>(1, n_seeds)));
-  HIP_TRY(p->gen_table.alloc(std::max<size_t>(1, PLAN_GEN_CELLS * a.n_gens)));
-  p->h_gen_table.resize(PLAN_GEN_CELLS * a.n_gens);
-  if (a.n_gens) {
+  const size_t n_gens = p->h_gens.size();
+  HIP_TRY(p->gen_table.alloc(std::max<size_t>(1, a.n_gen_cells)));
+  HIP_TRY(p->gen_off.alloc(n_gens + 1));
+  HIP_TRY(p->gen_shape.alloc(std::max<size_t>(1, n_gens)));
+  p->h_gen_table.resize(a.n_gen_cells);
+  std::vector<uint32_t> shapes(n_gens);
+  for (size_t g = 0; g < n_gens; g++) {
+    shapes[g] = p->h_gens.shape_word(g);
+    p->has_divrem |= p->h_gens.gens[g].kind == PLAN_GEN_BIGUINT_DIVREM;
+  }
+  HIP_TRY(hipMemcpyAsync(p->gen_off.p, p->h_gens.off.data(), 4 * (n_gens + 1), hipMemcpyHostToDevice, c->stream));
+  if (n_gens) HIP_TRY(hipMemcpyAsync(p->gen_shape.p, shapes.data(), 4 * n_gens, hipMemcpyHostToDevice, c->stream));
+  if (a.n_gen_cells) {
     HIP_TRY(hipMemcpyAsync(p->gen_table.p, a.gen_table, 4 * p->h_gen_table.size(), a.kind, c->stream));
     if (a.kind == hipMemcpyHostToDevice) memcpy(p->h_gen_table.data(), a.gen_table, 4 * p->h_gen_table.size());
     else HIP_TRY(hipMemcpyAsync(p->h_gen_table.data(), a.gen_table, 4 * p->h_gen_table.size(), hipMemcpyDeviceToHost, c->stream));
@@ -67,7 +79,7 @@ int plan_compile(p2gpu_witness_plan *p) {
   PlanArrays a;
   a.cell_slot = plan.cell_slot.data(); a.ops = reinterpret_cast<const OpRec *>(plan.ops.data()); a.level_off = plan.level_off.data();
   a.levels = plan.levels; a.slots = plan.slots; a.widest = plan.widest; a.n_ops = plan.ops.size();
-  a.gen_table = plan.gen_table.data(); a.n_gens = p->h_gens.size();
+  a.gen_table = plan.gen_table.data(); a.n_gen_cells = plan.gen_table.size();
   return plan_finish(p, a);
 }
 
@@ -80,11 +92,14 @@ int plan_build(p2gpu_witness_plan *p) {
 }
 
 // the front checks, the seed and generator checks and the ownership of a half-made plan, for either compiler
-int plan_new(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, const p2gpu_generator *generators, size_t n_generators,
+// check_generators(d, R, list): the caller's generator list of either record form through planhost.hpp's checks
+using GeneratorCheck = std::function<PlanRefusal(uint32_t, uint32_t, PlanGenList &)>;
+int plan_new(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, size_t n_generators, size_t n_generator_cells, const GeneratorCheck &check_generators,
              p2gpu_witness_plan **out, int (*compile)(p2gpu_witness_plan *)) {
   static_assert(sizeof(p2gpu_generator) == sizeof(PlanGenerator) && P2GPU_GEN_EQUALITY == PLAN_GEN_EQUALITY, "planhost.hpp restates the record");
+  static_assert(sizeof(p2gpu_generator_v) == sizeof(PlanGeneratorV) && P2GPU_GEN_BIGUINT_DIVREM == PLAN_GEN_BIGUINT_DIVREM, "planhost.hpp restates the record");
   if (out) *out = nullptr;
-  if (!c || !out || (n_seeds && !seed_cells) || n_generators >= ((size_t)1 << 32)) return P2GPU_E_ARG;
+  if (!c || !out || (n_seeds && !seed_cells) || n_generators >= ((size_t)1 << 32) || n_generator_cells >= ((size_t)1 << 32)) return P2GPU_E_ARG;
   if (int rc = prover_handle(c)) return rc;
   if (!c->group.empty()) {
     set_err("p2gpu_witness_plan_create: a device group takes a wire matrix (every rank of a sharded proof reads all of it)");
@@ -99,7 +114,7 @@ int plan_new(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, const
   int rc;
   try {
     PlanRefusal r = plan_seeds(c->d, c->W, seed_cells, n_seeds, p->h_seed_cells);
-    if (!r) r = plan_generators(c->d, c->R, reinterpret_cast<const PlanGenerator *>(generators), n_generators, p->h_gens);
+    if (!r) r = check_generators(c->d, c->R, p->h_gens);
     rc = r ? plan_refuse(c, r) : compile(p);
   } catch (...) {
     p->release();
@@ -114,6 +129,20 @@ int plan_new(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, const
   p->compile_ms = wall_ms() - t0;
   *out = p;
   return P2GPU_OK;
+}
+
+// the two record forms of the generator list in front of plan_new
+int plan_new_gen(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, const p2gpu_generator *generators, size_t n_generators,
+                 p2gpu_witness_plan **out, int (*compile)(p2gpu_witness_plan *)) {
+  const PlanGenerator *recs = reinterpret_cast<const PlanGenerator *>(generators);
+  return plan_new(c, seed_cells, n_seeds, n_generators, 0,
+                  [=](uint32_t d, uint32_t R, PlanGenList &list) { return plan_generators(d, R, recs, n_generators, list); }, out, compile);
+}
+int plan_new_genv(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, const p2gpu_generator_v *generators, size_t n_generators,
+                  const uint32_t *cells, size_t n_cells, p2gpu_witness_plan **out, int (*compile)(p2gpu_witness_plan *)) {
+  const PlanGeneratorV *recs = reinterpret_cast<const PlanGeneratorV *>(generators);
+  return plan_new(c, seed_cells, n_seeds, n_generators, n_cells,
+                  [=](uint32_t d, uint32_t R, PlanGenList &list) { return plan_generators_v(d, R, recs, n_generators, cells, n_cells, list); }, out, compile);
 }
 
 }  // namespace
@@ -137,26 +166,54 @@ int plan_reserve(p2gpu_witness_plan *p, size_t batch) {
 extern "C" {
 
 int p2gpu_witness_plan_create(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, p2gpu_witness_plan **out) try {
-  return plan_new(c, seed_cells, n_seeds, nullptr, 0, out, plan_compile);
+  return plan_new_gen(c, seed_cells, n_seeds, nullptr, 0, out, plan_compile);
 } P2GPU_CATCH
 
 int p2gpu_witness_plan_build(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, p2gpu_witness_plan **out) try {
-  return plan_new(c, seed_cells, n_seeds, nullptr, 0, out, plan_build);
+  return plan_new_gen(c, seed_cells, n_seeds, nullptr, 0, out, plan_build);
 } P2GPU_CATCH
 
 int p2gpu_witness_plan_create_gen(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, const p2gpu_generator *generators,
                                   size_t n_generators, p2gpu_witness_plan **out) try {
-  return plan_new(c, seed_cells, n_seeds, generators, n_generators, out, plan_compile);
+  return plan_new_gen(c, seed_cells, n_seeds, generators, n_generators, out, plan_compile);
 } P2GPU_CATCH
 
 int p2gpu_witness_plan_build_gen(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, const p2gpu_generator *generators,
                                  size_t n_generators, p2gpu_witness_plan **out) try {
-  return plan_new(c, seed_cells, n_seeds, generators, n_generators, out, plan_build);
+  return plan_new_gen(c, seed_cells, n_seeds, generators, n_generators, out, plan_build);
+} P2GPU_CATCH
+
+int p2gpu_witness_plan_create_genv(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, const p2gpu_generator_v *generators,
+                                   size_t n_generators, const uint32_t *cells, size_t n_cells, p2gpu_witness_plan **out) try {
+  return plan_new_genv(c, seed_cells, n_seeds, generators, n_generators, cells, n_cells, out, plan_compile);
+} P2GPU_CATCH
+
+int p2gpu_witness_plan_build_genv(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, const p2gpu_generator_v *generators,
+                                  size_t n_generators, const uint32_t *cells, size_t n_cells, p2gpu_witness_plan **out) try {
+  return plan_new_genv(c, seed_cells, n_seeds, generators, n_generators, cells, n_cells, out, plan_build);
+} P2GPU_CATCH
+
+int p2gpu_witness_plan_export_generators_v(const p2gpu_witness_plan *p, uint32_t *off, uint32_t *table, size_t sizes[2]) try {
+  if (!p || !sizes) return P2GPU_E_ARG;
+  const size_t n_gens = p->h_gens.size(), n_words = p->h_gens.n_cells();
+  sizes[0] = n_gens; sizes[1] = n_words;
+  if (!off && !table) return P2GPU_OK;
+  if (!off || !table) return P2GPU_E_ARG;
+  const p2gpu_circuit *c = p->c;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(off, p->gen_off.p, 4 * (n_gens + 1), hipMemcpyDeviceToHost, c->stream));
+  if (n_words) HIP_TRY(hipMemcpyAsync(table, p->gen_table.p, 4 * n_words, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return P2GPU_OK;
 } P2GPU_CATCH
 
 int p2gpu_witness_plan_export_generators(const p2gpu_witness_plan *p, uint32_t *table, size_t *n_generators) try {
   if (!p || !n_generators) return P2GPU_E_ARG;
   *n_generators = p->h_gens.size();
+  if (!p->h_gens.four_cells_each()) {
+    set_err("p2gpu_witness_plan_export_generators: a generator of this plan has more than four cells (p2gpu_witness_plan_export_generators_v reads it)");
+    return P2GPU_E_ARG;
+  }
   if (!table || p->h_gens.empty()) return P2GPU_OK;
   const p2gpu_circuit *c = p->c;
   HIP_TRY(hipSetDevice(c->device));

@@ -12,11 +12,13 @@ struct p2gpu_witness_plan {
   p2::DBuf<uint32_t> level_off, cell_slot;
   p2::DBuf<uint2> seed_cells;
   std::vector<p2::PlanSeed> h_seed_cells;
-  // the generators that are no gate's own: the checked list, and the plan's table [n_gens][4] (cell key | PLAN_WRITER) on the
-  // device for the walk and on the host to name the cell of a contradiction
-  std::vector<p2::PlanGenerator> h_gens;
+  // the generators that are no gate's own: the checked list, and the plan's table (one word per cell a generator names: cell
+  // key | PLAN_WRITER; generator g's words begin at h_gens.off[g]) on the device for the walk and on the host to name the cell
+  // of a contradiction; gen_off [generators + 1] and gen_shape [generators] (PlanGenList::shape_word) are the list's, for the walk
+  p2::PlanGenList h_gens;
   std::vector<uint32_t> h_gen_table;
-  p2::DBuf<uint32_t> gen_table;
+  p2::DBuf<uint32_t> gen_table, gen_off, gen_shape;
+  bool has_divrem = false;  // a div-rem generator is listed: the walk kernel's form with that arm runs this plan
   // The values of `cap` witnesses (plan_finish: 1; a batch grows them).  A call of B <= cap witnesses lays its values out
   // with its own B as the stride, in the front of the buffers: val [slots][B], seed_vals [n_seeds][B], err [B].
   size_t cap = 0;
@@ -31,7 +33,7 @@ struct p2gpu_witness_plan {
     cap = 0;
   }
   void release() {
-    ops.release(); level_off.release(); cell_slot.release(); seed_cells.release(); gen_table.release();
+    ops.release(); level_off.release(); cell_slot.release(); seed_cells.release(); gen_table.release(); gen_off.release(); gen_shape.release();
     release_values();
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);

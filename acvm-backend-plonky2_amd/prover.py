@@ -98,6 +98,9 @@ def load_library():
     lib.p2gpu_witness_plan_create_gen.argtypes = [vp, vp, sz, vp, sz, ctypes.POINTER(vp)]
     lib.p2gpu_witness_plan_build_gen.argtypes = [vp, vp, sz, vp, sz, ctypes.POINTER(vp)]
     lib.p2gpu_witness_plan_export_generators.argtypes = [vp, vp, ctypes.POINTER(sz)]
+    lib.p2gpu_witness_plan_create_genv.argtypes = [vp, vp, sz, vp, sz, vp, sz, ctypes.POINTER(vp)]
+    lib.p2gpu_witness_plan_build_genv.argtypes = [vp, vp, sz, vp, sz, vp, sz, ctypes.POINTER(vp)]
+    lib.p2gpu_witness_plan_export_generators_v.argtypes = [vp, vp, vp, vp]
     lib.p2gpu_witness_plan_destroy.argtypes = [vp]
     lib.p2gpu_witness_plan_destroy.restype = None
     lib.p2gpu_witness_plan_info.argtypes = [vp, vp, vp]
@@ -438,8 +441,10 @@ class CircuitData:
         caller assigns per proof, ``pw.set_target`` on the Rust side) into the whole witness on the GPU.
         ``compile="device"``: the same plan through ``p2gpu_witness_plan_build``, compiled on the GPU.
         ``generators``: the generators that are no gate's own, [("equality", (cell_x, cell_y, cell_equal, cell_inv))] with
-        (row, col) cells (``translate.CircuitBuilder.generators()``); the plan then comes from
-        ``p2gpu_witness_plan_create_gen`` / ``_build_gen``."""
+        (row, col) cells, and ("biguint_divrem", (a_cells, b_cells, div_cells, rem_cells)) with the limbs' cells, least
+        significant first (``translate.CircuitBuilder.generators()``); the plan then comes from
+        ``p2gpu_witness_plan_create_gen`` / ``_build_gen``, or from ``_create_genv`` / ``_build_genv`` when a generator has
+        another number of cells than four."""
         return WitnessPlan(self, seed_cells, compile=compile, generators=generators)
 
     def prove_routed(self, routed, public_inputs=()):
@@ -518,7 +523,7 @@ class WitnessPlan:
     """Witness generation on the GPU for one circuit and one set of seed cells (``p2gpu_witness_plan``).  Close it before
     the circuit."""
 
-    GENERATOR_KINDS = {"equality": 0}   # p2gpu.h P2GPU_GEN_EQUALITY
+    GENERATOR_KINDS = {"equality": 0, "biguint_divrem": 1}   # p2gpu.h P2GPU_GEN_EQUALITY, P2GPU_GEN_BIGUINT_DIVREM
 
     def __init__(self, circuit, seed_cells, compile="host", generators=None):
         if compile not in ("host", "device"):
@@ -534,6 +539,10 @@ class WitnessPlan:
             make = self._lib.p2gpu_witness_plan_build if compile == "device" else self._lib.p2gpu_witness_plan_create
             _check(make(circuit._h, cells.ctypes.data if cells.size else None, len(cells), ctypes.byref(self._h)))
             return
+        generators = list(generators)
+        if any(self._groups(gcells) is not None for _, gcells in generators):
+            self._init_genv(circuit, cells, compile, generators)
+            return
         # p2gpu_generator records: kind, then four (row, col) pairs; a kind may be given by its number
         recs = np.zeros((len(generators), 9), dtype=np.int64)
         for i, (kind, gcells) in enumerate(generators):
@@ -545,6 +554,33 @@ class WitnessPlan:
         make = self._lib.p2gpu_witness_plan_build_gen if compile == "device" else self._lib.p2gpu_witness_plan_create_gen
         _check(make(circuit._h, cells.ctypes.data if cells.size else None, len(cells), recs.ctypes.data if recs.size else None, len(recs),
                     ctypes.byref(self._h)))
+
+    @staticmethod
+    def _groups(gcells):
+        """The four cell groups of a generator given as (a_cells, b_cells, div_cells, rem_cells), None for four plain cells."""
+        gcells = list(gcells)
+        if len(gcells) == 4 and all(len(g) == 2 and all(isinstance(v, (int, np.integer)) for v in g) for g in gcells):
+            return None
+        return [[tuple(cell) for cell in grp] for grp in gcells]
+
+    def _init_genv(self, circuit, cells, compile, generators):
+        """p2gpu_generator_v records (kind, shape[4]) and the flat (row, col) list of their cells: the entry points for
+        generators with any number of cells."""
+        recs, flat = np.zeros((len(generators), 5), dtype=np.int64), []
+        for i, (kind, gcells) in enumerate(generators):
+            groups = self._groups(gcells) or [[tuple(cell)] for cell in gcells]
+            if len(groups) != 4:
+                raise P2GpuError(-7, "a generator is a kind and four groups of (row, col) cells")
+            recs[i, 0] = self.GENERATOR_KINDS.get(kind, kind) if isinstance(kind, str) else kind
+            recs[i, 1:] = [len(g) for g in groups]
+            flat += [cell for g in groups for cell in g]
+        flat = np.array(flat, dtype=np.int64).reshape(-1, 2)
+        if (recs.size and (recs.min() < 0 or recs.max() >= 1 << 32)) or (flat.size and (flat.min() < 0 or flat.max() >= 1 << 32)):
+            raise P2GpuError(-7, "a generator is a kind, a shape and (row, col) cells of unsigned 32-bit numbers")
+        recs, flat = np.ascontiguousarray(recs.astype(np.uint32)), np.ascontiguousarray(flat.astype(np.uint32))
+        make = self._lib.p2gpu_witness_plan_build_genv if compile == "device" else self._lib.p2gpu_witness_plan_create_genv
+        _check(make(circuit._h, cells.ctypes.data if cells.size else None, len(cells), recs.ctypes.data if recs.size else None, len(recs),
+                    flat.ctypes.data if flat.size else None, len(flat), ctypes.byref(self._h)))
 
     def _values(self, values):
         v = _u64(np.array([int(x) for x in values], dtype=np.uint64))
@@ -580,6 +616,16 @@ class WitnessPlan:
         if count.value:
             _check(self._lib.p2gpu_witness_plan_export_generators(self._h, table.ctypes.data, ctypes.byref(count)))
         return table
+
+    def export_generators_v(self):
+        """``p2gpu_witness_plan_export_generators_v``: (off [generators + 1] uint32, table [off[-1]] uint32) of any plan:
+        generator g's table words are table[off[g]:off[g + 1]], one per cell in list order, cell key | bit 31 = this naming
+        writes the cell's slot."""
+        sizes = (ctypes.c_size_t * 2)()
+        _check(self._lib.p2gpu_witness_plan_export_generators_v(self._h, None, None, sizes))
+        off, table = np.zeros(sizes[0] + 1, dtype=np.uint32), np.zeros(max(1, sizes[1]), dtype=np.uint32)
+        _check(self._lib.p2gpu_witness_plan_export_generators_v(self._h, off.ctypes.data, table.ctypes.data, sizes))
+        return off, table[:sizes[1]]
 
     def generate(self, values):
         """``p2gpu_generate_witness``: the wire matrix [num_wires][degree] as an int64 tensor on the circuit's GPU."""

@@ -20,6 +20,11 @@ Mirrors, with the reference's names:
     SHA-256 compression vector, tests/test_sha256_internal.rs:481-549, comes out of it), and the oracle and the
     GPU prove it to identical bytes.
 
+  * the u32 and biguint gadgets of the reference's own tree (plonky2_ecdsa/biguint/gadgets/arithmetic_u32.rs,
+    multiple_comparison.rs, range_check_u32.rs, biguint/biguint.rs) over its five gates (biguint/gates/*.rs: shapes, wire
+    positions, degrees and ids are read off that source, so they are pinned), with the BigUintDivRemGenerator of
+    `div_rem_biguint` as the event "divrem".  Only `find_slot`, plonky2's row sharing, is UNPINNED (see `_u32_slot`).
+
 What it is NOT: an ACIR *reader*.  The reference deserialises gzip + bincode `Program` bytes through the acvm
 crate (noir_and_plonky2_serialization.rs:42-64); no compiled program exists in the tree to test a reader on, so
 programs are given as Python data: [("assert_zero", mul_terms, linear, q_c), ("sha256_compression", inputs16,
@@ -39,6 +44,11 @@ NUM_WIRES, NUM_ROUTED, NUM_OPS, BASE_SUM_LIMBS = 234, 80, 20, 63
 G_NOOP, G_CONSTANT, G_PUBLIC_INPUT, G_ARITHMETIC, G_BASE_SUM, G_RANDOM_ACCESS, G_POSEIDON = 0, 1, 2, 3, 4, 5, 6
 NUM_CONSTANTS = 2            # CircuitConfig::num_constants of both configurations
 GEN_EQUALITY = 0             # p2gpu.h P2GPU_GEN_EQUALITY
+GEN_BIGUINT_DIVREM = 1       # p2gpu.h P2GPU_GEN_BIGUINT_DIVREM
+G_U32_ARITHMETIC, G_U32_ADD_MANY, G_U32_SUBTRACTION, G_U32_RANGE_CHECK, G_COMPARISON = 7, 8, 9, 10, 11   # p2gpu.h gate kinds
+MAX_NUM_ADDENDS = 16         # gates/add_many_u32.rs:24
+U32_MAX = 0xFFFFFFFF
+_PHANTOM = "_phantom: PhantomData<plonky2_field::goldilocks_field::GoldilocksField>"
 
 
 class CircuitBuilder:
@@ -57,6 +67,7 @@ class CircuitBuilder:
         self.arith_results = {}   # (c0, c1, m0, m1, addend) -> output target of the identical earlier operation
         self.events = []          # witness generators in creation order
         self.free_ra = {}         # bits -> RandomAccess row with a free copy
+        self.free_u32 = {}        # (gate, params) -> U32 row with a free operation
         self.rng = np.random.default_rng(seed)
         self._lay = None          # what _layout() made
 
@@ -274,6 +285,273 @@ class CircuitBuilder:
         self.events.append(("lesum", row))
         return row["sum"]
 
+    # -- plonky2_ecdsa/biguint/gadgets/arithmetic_u32.rs: a U32Target is a target that is assumed to hold 32 bits ------------
+    def u32_gate_ops(self, kind, num_addends=0):
+        """Operations per row: U32ArithmeticGate::num_ops (gates/arithmetic_u32.rs:39-42: 6 routed wires and 32 two-bit limbs
+        per op), U32AddManyGate::num_ops (add_many_u32.rs:43-48: num_addends + 3 routed, 18 limbs), U32SubtractionGate::num_ops
+        (subtraction_u32.rs:39-43: 5 routed, 16 limbs).  135 wires: 3 / 135 // (a + 21) / 6; 234 wires: 6 / min(234 // (a + 21),
+        80 // (a + 3)) / 11."""
+        routed, limbs = {"u32arith": (6, 32), "u32addmany": (num_addends + 3, 18), "u32sub": (5, 16)}[kind]
+        return min(self.num_wires // (routed + limbs), NUM_ROUTED // routed)
+
+    def _u32_slot(self, kind, num_addends=0):
+        """circuit_builder.rs `find_slot(gate, params, constants)` -- UNPINNED (recollection of plonky2 0.2.2, restated as
+        `random_access` restates it): one open row per (gate, params) until it is full.  The operations of a shared row that
+        nobody takes stay unconnected: their wires are what the gate's generator derives from zeros (build() fills them so, and
+        so does the device: an op without a slot is left to fill_witness)."""
+        key = (kind, num_addends)
+        r = self.free_u32.get(key)
+        if r is None or len(self.rows[r]["ops"]) == self.rows[r]["num_ops"]:
+            r = len(self.rows)
+            self.rows.append({"kind": kind, "na": num_addends, "num_ops": self.u32_gate_ops(kind, num_addends), "ops": []})
+            self.free_u32[key] = r
+        return self.rows[r]
+
+    def add_virtual_u32_target(self):
+        """arithmetic_u32.rs:79-81"""
+        return self.add_virtual_target()
+
+    def add_virtual_u32_targets(self, n):
+        """arithmetic_u32.rs:83-88"""
+        return [self.add_virtual_target() for _ in range(n)]
+
+    def constant_u32(self, c):
+        """arithmetic_u32.rs:91-93"""
+        assert 0 <= c <= U32_MAX
+        return self.constant(c)
+
+    def zero_u32(self):
+        """arithmetic_u32.rs:95-97"""
+        return self.zero()
+
+    def one_u32(self):
+        """arithmetic_u32.rs:99-101"""
+        return self.one()
+
+    def connect_u32(self, x, y):
+        """arithmetic_u32.rs:103-105"""
+        self.connect(x, y)
+
+    def assert_zero_u32(self, x):
+        """arithmetic_u32.rs:107-109"""
+        self.assert_zero(x)
+
+    def assert_one(self, x):
+        """circuit_builder.rs assert_one (biguint.rs:259 calls it)"""
+        self.connect(x, self.one())
+
+    def target_as_constant(self, t):
+        """circuit_builder.rs target_as_constant: the constant of a target `constant()` returned, else None."""
+        return self.const_of.get(t)
+
+    def arithmetic_u32_special_cases(self, x, y, z):
+        """arithmetic_u32.rs:114-138: all three constant -> the two halves of x * y + z as constants, no gate."""
+        kx, ky, kz = self.target_as_constant(x), self.target_as_constant(y), self.target_as_constant(z)
+        if kx is None or ky is None or kz is None:
+            return None
+        total = (kx * ky + kz) % P
+        return self.constant_u32(total & U32_MAX), self.constant_u32(total >> 32)
+
+    def mul_add_u32(self, x, y, z):
+        """arithmetic_u32.rs:141-157: (low, high) of x * y + z in a U32ArithmeticGate operation."""
+        special = self.arithmetic_u32_special_cases(x, y, z)
+        if special is not None:
+            return special
+        row = self._u32_slot("u32arith")
+        low, high = self.add_virtual_target(), self.add_virtual_target()
+        row["ops"].append((x, y, z, low, high))
+        self.events.append(("u32arith", x, y, z, low, high))
+        return low, high
+
+    def add_u32(self, a, b):
+        """arithmetic_u32.rs:159-162"""
+        return self.mul_add_u32(a, self.one_u32(), b)
+
+    def _add_many_gate(self, to_add, carry):
+        if len(to_add) > MAX_NUM_ADDENDS:
+            raise ValueError("U32AddManyGate: %d addends, MAX_NUM_ADDENDS is %d" % (len(to_add), MAX_NUM_ADDENDS))
+        row = self._u32_slot("u32addmany", len(to_add))
+        result, out_carry = self.add_virtual_target(), self.add_virtual_target()
+        row["ops"].append(tuple(to_add) + (carry, result, out_carry))
+        self.events.append(("u32addmany", tuple(to_add), carry, result, out_carry))
+        return result, out_carry
+
+    def add_many_u32(self, to_add):
+        """arithmetic_u32.rs:164-190: no gate for 0 or 1 addends, add_u32 for 2, else a U32AddManyGate operation per distinct
+        number of addends (find_slot's params), its carry wire tied to zero."""
+        to_add = list(to_add)
+        if len(to_add) == 0:
+            return self.zero_u32(), self.zero_u32()
+        if len(to_add) == 1:
+            return to_add[0], self.zero_u32()
+        if len(to_add) == 2:
+            return self.add_u32(to_add[0], to_add[1])
+        return self._add_many_gate(to_add, self.zero())
+
+    def add_u32s_with_carry(self, to_add, carry):
+        """arithmetic_u32.rs:192-218.  An empty `to_add` is a U32AddManyGate { num_addends: 0 } operation, result = carry, as
+        upstream places it (mul_biguint by a target without limbs: div_rem_biguint with b_len > a_len + 1)."""
+        to_add = list(to_add)
+        if len(to_add) == 1:
+            return self.add_u32(to_add[0], carry)
+        return self._add_many_gate(to_add, carry)
+
+    def mul_u32(self, a, b):
+        """arithmetic_u32.rs:220-223"""
+        return self.mul_add_u32(a, b, self.zero_u32())
+
+    def sub_u32(self, x, y, borrow):
+        """arithmetic_u32.rs:226-241: (x - y - borrow mod 2^32, the borrow out) in a U32SubtractionGate operation."""
+        row = self._u32_slot("u32sub")
+        result, out_borrow = self.add_virtual_target(), self.add_virtual_target()
+        row["ops"].append((x, y, borrow, result, out_borrow))
+        self.events.append(("u32sub", x, y, borrow, result, out_borrow))
+        return result, out_borrow
+
+    def range_check_u32(self, vals):
+        """gadgets/range_check_u32.rs:9-20: one U32RangeCheckGate row (add_gate: never shared) over all of `vals`."""
+        vals = list(vals)
+        if 17 * len(vals) > self.num_wires:
+            raise ValueError("U32RangeCheckGate: %d limbs need %d wires" % (len(vals), 17 * len(vals)))
+        self.rows.append({"kind": "u32range", "limbs": vals})
+        self.events.append(("u32range", tuple(vals)))
+
+    # -- gadgets/multiple_comparison.rs ------------------------------------------------------------------------------------
+    def list_le(self, a, b, num_bits):
+        """multiple_comparison.rs:15-66: a <= b as little-endian lists of `num_bits`-bit limbs: per limb two ComparisonGate rows
+        (add_gate: never shared) with chunk_bits = 2, then mul, sub, mul_add.  The result is boolean by construction."""
+        a, b = list(a), list(b)
+        assert len(a) == len(b), "Comparison must be between same number of inputs and outputs"
+        num_chunks = -(-num_bits // 2)
+        one = self.one()
+        result = one
+        for x, y in zip(a, b):
+            res = []
+            for first, second in ((x, y), (y, x)):
+                out = self.add_virtual_target()
+                self.rows.append({"kind": "cmp", "bits": num_bits, "chunks": num_chunks, "a": first, "b": second, "res": out})
+                self.events.append(("cmp", first, second, out))
+                res.append(out)
+            a_le_b, b_le_a = res
+            these_limbs_equal = self.mul(a_le_b, b_le_a)
+            these_limbs_less_than = self.sub(one, b_le_a)
+            result = self.mul_add(these_limbs_equal, result, these_limbs_less_than)
+        return result
+
+    def list_le_u32(self, a, b):
+        """multiple_comparison.rs:69-78"""
+        return self.list_le(a, b, 32)
+
+    # -- plonky2_ecdsa/biguint/biguint.rs: a BigUintTarget is the list of its U32Target limbs, least significant first ------
+    def constant_biguint(self, value):
+        """biguint.rs:81-86 (`to_u32_digits`: zero has no limbs)"""
+        limbs = []
+        while value:
+            limbs.append(self.constant_u32(value & U32_MAX))
+            value >>= 32
+        return limbs
+
+    def zero_biguint(self):
+        """biguint.rs:88-90"""
+        return self.constant_biguint(0)
+
+    def connect_biguint(self, lhs, rhs):
+        """biguint.rs:92-104: the common limbs are connected, the others are zero."""
+        m = min(len(lhs), len(rhs))
+        for x, y in zip(lhs[:m], rhs[:m]):
+            self.connect_u32(x, y)
+        for x in lhs[m:] + rhs[m:]:
+            self.assert_zero_u32(x)
+
+    def pad_biguints(self, a, b):
+        """biguint.rs:106-126"""
+        n = max(len(a), len(b))
+        return list(a) + [self.zero_u32()] * (n - len(a)), list(b) + [self.zero_u32()] * (n - len(b))
+
+    def cmp_biguint(self, a, b):
+        """biguint.rs:128-132: a <= b"""
+        a, b = self.pad_biguints(a, b)
+        return self.list_le_u32(a, b)
+
+    def add_virtual_biguint_target(self, num_limbs):
+        """biguint.rs:134-138"""
+        return self.add_virtual_u32_targets(num_limbs)
+
+    def add_biguint(self, a, b):
+        """biguint.rs:140-162: max(len) + 1 limbs"""
+        out, carry = [], self.zero_u32()
+        for i in range(max(len(a), len(b))):
+            x = a[i] if i < len(a) else self.zero_u32()
+            y = b[i] if i < len(b) else self.zero_u32()
+            limb, carry = self.add_many_u32([carry, x, y])
+            out.append(limb)
+        return out + [carry]
+
+    def sub_biguint(self, a, b):
+        """biguint.rs:164-181: a - b for a >= b (the last borrow is not constrained, as upstream)"""
+        a, b = self.pad_biguints(a, b)
+        out, borrow = [], self.zero_u32()
+        for x, y in zip(a, b):
+            limb, borrow = self.sub_u32(x, y, borrow)
+            out.append(limb)
+        return out
+
+    def mul_biguint(self, a, b):
+        """biguint.rs:183-207: len(a) + len(b) + 1 limbs"""
+        to_add = [[] for _ in range(len(a) + len(b))]
+        for i, x in enumerate(a):
+            for j, y in enumerate(b):
+                product, carry = self.mul_u32(x, y)
+                to_add[i + j].append(product)
+                to_add[i + j + 1].append(carry)
+        out, carry = [], self.zero_u32()
+        for summands in to_add:
+            limb, carry = self.add_u32s_with_carry(summands, carry)
+            out.append(limb)
+        return out + [carry]
+
+    def mul_biguint_by_bool(self, a, b):
+        """biguint.rs:209-219"""
+        return [self.mul(l, b) for l in a]
+
+    def mul_add_biguint(self, x, y, z):
+        """biguint.rs:221-229"""
+        return self.add_biguint(self.mul_biguint(x, y), z)
+
+    def div_rem_biguint(self, a, b):
+        """biguint.rs:231-262: (div, rem) from the BigUintDivRemGenerator (event "divrem": no gate's own), then
+        a == div * b + rem and rem <= b as upstream states it."""
+        a, b = list(a), list(b)
+        div = self.add_virtual_biguint_target(0 if len(b) > len(a) + 1 else len(a) - len(b) + 1)
+        rem = self.add_virtual_biguint_target(len(b))
+        self.events.append(("divrem", tuple(a), tuple(b), tuple(div), tuple(rem)))
+        div_b_plus_rem = self.add_biguint(self.mul_biguint(div, b), rem)
+        self.connect_biguint(a, div_b_plus_rem)
+        self.assert_one(self.cmp_biguint(rem, b))
+        return div, rem
+
+    def div_biguint(self, a, b):
+        """biguint.rs:264-267"""
+        return self.div_rem_biguint(a, b)[0]
+
+    def rem_biguint(self, a, b):
+        """biguint.rs:269-272"""
+        return self.div_rem_biguint(a, b)[1]
+
+    @staticmethod
+    def divrem_values(a_limbs, b_limbs, div_limbs, rem_limbs):
+        """BigUintDivRemGenerator::run_once (biguint.rs:337-344) on limb values: a and b are the integers sum limb_i 2^(32 i)
+        over the canonical limb values (`get_biguint_target`: a limb >= 2^32 carries into the next), (div, rem) = divmod(a, b)
+        as `div_limbs` and `rem_limbs` 32-bit digits.  ValueError where upstream panics: b = 0, or more digits than limbs."""
+        a = sum(v << (32 * i) for i, v in enumerate(a_limbs))
+        b = sum(v << (32 * i) for i, v in enumerate(b_limbs))
+        if b == 0:
+            raise ValueError("unsatisfiable: div_rem_biguint divides by zero")
+        q, r = divmod(a, b)
+        if q >> (32 * div_limbs) or r >> (32 * rem_limbs):
+            raise ValueError("unsatisfiable: div_rem_biguint: the quotient or the remainder has more digits than its target has limbs")
+        return ([(q >> (32 * i)) & U32_MAX for i in range(div_limbs)], [(r >> (32 * i)) & U32_MAX for i in range(rem_limbs)])
+
     # -- build(): rows -> blob (library) + witness ----------------------------------------------------
     def _layout(self):
         """The circuit half of build(): rows -> blob, and the cells of every copy class.  Runs once; build(), seed_cells() and
@@ -319,9 +597,13 @@ class CircuitBuilder:
         # gate set, sorted by (degree, id) like CommonCircuitData.gates
         kinds = {("noop",)} if used < n else set()
         kinds |= {("const",), ("pi",)} if const_rows else {("pi",)}
+        def gate_key(g):
+            k = g["kind"]
+            return ((k, g["bits"]) if k == "ra" else ("basesum", g["L"]) if k == "basesum" else (k, g["na"]) if k == "u32addmany" else
+                    (k, len(g["limbs"])) if k == "u32range" else (k, g["bits"], g["chunks"]) if k == "cmp" else (k,))
+
         for r in rows:
-            kinds.add(("arith",) if r["kind"] == "arith" else ("poseidon",) if r["kind"] == "poseidon" else
-                      ("ra", r["bits"]) if r["kind"] == "ra" else ("basesum", r["L"]))
+            kinds.add(gate_key(r))
         spec = {("noop",): (0, "NoopGate", (G_NOOP, (0, 0, 0, 0), 0, 0)),
                 ("const",): (1, "ConstantGate { num_consts: 2 }", (G_CONSTANT, (2, 0, 0, 0), 1, 2)),
                 ("pi",): (1, "PublicInputGate", (G_PUBLIC_INPUT, (0, 0, 0, 0), 1, 0)),
@@ -337,6 +619,24 @@ class CircuitBuilder:
                 spec[k] = (k[1] + 1, "RandomAccessGate { bits: %d, num_copies: %d, num_extra_constants: %d, _phantom: "
                            "PhantomData<plonky2_field::goldilocks_field::GoldilocksField> }<D=2>" % (k[1], copies, extra),
                            (G_RANDOM_ACCESS, (k[1], copies, extra, 0), k[1] + 1, extra))
+            # the five gates of plonky2_ecdsa/biguint/gates: id() = format!("{self:?}") (ComparisonGate: + "<D=2>"), degree
+            # 1 << limb_bits = 4 (range check: BASE = 4; comparison: 1 << chunk_bits), no constants
+            elif k[0] == "u32arith":
+                ops = self.u32_gate_ops("u32arith")
+                spec[k] = (4, "U32ArithmeticGate { num_ops: %d, %s }" % (ops, _PHANTOM), (G_U32_ARITHMETIC, (ops, 0, 0, 0), 4, 0))
+            elif k[0] == "u32addmany":
+                ops = self.u32_gate_ops("u32addmany", k[1])
+                spec[k] = (4, "U32AddManyGate { num_addends: %d, num_ops: %d, %s }" % (k[1], ops, _PHANTOM),
+                           (G_U32_ADD_MANY, (k[1], ops, 0, 0), 4, 0))
+            elif k[0] == "u32sub":
+                ops = self.u32_gate_ops("u32sub")
+                spec[k] = (4, "U32SubtractionGate { num_ops: %d, %s }" % (ops, _PHANTOM), (G_U32_SUBTRACTION, (ops, 0, 0, 0), 4, 0))
+            elif k[0] == "u32range":
+                spec[k] = (4, "U32RangeCheckGate { num_input_limbs: %d, %s }" % (k[1], _PHANTOM), (G_U32_RANGE_CHECK, (k[1], 0, 0, 0), 4, 0))
+            elif k[0] == "cmp":
+                chunk_bits = -(-k[1] // k[2])
+                spec[k] = (1 << chunk_bits, "ComparisonGate { num_bits: %d, num_chunks: %d, %s }<D=2>" % (k[1], k[2], _PHANTOM),
+                           (G_COMPARISON, (k[1], k[2], 0, 0), 1 << chunk_bits, 0))
         order = sorted(kinds, key=lambda k: (spec[k][0], spec[k][1]))
         index = {k: i for i, k in enumerate(order)}
         gates = [spec[k][2] for k in order]
@@ -371,11 +671,28 @@ class CircuitBuilder:
                     put(claimed, r, (2 + vec) * k + 1)
                     for j, t in enumerate(lst):
                         put(t, r, (2 + vec) * k + 2 + j)
-            else:
+            elif g["kind"] == "basesum":
                 row_gate[r] = index[("basesum", g["L"])]
                 put(g["sum"], r, 0)
                 for j, t in enumerate(g["limbs"]):
                     put(t, r, 1 + j)
+            else:
+                # the five gates of plonky2_ecdsa/biguint/gates: an operation's routed wires follow each other (arithmetic_u32.rs
+                # :44-69 six per op, add_many_u32.rs:50-70 addends, carry, result, carry out, subtraction_u32.rs:45-65 five per op)
+                row_gate[r] = index[gate_key(g)]
+                g["row"] = r
+                if g["kind"] == "u32range":          # range_check_u32.rs:40-43
+                    for j, t in enumerate(g["limbs"]):
+                        put(t, r, j)
+                elif g["kind"] == "cmp":             # comparison.rs:52-62
+                    put(g["a"], r, 0)
+                    put(g["b"], r, 1)
+                    put(g["res"], r, 2)
+                else:
+                    stride = 6 if g["kind"] == "u32arith" else 5 if g["kind"] == "u32sub" else g["na"] + 3
+                    for k, op in enumerate(g["ops"]):
+                        for j, t in enumerate(op):
+                            put(t, r, stride * k + j)
         row_gate[pi_row] = index[("pi",)]
         for i in range(4):                          # (no public inputs: four copies of `zero`)
             put(pi_hash[i], pi_row, i)
@@ -452,6 +769,39 @@ class CircuitBuilder:
                     if vs[0] >= len(lst):
                         raise ValueError("unsatisfiable: a random access reads position %d of %d" % (vs[0], len(lst)))
                     self._set(val, claimed, vs[1 + vs[0]])
+                elif ev[0] in ("u32arith", "u32addmany", "u32sub", "u32range", "cmp", "divrem"):
+                    ins = {"u32arith": ev[1:4], "u32sub": ev[1:4], "cmp": ev[1:3], "u32range": ev[1]}.get(ev[0])
+                    if ev[0] == "u32addmany":
+                        ins = ev[1] + (ev[2],)
+                    elif ev[0] == "divrem":
+                        ins = ev[1] + ev[2]
+                    vs = [val.get(self.find(t)) for t in ins]
+                    if any(v is None for v in vs):
+                        rest.append(ev)
+                        continue
+                    if ev[0] == "u32arith":          # U32ArithmeticGenerator, arithmetic_u32.rs:376-426
+                        o = (vs[0] * vs[1] + vs[2]) % P
+                        self._set(val, ev[4], o & U32_MAX)
+                        self._set(val, ev[5], o >> 32)
+                    elif ev[0] == "u32addmany":      # U32AddManyGenerator, add_many_u32.rs:329-378
+                        o = sum(vs) % P
+                        self._set(val, ev[3], o & U32_MAX)
+                        self._set(val, ev[4], o >> 32)
+                    elif ev[0] == "u32sub":          # U32SubtractionGenerator, subtraction_u32.rs:298-343
+                        init = (vs[0] - vs[1] - vs[2]) % P
+                        borrow = 1 if init > 1 << 32 else 0
+                        self._set(val, ev[4], (init + (borrow << 32)) % P)
+                        self._set(val, ev[5], borrow)
+                    elif ev[0] == "u32range":        # (no target is set; a limb of more than 32 bits has no two-bit limbs)
+                        if any(v > U32_MAX for v in vs):
+                            raise ValueError("unsatisfiable: a range-checked limb has more than 32 bits")
+                    elif ev[0] == "cmp":             # ComparisonGenerator, comparison.rs:439-537
+                        self._set(val, ev[3], 1 if vs[0] <= vs[1] else 0)
+                    else:                            # BigUintDivRemGenerator, biguint.rs:337-344
+                        _, a, b, div, rem = ev
+                        q, r = self.divrem_values(vs[:len(a)], vs[len(a):], len(div), len(rem))
+                        for t, v in zip(div + rem, q + r):
+                            self._set(val, t, v)
                 elif ev[0] == "split":
                     v = val.get(self.find(ev[1]))
                     if v is None:
@@ -491,6 +841,9 @@ class CircuitBuilder:
                 for k, (idx, _, _) in enumerate(g["copies"]):
                     for i in range(bits):
                         wires[routed + k * bits + i, g["row"]] = (val[self.find(idx)] >> i) & 1
+        for g in rows:                              # the U32 and comparison rows: every operation's generator, the unused ones' too
+            if g["kind"] in ("u32arith", "u32addmany", "u32sub", "u32range", "cmp"):
+                self._fill_u32_row(wires, g)
         # circuit_builder.rs randomize_unused_pi_wires: every wire of the PublicInputGate row after the hash, routed
         # or not, gets a random value (so no wire column of a real witness is zero in every row)
         wires[4:NUM_ROUTED, pi_row] = self.rng.integers(0, P, size=NUM_ROUTED - 4, dtype=np.uint64)
@@ -499,13 +852,82 @@ class CircuitBuilder:
         self.values = val
         return blob, wires
 
+    def _fill_u32_row(self, wires, g):
+        """The row's generator(s) as the reference states them, on the row's routed inputs as they stand in `wires` (zeros for
+        an operation nobody took): the outputs and the gate-internal columns -- two-bit limbs, the inverse of u32::MAX - high,
+        the comparison's chunks, equalities, intermediate values and the bits of the most significant difference."""
+        r = g["row"]
+
+        def get(c):
+            return int(wires[c, r])
+
+        def limbs(base, v, count):
+            for j in range(count):
+                wires[base + j, r] = (v >> (2 * j)) & 3
+
+        if g["kind"] == "u32arith":                  # arithmetic_u32.rs:376-426; wires :44-85
+            ops = g["num_ops"]
+            for i in range(ops):
+                o = (get(6 * i) * get(6 * i + 1) + get(6 * i + 2)) % P
+                low, high = o & U32_MAX, o >> 32
+                wires[6 * i + 3, r], wires[6 * i + 4, r] = low, high
+                wires[6 * i + 5, r] = pow(U32_MAX - high, P - 2, P)      # (0 when high is u32::MAX)
+                limbs(6 * ops + 32 * i, o, 32)
+        elif g["kind"] == "u32addmany":              # add_many_u32.rs:329-378; wires :50-86
+            na, ops = g["na"], g["num_ops"]
+            for i in range(ops):
+                b = (na + 3) * i
+                o = sum(get(b + j) for j in range(na + 1)) % P
+                wires[b + na + 1, r], wires[b + na + 2, r] = o & U32_MAX, o >> 32
+                limbs((na + 3) * ops + 18 * i, o & U32_MAX, 16)
+                limbs((na + 3) * ops + 18 * i + 16, o >> 32, 2)
+        elif g["kind"] == "u32sub":                  # subtraction_u32.rs:298-343; wires :45-79
+            ops = g["num_ops"]
+            for i in range(ops):
+                init = (get(5 * i) - get(5 * i + 1) - get(5 * i + 2)) % P
+                borrow = 1 if init > 1 << 32 else 0
+                res = (init + (borrow << 32)) % P
+                wires[5 * i + 3, r], wires[5 * i + 4, r] = res, borrow
+                limbs(5 * ops + 16 * i, res, 16)
+        elif g["kind"] == "u32range":                # range_check_u32.rs:198-220; wires :40-51
+            nl = len(g["limbs"])
+            for i in range(nl):
+                limbs(nl + 16 * i, get(i) & U32_MAX, 16)
+        else:                                        # comparison.rs:439-537; wires :52-96
+            nb, nc = g["bits"], g["chunks"]
+            cb = -(-nb // nc)
+            a, b = get(0), get(1)
+            wires[2, r] = 1 if a <= b else 0
+            msd = 0
+            for i in range(nc):
+                f, s2 = (a >> (cb * i)) & ((1 << cb) - 1), (b >> (cb * i)) & ((1 << cb) - 1)
+                wires[4 + i, r], wires[4 + nc + i, r] = f, s2
+                wires[4 + 2 * nc + i, r] = 1 if f == s2 else pow((s2 - f) % P, P - 2, P)
+                wires[4 + 3 * nc + i, r] = 1 if f == s2 else 0
+                if f != s2:
+                    msd = (s2 - f) % P
+                    wires[4 + 4 * nc + i, r] = 0
+                else:
+                    wires[4 + 4 * nc + i, r] = msd
+            wires[3, r] = msd
+            v = ((1 << cb) + msd) % P
+            for i in range(cb + 1):
+                wires[4 + 5 * nc + i, r] = (v >> i) & 1
+
     # -- the witness on the GPU: what the caller still has to supply ------------------------------------
     def _seed_classes(self):
         """(cells, roots) of the seeds that carry a value of the program: one cell per copy class that holds no constant and
         no generator's output -- the targets `pw.set_target` is called on -- in the order of the classes' first targets."""
         _, _, _, _, cells, _ = self._layout()
         derived = {self.find(t) for t in self.const_of}
+        # the operands of a div-rem generator are the program's when nothing created before it derives them: `div_rem_biguint`
+        # connects a to div * b + rem afterwards, which compares (biguint.rs:254-256) and does not make `a` an output.  (A seed
+        # names the first cell of its class: an operand that enters the circuit nowhere before div_rem_biguint has that result
+        # column as its only cell, and the row op then shares the cell's writer bit with the seed -- DESIGN.md 11.6.)
+        given = set()
         for ev in self.events:
+            if ev[0] == "divrem":
+                given.update(self.find(t) for t in ev[1] + ev[2] if self.find(t) not in derived)
             if ev[0] == "arith":
                 derived.add(self.find(ev[6]))
             elif ev[0] == "poseidon":
@@ -514,12 +936,22 @@ class CircuitBuilder:
                 derived.update((self.find(ev[3]), self.find(ev[4])))
             elif ev[0] == "ra":
                 derived.add(self.find(ev[3]))
+            elif ev[0] in ("u32arith", "u32sub"):
+                derived.update((self.find(ev[4]), self.find(ev[5])))
+            elif ev[0] == "u32addmany":
+                derived.update((self.find(ev[3]), self.find(ev[4])))
+            elif ev[0] == "cmp":
+                derived.add(self.find(ev[3]))
+            elif ev[0] == "divrem":
+                derived.update(self.find(t) for t in ev[3] + ev[4])
+            elif ev[0] == "u32range":
+                pass
             elif ev[0] == "split":
                 assert len(ev[2]) == 1, "a split over several BaseSum rows spans rows: not a gate-local generator"
                 derived.update(self.find(t) for t in ev[2][0]["limbs"])
             else:
                 derived.add(self.find(ev[1]["sum"]))
-        roots = sorted(rt for rt in cells if rt not in derived)
+        roots = sorted(rt for rt in cells if rt not in derived or rt in given)
         return [cells[rt][0] for rt in roots], roots
 
     def seed_cells(self):
@@ -546,8 +978,9 @@ class CircuitBuilder:
         return out
 
     def generators(self):
-        """The generators that are no gate's own, for CircuitData.witness_plan(..., generators=): [("equality", (cell_x, cell_y,
-        cell_equal, cell_inv))] in creation order; a target's cell is the first cell of its copy class."""
+        """The generators that are no gate's own, for CircuitData.witness_plan(..., generators=): ("equality", (cell_x, cell_y,
+        cell_equal, cell_inv)) and ("biguint_divrem", (a_cells, b_cells, div_cells, rem_cells)) in creation order; a target's
+        cell -- a limb's too -- is the first cell of its copy class."""
         _, _, _, _, cells, _ = self._layout()
         out = []
         for ev in self.events:
@@ -556,6 +989,11 @@ class CircuitBuilder:
                 if any(c is None for c in cl):
                     raise ValueError("is_equal: a target of the equality generator lies in no gate row")
                 out.append(("equality", tuple(c[0] for c in cl)))
+            elif ev[0] == "divrem":
+                groups = [[cells.get(self.find(t)) for t in grp] for grp in ev[1:]]
+                if any(c is None for grp in groups for c in grp):
+                    raise ValueError("div_rem_biguint: a limb of the div-rem generator lies in no gate row")
+                out.append(("biguint_divrem", tuple(tuple(c[0] for c in grp) for grp in groups)))
         return out
 
     def _set(self, val, t, v):

@@ -24,6 +24,9 @@
  *                          <- the same plans for a circuit that holds generators which are no gate's own: the
  *                             EqualityGenerators of `builder.is_equal` (gadgets/arithmetic.rs), which the memory writes of
  *                             the ACIR translation are made of (circuit_translation/memory_translator.rs:89-112)
+ *   p2gpu_witness_plan_create_genv / p2gpu_witness_plan_build_genv
+ *                          <- the same with generators of any number of cells: the BigUintDivRemGenerator of
+ *                             `div_rem_biguint` (plonky2_ecdsa/biguint/biguint.rs:231-262, :317-344), whose cells are limbs
  *   p2gpu_generate_witness_batch
  *                          <- the same for many value sets of one circuit at once (the reference has no counterpart: it
  *                             calls `prove` once per witness)
@@ -67,7 +70,7 @@
  *   0 Noop  1 Constant{p0=num_consts}  2 PublicInput  3 Arithmetic{p0=num_ops}
  *   4 BaseSum{p0=B,p1=num_limbs}  5 RandomAccess{p0=bits,p1=copies,p2=extra_consts}
  *   6 Poseidon (PoseidonGate, width 12)  7 U32Arithmetic{p0=num_ops}
- *   8 U32AddMany{p0=num_addends,p1=num_ops}  9 U32Subtraction{p0=num_ops}
+ *   8 U32AddMany{p0=num_addends 0..16,p1=num_ops}  9 U32Subtraction{p0=num_ops}
  *   10 U32RangeCheck{p0=num_input_limbs}  11 Comparison{p0=num_bits,p1=num_chunks}
  *
  * Proof bytes: plonky2's uncompressed ProofWithPublicInputs::to_bytes layout
@@ -194,8 +197,10 @@ int p2gpu_witness_plan_build(p2gpu_circuit *c, const uint32_t *seed_cells /* [n_
  * cells get value slots, the first op by level and creation order that reaches a slot writes it and every other one compares.
  * P2GPU_E_ARG, worded in p2gpu_last_error: an unknown kind, a cell outside [n] x [num_routed_wires] (with the generator's index
  * and the cell), n_generators > 0 with a null list; an input cell that nothing writes is the "a seed is missing" refusal.  A
- * contradiction of a generator at p2gpu_generate_witness reads "generator <i>: cell (row, column)".  Only the equality generator
- * is built; the record has a kind and four cells so that a later one fits. */
+ * contradiction of a generator at p2gpu_generate_witness reads "generator <i>: cell (row, column)".  These two entry points take
+ * records of four cells and know the equality generator only (any other kind is an unknown kind here, as it always was); a
+ * generator of another kind or number of cells goes through the _genv pair below, of which these are the case of equality
+ * generators, shapes {1, 1, 1, 1}. */
 #define P2GPU_GEN_EQUALITY 0   /* cells: x, y (read), equal, inv (set): equal = (x == y), inv = x == y ? 0 : 1 / (x - y) */
 typedef struct { uint32_t kind; uint32_t cells[4][2]; /* (row, col), routed columns only */ } p2gpu_generator;
 int p2gpu_witness_plan_create_gen(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds,
@@ -204,8 +209,41 @@ int p2gpu_witness_plan_create_gen(p2gpu_circuit *c, const uint32_t *seed_cells, 
 int p2gpu_witness_plan_build_gen(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds,
                                  const p2gpu_generator *generators, size_t n_generators, p2gpu_witness_plan **out);
 /* the plan's generator table, read back: [n_generators][4] words, cell key (col << d | row) | bit 31 = this generator writes the
- * cell's slot (its writer bits live here, not in cell_slot).  *n_generators is always filled; with table NULL nothing else happens */
+ * cell's slot (its writer bits live here, not in cell_slot).  *n_generators is always filled; with table NULL nothing else happens.
+ * P2GPU_E_ARG for a plan one of whose generators has another number of cells than four. */
 int p2gpu_witness_plan_export_generators(const p2gpu_witness_plan *p, uint32_t *table, size_t *n_generators);
+/* ---- generators with any number of cells ----
+ * A record is a kind and a shape, the cell counts of the generator's four groups; the cells of all generators follow each other
+ * in one flat (row, col) list, shape[0] + .. + shape[3] per generator, in list order.
+ *   P2GPU_GEN_EQUALITY        {1, 1, 1, 1}: x, y (read), equal, inv (set)
+ *   P2GPU_GEN_BIGUINT_DIVREM  {la, lb, ld, lr}: the limbs of a and of b (read), of div and of rem (set), least significant
+ *                             first -- the BigUintDivRemGenerator that `div_rem_biguint` registers (plonky2_ecdsa/biguint/
+ *                             biguint.rs:231-262, :317-344; the Rust side lists it at that call site).  a and b are
+ *                             the integers sum limb_i 2^(32 i) over the canonical limb values (a limb >= 2^32 carries into the
+ *                             next, as `get_biguint_target` folds them); (div, rem) = divmod(a, b) as 32-bit digits.  The shape
+ *                             is div_rem_biguint's: 1 <= la <= 32, 1 <= lb <= 16, lr = lb, ld = lb > la + 1 ? 0 : la - lb + 1.
+ *                             Where upstream panics, p2gpu_generate_witness answers P2GPU_E_UNSATISFIED with the generator and
+ *                             a cell: b = 0 -> b's first cell; a quotient or remainder with more digits than its target has
+ *                             limbs -> that target's top limb (a quotient for a target without limbs: a's first cell).
+ * Every rule of the plan holds per cell position: a slot that several input positions name is one dependency;
+ * among the outputs the first position that names a slot may write it, every later one compares.  The op record of a generator is
+ * list index | code << 32, code 13 for equality and 14 for div-rem.  P2GPU_E_ARG, worded in p2gpu_last_error and checked before
+ * anything indexes with a cell: an unknown kind, a shape that is not the kind's, n_cells different from the shapes' sum (fewer:
+ * reported at the first generator whose cells run past the list, with the sum up to it), a cell
+ * outside [n] x [num_routed_wires] (with the generator's index and the cell), a counted list behind a null pointer. */
+#define P2GPU_GEN_BIGUINT_DIVREM 1
+typedef struct { uint32_t kind; uint32_t shape[4]; } p2gpu_generator_v;
+int p2gpu_witness_plan_create_genv(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, const p2gpu_generator_v *generators,
+                                   size_t n_generators, const uint32_t *cells /* [n_cells][2] = (row, col) */, size_t n_cells,
+                                   p2gpu_witness_plan **out);
+/* the same arguments: compiled on the device */
+int p2gpu_witness_plan_build_genv(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, const p2gpu_generator_v *generators,
+                                  size_t n_generators, const uint32_t *cells, size_t n_cells, p2gpu_witness_plan **out);
+/* the plan's generator table of any plan, read back: off [n_generators + 1], the first table word of every generator, and table
+ * [off[n_generators]], one word per cell in list order: cell key (col << d | row) | bit 31 = this naming writes the cell's slot.
+ * sizes = { n_generators, off[n_generators] } is always filled; with both pointers NULL nothing else happens.  For a list of
+ * equality generators the table is p2gpu_witness_plan_export_generators' byte for byte. */
+int p2gpu_witness_plan_export_generators_v(const p2gpu_witness_plan *p, uint32_t *off, uint32_t *table, size_t sizes[2]);
 /* The plan's three device arrays, read back: cell_slot [num_routed_wires][n] (the value slot of every routed cell, 0xFFFFFFFF:
  * none, bit 31: this cell's op writes the slot), ops [n_ops] (row | (code | sub << 8) << 32, by level and creation order),
  * level_off [levels + 1].  sizes = { num_routed_wires * n, n_ops, levels + 1 } is always filled; with all three pointers NULL
