@@ -32,6 +32,7 @@ struct WalkArgs {
   const uint32_t *gen_table;  // one word per cell a generator names: cell key | WRITER; generator g's begin at gen_off[g]
   const uint32_t *gen_off;    // [generators + 1]
   const uint32_t *gen_shape;  // [generators] la | lb << 8 | ld << 16 | lr << 24
+  const uint32_t *seed_out;   // a bit per routed cell: a seed's cell that a row op of its row sets as well; null when there is none
   gl_t *val;                  // [slots][B]
   const uint2 *seed_cells;    // (row, col)
   const gl_t *seed_vals;      // [seeds][B]
@@ -48,7 +49,11 @@ struct RowSlots {
   size_t row;
   uint32_t pos;  // of the op in the schedule
   uint32_t b;    // witness of the batch
+  bool seed = false;  // the op is a seed: the writer bit of a cell that a seed and a row op both set is the seed's
   __device__ __forceinline__ gl_t &slot(uint32_t s) const { return a.val[(size_t)s * a.B + b]; }
+  // whether the writer bit of cell `key` is this op's: a row op's unless a seed names the very cell -- that seed wrote (or compared
+  // with) the slot in an earlier level, so the row op compares
+  __device__ __forceinline__ bool owns_bit(size_t key) const { return seed || !a.seed_out || !((a.seed_out[key >> 5] >> (key & 31)) & 1); }
   __device__ __forceinline__ gl_t get(uint32_t col) const {
     if (col >= a.R) return 0;
     const uint32_t s = a.cell_slot[((size_t)col << a.d) + row];
@@ -56,10 +61,11 @@ struct RowSlots {
   }
   __device__ __forceinline__ void set(uint32_t col, gl_t v) {
     if (col >= a.R) return;  // gate-internal column: fill_witness derives it
-    const uint32_t s = a.cell_slot[((size_t)col << a.d) + row];
+    const size_t key = ((size_t)col << a.d) + row;
+    const uint32_t s = a.cell_slot[key];
     if (s == UNSET) return;
-    if (s & WRITER) slot(s & ~WRITER) = v;
-    else if (slot(s) != v) reject(col);
+    if ((s & WRITER) && owns_bit(key)) slot(s & ~WRITER) = v;
+    else if (slot(s & ~WRITER) != v) reject(col);
   }
   __device__ __forceinline__ gl_t lc(uint32_t i) const { return i < a.ngc ? a.gconsts[((size_t)i << a.d) + row] : (gl_t)0; }
   __device__ __forceinline__ void reject(uint32_t col) { atomicMin(a.err + b, ((unsigned long long)pos << 8) | col); }
@@ -102,7 +108,7 @@ __device__ __forceinline__ void run_op(const WalkArgs &a, uint32_t pos, uint32_t
   if (code == OP_SEED) {
     const uint2 cell = a.seed_cells[op.x];
     const gl_t v = a.seed_vals[(size_t)op.x * a.B + b];
-    RowSlots w{a, cell.x, pos, b};
+    RowSlots w{a, cell.x, pos, b, true};
     if (v >= GL_P) w.reject(cell.y);
     else w.set(cell.y, v);
     return;
@@ -188,6 +194,7 @@ int walk_and_scatter(p2gpu_witness_plan *p, uint32_t B, gl_t *wires) {
   HIP_TRY(hipMemsetAsync(p->err.p, 0xFF, 8 * (size_t)B, st));
   WalkArgs a;
   a.ops = p->ops.p; a.level_off = p->level_off.p; a.levels = p->levels; a.cell_slot = p->cell_slot.p; a.gen_table = p->gen_table.p; a.gen_off = p->gen_off.p; a.gen_shape = p->gen_shape.p; a.val = p->val.p;
+  a.seed_out = p->has_seed_out ? p->seed_out.p : nullptr;
   a.seed_cells = p->seed_cells.p; a.seed_vals = p->seed_vals.p; a.row_gate = c->d_row_gate.p; a.gates = c->d_gates.p;
   a.gconsts = c->d_gconsts.p; a.prc = c->d_prc.p; a.err = p->err.p; a.d = c->d; a.R = c->R; a.ngc = ngc; a.B = B;
   HIP_TRY(hipEventRecord(p->ev0, st));

@@ -21,7 +21,10 @@
 //                             that nothing writes is an unreached slot: "a seed is missing", with that cell.
 //             writer bits     a generator's live in ITS OWN table word (gen_table [generators][4]: cell key | bit 31), not in
 //                             cell_slot, whose bit keeps meaning "the row op (or seed) that has this cell as an output writes
-//                             it": a cell that is a generator's output and a row op's output has one writer.  The level rule
+//                             it": a cell that is a generator's output and a row op's output has one writer.  A seed and a
+//                             row op can name ONE cell as their output, and then share its bit: it is the seed's (a seed's slot
+//                             is written in level 0, by this seed or by an earlier one of its class), the row op compares there
+//                             (the walk knows such cells from the plan's seed list: witplan.hpp seed_out).  The level rule
 //                             is unchanged: the first by (level, creation order) writes, every other op that derives the slot
 //                             -- another generator, a seed, a row op -- compares, one level above at least.
 //             refusals        before anything indexes with the cells: an unknown kind, a cell outside [n] x [R].

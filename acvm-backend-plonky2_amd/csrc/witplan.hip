@@ -45,6 +45,30 @@ int plan_finish(p2gpu_witness_plan *p, const PlanArrays &a) {
     if (a.kind == hipMemcpyHostToDevice) memcpy(p->h_gen_table.data(), a.gen_table, 4 * p->h_gen_table.size());
     else HIP_TRY(hipMemcpyAsync(p->h_gen_table.data(), a.gen_table, 4 * p->h_gen_table.size(), hipMemcpyDeviceToHost, c->stream));
   }
+  // the seeds on a row op's own output column (witplan.hpp seed_out): the registry's output columns of the seed's row
+  {
+    std::vector<uint8_t> row_gate(c->n);
+    HIP_TRY(hipMemcpyAsync(row_gate.data(), c->d_row_gate.p, c->n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<uint32_t> bits;
+    for (const PlanSeed &cell : p->h_seed_cells) {
+      if (cell.col >= c->R || row_gate[cell.row] >= c->gates.size()) continue;
+      const GateDesc &g = c->gates[row_gate[cell.row]];
+      bool is_out = false;
+      for (uint32_t k = 0, m = row_num_ops(g); k < m && !is_out; k++)
+        for_cols(row_op(g, k, 1, 1).out, [&](uint32_t col) { is_out |= col == cell.col; });
+      if (!is_out) continue;
+      if (bits.empty()) bits.assign((tot + 31) / 32, 0);
+      const size_t key = ((size_t)cell.col << c->d) + cell.row;
+      bits[key >> 5] |= 1u << (key & 31);
+    }
+    p->has_seed_out = !bits.empty();
+    if (p->has_seed_out) {
+      HIP_TRY(p->seed_out.alloc(bits.size()));
+      HIP_TRY(hipMemcpyAsync(p->seed_out.p, bits.data(), 4 * bits.size(), hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));  // (bits goes out of scope)
+    }
+  }
   if (int rc = plan_reserve(p, 1)) return rc;
   HIP_TRY(hipEventCreate(&p->ev0));
   HIP_TRY(hipEventCreate(&p->ev1));

@@ -19,6 +19,10 @@ struct p2gpu_witness_plan {
   std::vector<uint32_t> h_gen_table;
   p2::DBuf<uint32_t> gen_table, gen_off, gen_shape;
   bool has_divrem = false;  // a div-rem generator is listed: the walk kernel's form with that arm runs this plan
+  // One bit per routed cell, set for a seed's cell that is also an output column of a row op of its row: the cell's writer bit is
+  // the seed's there, and the row op compares (planhost.hpp, "writer bits").  Not allocated when the plan has no such cell.
+  p2::DBuf<uint32_t> seed_out;
+  bool has_seed_out = false;
   // The values of `cap` witnesses (plan_finish: 1; a batch grows them).  A call of B <= cap witnesses lays its values out
   // with its own B as the stride, in the front of the buffers: val [slots][B], seed_vals [n_seeds][B], err [B].
   size_t cap = 0;
@@ -34,6 +38,7 @@ struct p2gpu_witness_plan {
   }
   void release() {
     ops.release(); level_off.release(); cell_slot.release(); seed_cells.release(); gen_table.release(); gen_off.release(); gen_shape.release();
+    seed_out.release();
     release_values();
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
