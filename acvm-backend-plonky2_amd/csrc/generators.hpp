@@ -11,6 +11,7 @@
 #pragma once
 #include "bigdiv.hpp"
 #include "internal.hpp"
+#include "nonnative.hpp"
 #include "poseidon.hpp"
 
 namespace p2 {
@@ -100,6 +101,85 @@ __device__ void gen_biguint_divrem(A &a, const uint32_t shape[4]) {
   for (uint32_t i = lr; i < w.nv; i++) r_over |= w.remainder_word(i) != 0;
   if (q_over) a.reject(ld ? la + lb + ld - 1 : 0);
   if (r_over) a.reject(la + lb + ld + lr - 1);
+}
+
+// The four nonnative generators (plonky2_ecdsa/biguint/gadgets/nonnative.rs, registered by `add_nonnative` :193, `sub_nonnative`
+// :292, `mul_nonnative` :323, `inv_nonnative` :370): no gate's own.  Their accessor numbers the cells a[0 .. la), b[0 .. lb) (read)
+// and then the two targets they set, least significant limb first; shape as the plan checked it (la, lb <= 16), field < NN_FIELDS
+// from the op record.  M is the field's modulus, A = fold(a) mod M, B = fold(b) mod M (nonnative.hpp: upstream's
+// FF::from_noncanonical_biguint); what is set are 32-bit digits, zeros in the limbs beyond them.  Where upstream panics the walk
+// rejects, by the div-rem generator's rule: a value with more digits than its target has limbs on that target's top limb (on
+// the generator's first cell when the target has no limbs), the inverse of zero on x's first cell.  Not forced inline, for the
+// reason gen_biguint_divrem is not.
+template <class A>
+__device__ __forceinline__ void nn_load(A &a, NonNative &f, uint32_t first, uint32_t count, uint32_t *out) {
+  for (uint32_t i = 0; i < count; i++) f.push(i, a.get(first + i));
+  f.reduce(count, out);
+}
+// word(0) .. word(digits - 1) into the `limbs` cells from `first` on
+template <class A, class F>
+__device__ __forceinline__ void nn_store(A &a, uint32_t first, uint32_t limbs, uint32_t digits, F &&word) {
+  for (uint32_t i = 0; i < limbs; i++) a.set(first + i, i < digits ? (gl_t)word(i) : (gl_t)0);
+  bool over = false;
+  for (uint32_t i = limbs; i < digits; i++) over |= word(i) != 0;
+  if (over) a.reject(limbs ? first + limbs - 1 : 0);
+}
+
+// NonNativeAdditionGenerator (:469-484): S = A + B; S > M (strictly, as upstream: A + B = M leaves sum = M): sum = S - M,
+// overflow = 1; otherwise sum = S, overflow = 0.  shape {la, lb, 8, 1}
+template <class A>
+__device__ void gen_nonnative_add(A &a, const uint32_t shape[4], uint32_t field) {
+  const uint32_t la = shape[0], lb = shape[1], out = la + lb;
+  NonNative f(field);
+  uint32_t x[NN_LIMBS], y[NN_LIMBS];
+  nn_load(a, f, 0, la, x);
+  nn_load(a, f, la, lb, y);
+  const bool over = f.add_once(x, y);
+  nn_store(a, out, shape[2], NN_LIMBS, [&](uint32_t i) { return x[i]; });
+  nn_store(a, out + shape[2], shape[3], 1, [&](uint32_t) { return over ? 1u : 0u; });
+}
+
+// NonNativeSubtractionGenerator (:589-604): A >= B: diff = A - B, overflow = 0; otherwise diff = M + A - B, overflow = 1.
+// shape {la, lb, 8, 1}
+template <class A>
+__device__ void gen_nonnative_sub(A &a, const uint32_t shape[4], uint32_t field) {
+  const uint32_t la = shape[0], lb = shape[1], out = la + lb;
+  NonNative f(field);
+  uint32_t x[NN_LIMBS], y[NN_LIMBS];
+  nn_load(a, f, 0, la, x);
+  nn_load(a, f, la, lb, y);
+  const bool over = f.sub_once(x, y);
+  nn_store(a, out, shape[2], NN_LIMBS, [&](uint32_t i) { return x[i]; });
+  nn_store(a, out + shape[2], shape[3], 1, [&](uint32_t) { return over ? 1u : 0u; });
+}
+
+// NonNativeMultiplicationGenerator (:645-658): (Q, R) = divmod(A B, M); prod = R, overflow = Q.  shape {la, lb, 8, la + lb - 8}
+template <class A>
+__device__ void gen_nonnative_mul(A &a, const uint32_t shape[4], uint32_t field) {
+  const uint32_t la = shape[0], lb = shape[1], out = la + lb;
+  NonNative f(field);
+  uint32_t x[NN_LIMBS], y[NN_LIMBS];
+  nn_load(a, f, 0, la, x);
+  nn_load(a, f, la, lb, y);
+  f.mul_divmod(x, y);
+  nn_store(a, out, shape[2], NN_LIMBS, [&](uint32_t i) { return f.w.remainder_word(i); });
+  nn_store(a, out + shape[2], shape[3], f.w.nq, [&](uint32_t i) { return f.w.quotient_word(i); });
+}
+
+// NonNativeInverseGenerator (:691-703): X = fold(x) mod M, inv = X^-1 mod M, div = (X inv) div M.  shape {lx, 0, lx, lx}
+template <class A>
+__device__ void gen_nonnative_inv(A &a, const uint32_t shape[4], uint32_t field) {
+  const uint32_t lx = shape[0], out = lx + shape[1];
+  NonNative f(field);
+  uint32_t x[NN_LIMBS], inv[NN_LIMBS];
+  nn_load(a, f, 0, lx, x);
+  if (!f.invert(x, inv)) {
+    a.reject(0);
+    return;
+  }
+  nn_store(a, out, shape[2], NN_LIMBS, [&](uint32_t i) { return inv[i]; });
+  f.mul_divmod(x, inv);
+  nn_store(a, out + shape[2], shape[3], f.w.nq, [&](uint32_t i) { return f.w.quotient_word(i); });
 }
 
 // prc: the 360 round constants (wave-uniform index -> scalar loads)

@@ -148,7 +148,7 @@ __global__ void plan_gen_slots_kernel(const uint32_t *gkeys, uint32_t NE, const 
   const uint32_t e = blockIdx.x * TPB + threadIdx.x;
   if (e < NE && flag[e]) cell_slot[gkeys[e]] = (uint32_t)*base + scan[e];
 }
-// gmeta[g] = input cells | op code << 16
+// gmeta[g] = input cells | (op code | field << 8) << 16
 __global__ void plan_gen_ops_kernel(uint32_t S, uint32_t G, const uint32_t *gmeta, OpRec *recs) {
   const uint32_t i = blockIdx.x * TPB + threadIdx.x;
   if (i < G) recs[S + i] = make_uint2(i, gmeta[i] >> 16);
@@ -236,7 +236,7 @@ struct OpView {
   const uint32_t *gkeys;  // the generators' cell keys, generator g's from goff[g] on: its gmeta[g] & 0xFFFF inputs, then its outputs
   uint32_t *gen_table;    // the same with the writer bits the schedule sets
   const uint32_t *goff;   // [generators + 1]
-  const uint32_t *gmeta;  // [generators] input cells | op code << 16
+  const uint32_t *gmeta;  // [generators] input cells | (op code | field << 8) << 16
   template <class F> __device__ __forceinline__ void ins(uint32_t i, F &&f) const {
     const OpRec r = recs[i];
     const uint32_t code = r.y & 0xFF;
@@ -591,7 +591,7 @@ int PlanCtx::slots_ops() {
   if (NE) {
     std::vector<uint32_t> hkeys(NE), hmeta(NG);
     for (uint32_t e = 0; e < NE; e++) hkeys[e] = (gens.cells[2 * (size_t)e + 1] << d) + gens.cells[2 * (size_t)e];
-    for (uint32_t g = 0; g < NG; g++) hmeta[g] = gens.ins(g) | gens.code(g) << 16, gen_ins += gens.ins(g);
+    for (uint32_t g = 0; g < NG; g++) hmeta[g] = gens.ins(g) | gens.code_word(g) << 16, gen_ins += gens.ins(g);
     // (pageable memory: the copies have left the vectors when the call returns)
     if (!ok(hipMemcpyAsync(gkeys, hkeys.data(), 4 * (size_t)NE, hipMemcpyHostToDevice, st), "copy the generator cells")) return P2GPU_E_DEVICE;
     if (!ok(hipMemcpyAsync(goff, gens.off.data(), 4 * ((size_t)NG + 1), hipMemcpyHostToDevice, st), "copy the generator cells")) return P2GPU_E_DEVICE;

@@ -91,8 +91,8 @@ struct GenSlots {
 
 // The div-rem generator, called and not inlined: its word arrays (bigdiv.hpp, 53 words and the loop state) are private memory
 // of THIS frame.  A call in the kernel still costs every other arm (the SHA-256 walk 15.5 -> 23.8 ms: profiles/
-// device_witness.md), so the arm exists only in the walk kernel's DIVREM = true form, which runs the plans that list such a
-// generator; every other plan runs the form without it.  Lanes of one op run it with different trip counts.
+// device_witness.md), so the big-integer arms exist only in the walk kernel's BIGINT = true form, which runs the plans that list such a
+// generator (or a nonnative one, below); every other plan runs the form without them.  Lanes of one op run it with different trip counts.
 static_assert(BIGDIV_MAX_A == PLAN_DIVREM_MAX_A && BIGDIV_MAX_B == PLAN_DIVREM_MAX_B, "the plan admits the shapes the division's arrays hold");
 __device__ __noinline__ void run_biguint_divrem(const WalkArgs &a, uint32_t g, uint32_t pos, uint32_t b) {
   const uint32_t sw = a.gen_shape[g];
@@ -101,7 +101,22 @@ __device__ __noinline__ void run_biguint_divrem(const WalkArgs &a, uint32_t g, u
   gen_biguint_divrem(w, shape);
 }
 
-template <bool DIVREM>
+// The four nonnative generators behind one call, for the same reason: NonNative's arrays (nonnative.hpp: BigDiv, the modulus, the
+// operands, the four numbers of the inversion) are this frame's.  field: the op record's, < NN_FIELDS as the plan checked it.
+static_assert(NN_LIMBS == PLAN_NONNATIVE_LIMBS && NN_MAX_OPERAND == PLAN_NONNATIVE_MAX && NN_FIELDS == PLAN_NONNATIVE_FIELDS, "the plan admits the shapes and fields the arithmetic holds");
+__device__ __noinline__ void run_nonnative(const WalkArgs &a, uint32_t code, uint32_t field, uint32_t g, uint32_t pos, uint32_t b) {
+  const uint32_t sw = a.gen_shape[g];
+  const uint32_t shape[4] = {sw & 0xFF, (sw >> 8) & 0xFF, (sw >> 16) & 0xFF, sw >> 24};
+  GenSlots w{a, a.gen_table + a.gen_off[g], pos, b};
+  switch (code) {
+  case OP_NONNATIVE_ADD: gen_nonnative_add(w, shape, field); break;
+  case OP_NONNATIVE_SUB: gen_nonnative_sub(w, shape, field); break;
+  case OP_NONNATIVE_MUL: gen_nonnative_mul(w, shape, field); break;
+  default: gen_nonnative_inv(w, shape, field); break;
+  }
+}
+
+template <bool BIGINT>
 __device__ __forceinline__ void run_op(const WalkArgs &a, uint32_t pos, uint32_t b) {
   const OpRec op = a.ops[pos];
   const uint32_t code = op.y & 0xFF, sub = op.y >> 8;
@@ -118,8 +133,9 @@ __device__ __forceinline__ void run_op(const WalkArgs &a, uint32_t pos, uint32_t
     gen_equality(w);
     return;
   }
-  if (DIVREM && code == OP_BIGUINT_DIVREM) {  // (a plan with such an op runs the DIVREM form: walk_and_scatter)
-    run_biguint_divrem(a, op.x, pos, b);
+  if (BIGINT && op_is_bigint_generator(code)) {  // (a plan with such an op runs the BIGINT form: walk_and_scatter)
+    if (code == OP_BIGUINT_DIVREM) run_biguint_divrem(a, op.x, pos, b);
+    else run_nonnative(a, code, sub, op.x, pos, b);
     return;
   }
   RowSlots w{a, op.x, pos, b};
@@ -146,7 +162,7 @@ __device__ __forceinline__ void run_op(const WalkArgs &a, uint32_t pos, uint32_t
 // witnesses' words only; the rest of the device stays free for the proofs in flight.  With 1 << sh the group's width rounded
 // up to a power of two, lane t takes witness t & mask of the group and the level's ops t >> sh, + 512 >> sh, ... (the lone
 // call: sh = 0, a lane per op).
-template <bool DIVREM>
+template <bool BIGINT>
 __global__ __launch_bounds__(WALK_TPB) void genwit_walk_kernel(WalkArgs a) {
   const uint32_t b0 = blockIdx.x * WALK_GROUP, gw = min(WALK_GROUP, a.B - b0);
   const uint32_t sh = gw > 1 ? 32 - __clz(gw - 1) : 0, lb = threadIdx.x & ((1u << sh) - 1);
@@ -154,7 +170,7 @@ __global__ __launch_bounds__(WALK_TPB) void genwit_walk_kernel(WalkArgs a) {
   for (uint32_t l = 0; l < a.levels; l++) {
     const uint32_t end = a.level_off[l + 1];
     if (lb < gw)
-      for (uint32_t pos = a.level_off[l] + first; pos < end; pos += step) run_op<DIVREM>(a, pos, b0 + lb);
+      for (uint32_t pos = a.level_off[l] + first; pos < end; pos += step) run_op<BIGINT>(a, pos, b0 + lb);
     __syncthreads();
   }
 }
@@ -201,7 +217,7 @@ int walk_and_scatter(p2gpu_witness_plan *p, uint32_t B, gl_t *wires) {
   {
     ProfScope ps("genwit_walk_kernel", 16.0 * (double)p->n_ops * B);
     const dim3 grid((B + WALK_GROUP - 1) / WALK_GROUP);
-    if (p->has_divrem) hipLaunchKernelGGL(genwit_walk_kernel<true>, grid, dim3(WALK_TPB), 0, st, a);
+    if (p->has_bigint) hipLaunchKernelGGL(genwit_walk_kernel<true>, grid, dim3(WALK_TPB), 0, st, a);
     else hipLaunchKernelGGL(genwit_walk_kernel<false>, grid, dim3(WALK_TPB), 0, st, a);
   }
   HIP_TRY(hipEventRecord(p->ev1, st));

@@ -35,7 +35,10 @@
 //                             cells follow each other in one flat list, and so do its table words: gen_off [generators + 1]
 //                             names where a generator's begin.  Equality is the shape {1, 1, 1, 1}; the div-rem generator of
 //                             `div_rem_biguint` has {la, lb, ld, lr}: the limbs of a and b (read), of div and rem (set); its
-//                             op record is list index | OP_BIGUINT_DIVREM << 32.  Every rule above holds per cell position: a
+//                             op record is list index | OP_BIGUINT_DIVREM << 32.  The four nonnative generators (add, sub, mul, inv
+//                             of `CircuitBuilderNonNative`) carry their field in bits 8-15 of the kind word and their shapes
+//                             are stated at PLAN_GEN_NONNATIVE_ADD below; their op record is list index | (code | field << 8)
+//                             << 32, the field where a row op keeps its operation index.  Every rule above holds per cell position: a
 //                             slot named by several input positions is that many entries of its `users` list and as many
 //                             counts of `pending`, hence one dependency; among the outputs the first position that names a
 //                             slot may take the writer bit, every later position of the same slot compares.  Further
@@ -68,10 +71,27 @@ struct PlanGenerator {
 // a generator with any number of cells: p2gpu.h's p2gpu_generator_v, word for word.  shape: the cell counts of its four groups
 constexpr uint32_t PLAN_GEN_BIGUINT_DIVREM = 1;  // cells: a's limbs, b's (read), div's, rem's (set): shape {la, lb, ld, lr}
 constexpr uint32_t PLAN_DIVREM_MAX_A = 32, PLAN_DIVREM_MAX_B = 16;  // bigdiv.hpp's arrays; 32 + 16 + 17 + 16 = 81 cells at most
+// the four nonnative generators (plonky2_ecdsa/biguint/gadgets/nonnative.rs): the record's kind word is kind | field << 8, the
+// field one of the two the reference instantiates (nonnative.hpp); a field element has PLAN_NONNATIVE_LIMBS limbs
+//   add / sub  {la, lb, 8, 1}: a, b (read), sum or diff, overflow (set); an operand may have no limbs (`neg_nonnative`
+//              subtracts from constant_biguint(0)), not both
+//   mul        {la, lb, 8, la + lb - 8}: a, b (read), prod, overflow (set); la + lb < 8 underflows upstream
+//   inv        {lx, 0, lx, lx}: x (read), inv, div (set)
+constexpr uint32_t PLAN_GEN_NONNATIVE_ADD = 2, PLAN_GEN_NONNATIVE_SUB = 3, PLAN_GEN_NONNATIVE_MUL = 4, PLAN_GEN_NONNATIVE_INV = 5;
+constexpr uint32_t PLAN_NONNATIVE_LIMBS = 8, PLAN_NONNATIVE_MAX = 16, PLAN_NONNATIVE_FIELDS = 2;
+static_assert(OP_BIGUINT_DIVREM == OP_EQUALITY + PLAN_GEN_BIGUINT_DIVREM && OP_NONNATIVE_ADD == OP_EQUALITY + PLAN_GEN_NONNATIVE_ADD &&
+                  OP_NONNATIVE_INV == OP_EQUALITY + PLAN_GEN_NONNATIVE_INV,
+              "PlanGenList::code: the listed kinds and their op codes run in one order");
 struct PlanGeneratorV {
   uint32_t kind;
   uint32_t shape[4];
 };
+// whether a record's kind word is a known one: the kind in bits 0-7, the field in bits 8-15 (the nonnative kinds only), nothing above
+inline bool plan_generator_kind_ok(uint32_t word) {
+  const uint32_t kind = word & 0xFF, field = (word >> 8) & 0xFF;
+  if (word >> 16 || kind > PLAN_GEN_NONNATIVE_INV) return false;
+  return kind >= PLAN_GEN_NONNATIVE_ADD ? field < PLAN_NONNATIVE_FIELDS : field == 0;
+}
 // the checked list of either ABI: generator g owns the cells [off[g], off[g + 1]) of the flat list
 struct PlanGenList {
   std::vector<PlanGeneratorV> gens;
@@ -81,7 +101,10 @@ struct PlanGenList {
   bool empty() const { return gens.empty(); }
   uint32_t n_cells() const { return off.back(); }
   uint32_t ins(size_t g) const { return gens[g].shape[0] + gens[g].shape[1]; }
-  uint32_t code(size_t g) const { return gens[g].kind == PLAN_GEN_EQUALITY ? OP_EQUALITY : OP_BIGUINT_DIVREM; }
+  // the op record's code and the field beside it: code | field << 8 is the word behind the list index
+  uint32_t code(size_t g) const { return OP_EQUALITY + (gens[g].kind & 0xFF); }
+  uint32_t field(size_t g) const { return gens[g].kind >> 8; }
+  uint32_t code_word(size_t g) const { return code(g) | field(g) << 8; }
   // la | lb << 8 | ld << 16 | lr << 24: what the walk reads of a generator beside its table words
   uint32_t shape_word(size_t g) const { const uint32_t *s = gens[g].shape; return s[0] | s[1] << 8 | s[2] << 16 | s[3] << 24; }
   bool four_cells_each() const { return (size_t)n_cells() == PLAN_GEN_CELLS * gens.size(); }
@@ -98,7 +121,7 @@ struct PlanInput {
 };
 
 // cell_slot [R][n]; ops by (level, creation order), one 64-bit word each: row | (code | sub << 8) << 32 (OP_SEED: the seed's
-// index for the row, OP_EQUALITY / OP_BIGUINT_DIVREM: the generator's); level_off [levels + 1]; gen_off [generators + 1] and
+// index for the row, OP_EQUALITY .. OP_NONNATIVE_INV: the generator's, sub the field); level_off [levels + 1]; gen_off [generators + 1] and
 // gen_table [gen_off[generators]], one word per cell a generator names: cell key (col << d | row) | PLAN_WRITER = this naming
 // writes the cell's slot (four words per generator when all are equality generators: [generators][4])
 struct HostPlan {
@@ -186,10 +209,14 @@ inline PlanRefusal plan_seeds(uint32_t d, uint32_t W, const uint32_t *seed_cells
   return PlanRefusal();
 }
 
-// whether `shape` is one of kind `kind` (a known one)
-inline bool plan_generator_shape_ok(uint32_t kind, const uint32_t shape[4]) {
-  const uint32_t la = shape[0], lb = shape[1], ld = shape[2], lr = shape[3];
+// whether `shape` is one of the kind of the kind word `word` (a known one)
+inline bool plan_generator_shape_ok(uint32_t word, const uint32_t shape[4]) {
+  const uint32_t kind = word & 0xFF, la = shape[0], lb = shape[1], ld = shape[2], lr = shape[3];
+  const uint32_t L = PLAN_NONNATIVE_LIMBS, MAX = PLAN_NONNATIVE_MAX;
   if (kind == PLAN_GEN_EQUALITY) return la == 1 && lb == 1 && ld == 1 && lr == 1;
+  if (kind == PLAN_GEN_NONNATIVE_ADD || kind == PLAN_GEN_NONNATIVE_SUB) return la <= MAX && lb <= MAX && la + lb >= 1 && ld == L && lr == 1;
+  if (kind == PLAN_GEN_NONNATIVE_MUL) return la <= MAX && lb <= MAX && la + lb >= L && ld == L && lr == la + lb - L;
+  if (kind == PLAN_GEN_NONNATIVE_INV) return la >= 1 && la <= MAX && lb == 0 && ld == la && lr == la;
   // div_rem_biguint (biguint.rs:236-244): rem has b's limbs, div a_len - b_len + 1, or none when b_len > a_len + 1
   return la >= 1 && la <= PLAN_DIVREM_MAX_A && lb >= 1 && lb <= PLAN_DIVREM_MAX_B && lr == lb && ld == (lb > la + 1 ? 0 : la - lb + 1);
 }
@@ -211,7 +238,7 @@ inline PlanRefusal plan_generators_v(uint32_t d, uint32_t R, const PlanGenerator
   size_t at = 0;
   for (size_t i = 0; i < n_gens; i++) {
     r.seed = i; r.seed2 = gens[i].kind;
-    if (gens[i].kind != PLAN_GEN_EQUALITY && gens[i].kind != PLAN_GEN_BIGUINT_DIVREM) {
+    if (!plan_generator_kind_ok(gens[i].kind)) {
       r.kind = PLAN_GEN_KIND;
       return r;
     }
@@ -419,7 +446,7 @@ struct Compiler {
     gen_off = gens.off.data();
     for (size_t i = 0; i < gens.size(); i++) {
       HostOp op;
-      op.code = gens.code(i); op.row = (uint32_t)i; op.sub = 0;
+      op.code = gens.code(i); op.row = (uint32_t)i; op.sub = gens.field(i);
       op.in0 = (uint32_t)cells.size();
       for (uint32_t e = gens.off[i]; e < gens.off[i + 1]; e++) {
         const uint32_t v = (uint32_t)key(gens.cells[2 * (size_t)e], gens.cells[2 * (size_t)e + 1]);

@@ -36,7 +36,7 @@ int plan_finish(p2gpu_witness_plan *p, const PlanArrays &a) {
   std::vector<uint32_t> shapes(n_gens);
   for (size_t g = 0; g < n_gens; g++) {
     shapes[g] = p->h_gens.shape_word(g);
-    p->has_divrem |= p->h_gens.gens[g].kind == PLAN_GEN_BIGUINT_DIVREM;
+    p->has_bigint |= op_is_bigint_generator(p->h_gens.code(g));
   }
   HIP_TRY(hipMemcpyAsync(p->gen_off.p, p->h_gens.off.data(), 4 * (n_gens + 1), hipMemcpyHostToDevice, c->stream));
   if (n_gens) HIP_TRY(hipMemcpyAsync(p->gen_shape.p, shapes.data(), 4 * n_gens, hipMemcpyHostToDevice, c->stream));
@@ -122,6 +122,9 @@ int plan_new(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, size_
              p2gpu_witness_plan **out, int (*compile)(p2gpu_witness_plan *)) {
   static_assert(sizeof(p2gpu_generator) == sizeof(PlanGenerator) && P2GPU_GEN_EQUALITY == PLAN_GEN_EQUALITY, "planhost.hpp restates the record");
   static_assert(sizeof(p2gpu_generator_v) == sizeof(PlanGeneratorV) && P2GPU_GEN_BIGUINT_DIVREM == PLAN_GEN_BIGUINT_DIVREM, "planhost.hpp restates the record");
+  static_assert(P2GPU_GEN_NONNATIVE_ADD == PLAN_GEN_NONNATIVE_ADD && P2GPU_GEN_NONNATIVE_SUB == PLAN_GEN_NONNATIVE_SUB && P2GPU_GEN_NONNATIVE_MUL == PLAN_GEN_NONNATIVE_MUL &&
+                    P2GPU_GEN_NONNATIVE_INV == PLAN_GEN_NONNATIVE_INV && P2GPU_FIELD_SECP256K1_BASE == 0 && P2GPU_FIELD_SECP256K1_SCALAR == 1,
+                "planhost.hpp restates the kinds");
   if (out) *out = nullptr;
   if (!c || !out || (n_seeds && !seed_cells) || n_generators >= ((size_t)1 << 32) || n_generator_cells >= ((size_t)1 << 32)) return P2GPU_E_ARG;
   if (int rc = prover_handle(c)) return rc;

@@ -18,7 +18,7 @@ struct p2gpu_witness_plan {
   p2::PlanGenList h_gens;
   std::vector<uint32_t> h_gen_table;
   p2::DBuf<uint32_t> gen_table, gen_off, gen_shape;
-  bool has_divrem = false;  // a div-rem generator is listed: the walk kernel's form with that arm runs this plan
+  bool has_bigint = false;  // a big-integer generator (div-rem, nonnative) is listed: the walk kernel's form with those arms runs this plan
   // One bit per routed cell, set for a seed's cell that is also an output column of a row op of its row: the cell's writer bit is
   // the seed's there, and the row op compares (planhost.hpp, "writer bits").  Not allocated when the plan has no such cell.
   p2::DBuf<uint32_t> seed_out;

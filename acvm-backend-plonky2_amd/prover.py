@@ -442,9 +442,11 @@ class CircuitData:
         ``compile="device"``: the same plan through ``p2gpu_witness_plan_build``, compiled on the GPU.
         ``generators``: the generators that are no gate's own, [("equality", (cell_x, cell_y, cell_equal, cell_inv))] with
         (row, col) cells, and ("biguint_divrem", (a_cells, b_cells, div_cells, rem_cells)) with the limbs' cells, least
-        significant first (``translate.CircuitBuilder.generators()``); the plan then comes from
+        significant first, and ("nonnative_add" | "nonnative_sub" | "nonnative_mul" | "nonnative_inv", (a_cells, b_cells, first
+        target's cells, second target's cells), "secp256k1_base" | "secp256k1_scalar") for the four nonnative generators
+        (``translate.CircuitBuilder.generators()``); the plan then comes from
         ``p2gpu_witness_plan_create_gen`` / ``_build_gen``, or from ``_create_genv`` / ``_build_genv`` when a generator has
-        another number of cells than four."""
+        another number of cells than four or names a field."""
         return WitnessPlan(self, seed_cells, compile=compile, generators=generators)
 
     def prove_routed(self, routed, public_inputs=()):
@@ -524,6 +526,25 @@ class WitnessPlan:
     the circuit."""
 
     GENERATOR_KINDS = {"equality": 0, "biguint_divrem": 1}   # p2gpu.h P2GPU_GEN_EQUALITY, P2GPU_GEN_BIGUINT_DIVREM
+    # the nonnative generators, given as (kind, groups, field): p2gpu.h P2GPU_GEN_NONNATIVE_*, P2GPU_FIELD_*; the record's kind
+    # word is kind | field << 8
+    NONNATIVE_KINDS = {"nonnative_add": 2, "nonnative_sub": 3, "nonnative_mul": 4, "nonnative_inv": 5}
+    NONNATIVE_FIELDS = {"secp256k1_base": 0, "secp256k1_scalar": 1}
+
+    @classmethod
+    def _kind_word(cls, gen):
+        """The kind word of a generator (kind, cells) or (kind, cells, field); a kind or a field may be given by its number."""
+        kind = gen[0]
+        if isinstance(kind, str):
+            kind = cls.GENERATOR_KINDS[kind] if kind in cls.GENERATOR_KINDS else cls.NONNATIVE_KINDS.get(kind, kind)
+        if len(gen) > 2:
+            field = cls.NONNATIVE_FIELDS.get(gen[2], gen[2]) if isinstance(gen[2], str) else gen[2]
+            if isinstance(kind, str) or isinstance(field, str):
+                raise P2GpuError(-7, f"unknown generator kind or field in {gen[0]!r}, {gen[2]!r}")
+            return int(kind) | int(field) << 8
+        if isinstance(kind, str):
+            raise P2GpuError(-7, f"unknown generator kind {kind!r}")
+        return kind
 
     def __init__(self, circuit, seed_cells, compile="host", generators=None):
         if compile not in ("host", "device"):
@@ -540,13 +561,13 @@ class WitnessPlan:
             _check(make(circuit._h, cells.ctypes.data if cells.size else None, len(cells), ctypes.byref(self._h)))
             return
         generators = list(generators)
-        if any(self._groups(gcells) is not None for _, gcells in generators):
+        if any(len(g) > 2 or self._groups(g[1]) is not None for g in generators):
             self._init_genv(circuit, cells, compile, generators)
             return
         # p2gpu_generator records: kind, then four (row, col) pairs; a kind may be given by its number
         recs = np.zeros((len(generators), 9), dtype=np.int64)
         for i, (kind, gcells) in enumerate(generators):
-            recs[i, 0] = self.GENERATOR_KINDS.get(kind, kind) if isinstance(kind, str) else kind
+            recs[i, 0] = self._kind_word((kind, gcells))
             recs[i, 1:] = np.array(list(gcells), dtype=np.int64).reshape(8)
         if recs.size and (recs.min() < 0 or recs.max() >= 1 << 32):
             raise P2GpuError(-7, "a generator is a kind and four (row, col) cells of unsigned 32-bit numbers")
@@ -567,11 +588,12 @@ class WitnessPlan:
         """p2gpu_generator_v records (kind, shape[4]) and the flat (row, col) list of their cells: the entry points for
         generators with any number of cells."""
         recs, flat = np.zeros((len(generators), 5), dtype=np.int64), []
-        for i, (kind, gcells) in enumerate(generators):
+        for i, gen in enumerate(generators):
+            gcells = gen[1]
             groups = self._groups(gcells) or [[tuple(cell)] for cell in gcells]
             if len(groups) != 4:
                 raise P2GpuError(-7, "a generator is a kind and four groups of (row, col) cells")
-            recs[i, 0] = self.GENERATOR_KINDS.get(kind, kind) if isinstance(kind, str) else kind
+            recs[i, 0] = self._kind_word(gen)
             recs[i, 1:] = [len(g) for g in groups]
             flat += [cell for g in groups for cell in g]
         flat = np.array(flat, dtype=np.int64).reshape(-1, 2)

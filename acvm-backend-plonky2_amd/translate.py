@@ -24,6 +24,9 @@ Mirrors, with the reference's names:
     multiple_comparison.rs, range_check_u32.rs, biguint/biguint.rs) over its five gates (biguint/gates/*.rs: shapes, wire
     positions, degrees and ids are read off that source, so they are pinned), with the BigUintDivRemGenerator of
     `div_rem_biguint` as the event "divrem".  Only `find_slot`, plonky2's row sharing, is UNPINNED (see `_u32_slot`).
+  * the nonnative gadgets above them (plonky2_ecdsa/biguint/gadgets/nonnative.rs:131-443, `CircuitBuilderNonNative`), the field
+    an argument (a name of NONNATIVE_FIELDS), with their four generators as the events "nnadd", "nnsub", "nnmul", "nninv".
+    `add_many_nonnative` is left out (nothing on the ECDSA path calls it).
 
 What it is NOT: an ACIR *reader*.  The reference deserialises gzip + bincode `Program` bytes through the acvm
 crate (noir_and_plonky2_serialization.rs:42-64); no compiled program exists in the tree to test a reader on, so
@@ -45,6 +48,11 @@ G_NOOP, G_CONSTANT, G_PUBLIC_INPUT, G_ARITHMETIC, G_BASE_SUM, G_RANDOM_ACCESS, G
 NUM_CONSTANTS = 2            # CircuitConfig::num_constants of both configurations
 GEN_EQUALITY = 0             # p2gpu.h P2GPU_GEN_EQUALITY
 GEN_BIGUINT_DIVREM = 1       # p2gpu.h P2GPU_GEN_BIGUINT_DIVREM
+GEN_NONNATIVE_ADD, GEN_NONNATIVE_SUB, GEN_NONNATIVE_MUL, GEN_NONNATIVE_INV = 2, 3, 4, 5   # p2gpu.h P2GPU_GEN_NONNATIVE_*
+# the two `FF` the reference instantiates (plonky2_ecdsa/curve/secp256k1.rs, glv.rs): name -> (p2gpu.h P2GPU_FIELD_*, order)
+NONNATIVE_FIELDS = {"secp256k1_base": (0, 2**256 - 2**32 - 977),
+                    "secp256k1_scalar": (1, 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141)}
+NONNATIVE_EVENTS = {"nnadd": "nonnative_add", "nnsub": "nonnative_sub", "nnmul": "nonnative_mul", "nninv": "nonnative_inv"}
 G_U32_ARITHMETIC, G_U32_ADD_MANY, G_U32_SUBTRACTION, G_U32_RANGE_CHECK, G_COMPARISON = 7, 8, 9, 10, 11   # p2gpu.h gate kinds
 MAX_NUM_ADDENDS = 16         # gates/add_many_u32.rs:24
 U32_MAX = 0xFFFFFFFF
@@ -189,6 +197,10 @@ class CircuitBuilder:
         b = self.add_virtual_target()
         self.assert_bool(b)
         return b
+
+    def add_virtual_bool_target_unsafe(self):
+        """circuit_builder.rs add_virtual_bool_target_unsafe: nothing constrains it to a bit"""
+        return self.add_virtual_target()
 
     def and_(self, a, b):
         return self.mul(a, b)
@@ -552,6 +564,188 @@ class CircuitBuilder:
             raise ValueError("unsatisfiable: div_rem_biguint: the quotient or the remainder has more digits than its target has limbs")
         return ([(q >> (32 * i)) & U32_MAX for i in range(div_limbs)], [(r >> (32 * i)) & U32_MAX for i in range(rem_limbs)])
 
+    # -- plonky2_ecdsa/biguint/gadgets/nonnative.rs: a NonNativeTarget<FF> is the list of its limbs, as a BigUintTarget is; FF is
+    # the `field` argument, a name of NONNATIVE_FIELDS ---------------------------------------------------------------------
+    @staticmethod
+    def nonnative_order(field):
+        """FF::order()"""
+        return NONNATIVE_FIELDS[field][1]
+
+    @staticmethod
+    def num_nonnative_limbs(field):
+        """nonnative.rs:127-129: ceil_div_usize(FF::BITS, 32)"""
+        return -(-NONNATIVE_FIELDS[field][1].bit_length() // 32)
+
+    def biguint_to_nonnative(self, x, field):
+        """nonnative.rs:131-136"""
+        return list(x)
+
+    def nonnative_to_canonical_biguint(self, x, field):
+        """nonnative.rs:138-143"""
+        return list(x)
+
+    def constant_nonnative(self, x, field):
+        """nonnative.rs:145-148: `x` an element of the field, as a Python integer"""
+        assert 0 <= x < self.nonnative_order(field)
+        return self.biguint_to_nonnative(self.constant_biguint(x), field)
+
+    def zero_nonnative(self, field):
+        """nonnative.rs:150-152"""
+        return self.constant_nonnative(0, field)
+
+    def connect_nonnative(self, lhs, rhs, field):
+        """nonnative.rs:155-161: both assumed to be in reduced form"""
+        self.connect_biguint(lhs, rhs)
+
+    def add_virtual_nonnative_target(self, field):
+        """nonnative.rs:163-171"""
+        return self.add_virtual_biguint_target(self.num_nonnative_limbs(field))
+
+    def add_virtual_nonnative_target_sized(self, num_limbs, field):
+        """nonnative.rs:173-183"""
+        return self.add_virtual_biguint_target(num_limbs)
+
+    def add_nonnative(self, a, b, field):
+        """nonnative.rs:185-215: (sum, overflow) from the NonNativeAdditionGenerator (event "nnadd": no gate's own), then
+        a + b == sum + overflow * modulus and sum <= modulus (`cmp_biguint` is <=: sum = modulus passes, as upstream)."""
+        a, b = list(a), list(b)
+        total = self.add_virtual_nonnative_target(field)
+        overflow = self.add_virtual_bool_target_unsafe()
+        self.events.append(("nnadd", tuple(a), tuple(b), tuple(total), (overflow,), field))
+        sum_expected = self.add_biguint(a, b)
+        modulus = self.constant_biguint(self.nonnative_order(field))
+        mod_times_overflow = self.mul_biguint_by_bool(modulus, overflow)
+        sum_actual = self.add_biguint(total, mod_times_overflow)
+        self.connect_biguint(sum_expected, sum_actual)
+        self.connect(self.cmp_biguint(total, modulus), self.one())
+        return total
+
+    def mul_nonnative_by_bool(self, a, b, field):
+        """nonnative.rs:217-226"""
+        return self.mul_biguint_by_bool(a, b)
+
+    def if_nonnative(self, b, x, y, field):
+        """nonnative.rs:228-238"""
+        not_b = self.not_(b)
+        maybe_x = self.mul_nonnative_by_bool(x, b, field)
+        maybe_y = self.mul_nonnative_by_bool(y, not_b, field)
+        return self.add_nonnative(maybe_x, maybe_y, field)
+
+    def sub_nonnative(self, a, b, field):
+        """nonnative.rs:284-310: (diff, overflow) from the NonNativeSubtractionGenerator (event "nnsub"), diff's limbs range-checked
+        in one U32RangeCheckGate row, overflow a bit, then a == diff + b - overflow * modulus."""
+        a, b = list(a), list(b)
+        diff = self.add_virtual_nonnative_target(field)
+        overflow = self.add_virtual_bool_target_unsafe()
+        self.events.append(("nnsub", tuple(a), tuple(b), tuple(diff), (overflow,), field))
+        self.range_check_u32(diff)
+        self.assert_bool(overflow)
+        diff_plus_b = self.add_biguint(diff, b)
+        modulus = self.constant_biguint(self.nonnative_order(field))
+        mod_times_overflow = self.mul_biguint_by_bool(modulus, overflow)
+        diff_plus_b_reduced = self.sub_biguint(diff_plus_b, mod_times_overflow)
+        self.connect_biguint(a, diff_plus_b_reduced)
+        return diff
+
+    def mul_nonnative(self, a, b, field):
+        """nonnative.rs:312-341: (prod, overflow) from the NonNativeMultiplicationGenerator (event "nnmul"), both range-checked,
+        then a * b == prod + modulus * overflow.  overflow has len(a) + len(b) - 8 limbs (fewer than 8 operand limbs in all
+        underflow upstream: ValueError).  A range check over no limbs (len(a) + len(b) == 8) places no row here: upstream's
+        U32RangeCheckGate { num_input_limbs: 0 } constrains nothing and the gate table takes 1 limb at least."""
+        a, b = list(a), list(b)
+        prod = self.add_virtual_nonnative_target(field)
+        modulus = self.constant_biguint(self.nonnative_order(field))
+        if len(a) + len(b) < len(modulus):
+            raise ValueError("mul_nonnative: %d + %d operand limbs are fewer than the modulus has" % (len(a), len(b)))
+        overflow = self.add_virtual_biguint_target(len(a) + len(b) - len(modulus))
+        self.events.append(("nnmul", tuple(a), tuple(b), tuple(prod), tuple(overflow), field))
+        self.range_check_u32(prod)
+        if overflow:
+            self.range_check_u32(overflow)
+        prod_expected = self.mul_biguint(a, b)
+        mod_times_overflow = self.mul_biguint(modulus, overflow)
+        prod_actual = self.add_biguint(prod, mod_times_overflow)
+        self.connect_biguint(prod_expected, prod_actual)
+        return prod
+
+    def mul_many_nonnative(self, to_mul, field):
+        """nonnative.rs:343-356"""
+        to_mul = list(to_mul)
+        if len(to_mul) == 1:
+            return to_mul[0]
+        acc = self.mul_nonnative(to_mul[0], to_mul[1], field)
+        for t in to_mul[2:]:
+            acc = self.mul_nonnative(acc, t, field)
+        return acc
+
+    def neg_nonnative(self, x, field):
+        """nonnative.rs:358-363: zero minus x, the zero a target without limbs"""
+        zero_ff = self.biguint_to_nonnative(self.constant_biguint(0), field)
+        return self.sub_nonnative(zero_ff, x, field)
+
+    def inv_nonnative(self, x, field):
+        """nonnative.rs:365-389: (inv, div) from the NonNativeInverseGenerator (event "nninv"), both with x's limbs, then
+        x * inv == modulus * div + 1."""
+        x = list(x)
+        inv = self.add_virtual_biguint_target(len(x))
+        div = self.add_virtual_biguint_target(len(x))
+        self.events.append(("nninv", tuple(x), (), tuple(inv), tuple(div), field))
+        product = self.mul_biguint(x, inv)
+        modulus = self.constant_biguint(self.nonnative_order(field))
+        mod_times_div = self.mul_biguint(modulus, div)
+        expected_product = self.add_biguint(mod_times_div, self.constant_biguint(1))
+        self.connect_biguint(product, expected_product)
+        return inv
+
+    def reduce(self, x, field):
+        """nonnative.rs:391-401: x % |FF| through `rem_biguint`"""
+        return self.rem_biguint(x, self.constant_biguint(self.nonnative_order(field)))
+
+    def reduce_nonnative(self, x, field):
+        """nonnative.rs:403-406"""
+        return self.reduce(self.nonnative_to_canonical_biguint(x, field), field)
+
+    def bool_to_nonnative(self, b, field):
+        """nonnative.rs:408-416: one limb"""
+        return [b]
+
+    def split_nonnative_to_bits(self, x, field):
+        """nonnative.rs:418-430: 32 bits per limb, least significant first"""
+        return [bit for limb in x for bit in self.split_le(limb, 32)]
+
+    def nonnative_conditional_neg(self, x, b, field):
+        """nonnative.rs:432-443"""
+        not_b = self.not_(b)
+        neg = self.neg_nonnative(x, field)
+        x_if_true = self.mul_nonnative_by_bool(neg, b, field)
+        x_if_false = self.mul_nonnative_by_bool(x, not_b, field)
+        return self.add_nonnative(x_if_true, x_if_false, field)
+
+    @staticmethod
+    def nonnative_values(event, field, a_limbs, b_limbs, first_limbs, second_limbs):
+        """The four generators' run_once (nonnative.rs:469-484, :589-604, :645-658, :691-703) on limb values: A and B are the
+        operands' integers sum limb_i 2^(32 i) (`get_biguint_target`) reduced modulo the order (FF::from_noncanonical_biguint).
+        Returns the two targets' 32-bit digits.  ValueError where upstream panics: the inverse of zero, or more digits than limbs
+        (`set_biguint_target`)."""
+        m = NONNATIVE_FIELDS[field][1]
+        a = sum(v << (32 * i) for i, v in enumerate(a_limbs)) % m
+        b = sum(v << (32 * i) for i, v in enumerate(b_limbs)) % m
+        if event == "nnadd":
+            s = a + b
+            first, second = (s - m, 1) if s > m else (s, 0)          # (strictly: a + b == m leaves sum = m)
+        elif event == "nnsub":
+            first, second = (a - b, 0) if a >= b else (m + a - b, 1)
+        elif event == "nnmul":
+            second, first = divmod(a * b, m)
+        else:
+            if a == 0:
+                raise ValueError("unsatisfiable: inv_nonnative inverts zero")
+            first = pow(a, -1, m)
+            second = a * first // m
+        if first >> (32 * first_limbs) or second >> (32 * second_limbs):
+            raise ValueError("unsatisfiable: a nonnative generator's value has more digits than its target has limbs")
+        return ([(first >> (32 * i)) & U32_MAX for i in range(first_limbs)], [(second >> (32 * i)) & U32_MAX for i in range(second_limbs)])
+
     # -- build(): rows -> blob (library) + witness ----------------------------------------------------
     def _layout(self):
         """The circuit half of build(): rows -> blob, and the cells of every copy class.  Runs once; build(), seed_cells() and
@@ -802,6 +996,15 @@ class CircuitBuilder:
                         q, r = self.divrem_values(vs[:len(a)], vs[len(a):], len(div), len(rem))
                         for t, v in zip(div + rem, q + r):
                             self._set(val, t, v)
+                elif ev[0] in NONNATIVE_EVENTS:
+                    _, a, b, first, second, field = ev
+                    vs = [val.get(self.find(t)) for t in a + b]
+                    if any(v is None for v in vs):
+                        rest.append(ev)
+                        continue
+                    x, y = self.nonnative_values(ev[0], field, vs[:len(a)], vs[len(a):], len(first), len(second))
+                    for t, v in zip(first + second, x + y):
+                        self._set(val, t, v)
                 elif ev[0] == "split":
                     v = val.get(self.find(ev[1]))
                     if v is None:
@@ -926,7 +1129,7 @@ class CircuitBuilder:
         # column as its only cell, and the row op then shares the cell's writer bit with the seed -- DESIGN.md 11.6.)
         given = set()
         for ev in self.events:
-            if ev[0] == "divrem":
+            if ev[0] == "divrem" or ev[0] in NONNATIVE_EVENTS:     # (the nonnative gadgets connect their operands the same way)
                 given.update(self.find(t) for t in ev[1] + ev[2] if self.find(t) not in derived)
             if ev[0] == "arith":
                 derived.add(self.find(ev[6]))
@@ -942,7 +1145,7 @@ class CircuitBuilder:
                 derived.update((self.find(ev[3]), self.find(ev[4])))
             elif ev[0] == "cmp":
                 derived.add(self.find(ev[3]))
-            elif ev[0] == "divrem":
+            elif ev[0] == "divrem" or ev[0] in NONNATIVE_EVENTS:
                 derived.update(self.find(t) for t in ev[3] + ev[4])
             elif ev[0] == "u32range":
                 pass
@@ -979,8 +1182,9 @@ class CircuitBuilder:
 
     def generators(self):
         """The generators that are no gate's own, for CircuitData.witness_plan(..., generators=): ("equality", (cell_x, cell_y,
-        cell_equal, cell_inv)) and ("biguint_divrem", (a_cells, b_cells, div_cells, rem_cells)) in creation order; a target's
-        cell -- a limb's too -- is the first cell of its copy class."""
+        cell_equal, cell_inv)), ("biguint_divrem", (a_cells, b_cells, div_cells, rem_cells)) and, for the four nonnative
+        generators, ("nonnative_add" | "_sub" | "_mul" | "_inv", (a_cells, b_cells, first target's cells, second target's cells),
+        field name) in creation order; a target's cell -- a limb's too -- is the first cell of its copy class."""
         _, _, _, _, cells, _ = self._layout()
         out = []
         for ev in self.events:
@@ -994,6 +1198,11 @@ class CircuitBuilder:
                 if any(c is None for grp in groups for c in grp):
                     raise ValueError("div_rem_biguint: a limb of the div-rem generator lies in no gate row")
                 out.append(("biguint_divrem", tuple(tuple(c[0] for c in grp) for grp in groups)))
+            elif ev[0] in NONNATIVE_EVENTS:
+                groups = [[cells.get(self.find(t)) for t in grp] for grp in ev[1:5]]
+                if any(c is None for grp in groups for c in grp):
+                    raise ValueError("%s: a limb of the generator lies in no gate row" % NONNATIVE_EVENTS[ev[0]])
+                out.append((NONNATIVE_EVENTS[ev[0]], tuple(tuple(c[0] for c in grp) for grp in groups), ev[5]))
         return out
 
     def _set(self, val, t, v):

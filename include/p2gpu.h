@@ -233,6 +233,33 @@ int p2gpu_witness_plan_export_generators(const p2gpu_witness_plan *p, uint32_t *
  * outside [n] x [num_routed_wires] (with the generator's index and the cell), a counted list behind a null pointer. */
 #define P2GPU_GEN_BIGUINT_DIVREM 1
 typedef struct { uint32_t kind; uint32_t shape[4]; } p2gpu_generator_v;
+/* ---- the nonnative generators ----
+ * The four generators that `add_nonnative`, `sub_nonnative`, `mul_nonnative` and `inv_nonnative` register (plonky2_ecdsa/biguint/
+ * gadgets/nonnative.rs:185-215, :284-310, :312-341, :365-389; generators :446-715; the Rust side lists them at those call sites,
+ * INTEGRATION.md).  The record's kind word carries the field in bits 8-15: kind | field << 8, the field one of the two `FF` the
+ * reference instantiates.  M is the field's modulus, A = fold(a) mod M and B = fold(b) mod M with fold as the div-rem generator
+ * folds limbs (upstream's FF::from_noncanonical_biguint); a field element has L = 8 limbs; what is set are 32-bit digits, least
+ * significant first, zeros in the limbs beyond them.
+ *   P2GPU_GEN_NONNATIVE_ADD  {la, lb, L, 1}: a, b (read), sum, overflow (set).  S = A + B; S > M (strictly): sum = S - M,
+ *                            overflow = 1; otherwise sum = S, overflow = 0 -- A + B = M leaves sum = M, as upstream.
+ *   P2GPU_GEN_NONNATIVE_SUB  {la, lb, L, 1}: a, b (read), diff, overflow (set).  A >= B: diff = A - B, overflow = 0; otherwise
+ *                            diff = M + A - B, overflow = 1.  For both: 0 <= la, lb <= 16, la + lb >= 1 (`neg_nonnative` subtracts
+ *                            from a target without limbs).
+ *   P2GPU_GEN_NONNATIVE_MUL  {la, lb, L, la + lb - L}: a, b (read), prod, overflow (set).  (overflow, prod) = divmod(A B, M);
+ *                            0 <= la, lb <= 16, la + lb >= L.
+ *   P2GPU_GEN_NONNATIVE_INV  {lx, 0, lx, lx}: x (read), inv, div (set).  X = fold(x) mod M, inv = 1 / X mod M, div = (X inv) div M;
+ *                            1 <= lx <= 16.
+ * Where upstream panics, p2gpu_generate_witness answers P2GPU_E_UNSATISFIED with the generator and a cell: X = 0 -> x's first
+ * cell; a value with more digits than its target has limbs -> that target's top limb (a target without limbs: the generator's
+ * first cell).  The op record is list index | (code | field << 8) << 32, codes 15 .. 18 in the order above.  An unknown kind, as
+ * above and with the whole word in the message: a field other than these two, a field on kinds 0 and 1, a bit above 15, a kind
+ * above 5. */
+#define P2GPU_GEN_NONNATIVE_ADD 2
+#define P2GPU_GEN_NONNATIVE_SUB 3
+#define P2GPU_GEN_NONNATIVE_MUL 4
+#define P2GPU_GEN_NONNATIVE_INV 5
+#define P2GPU_FIELD_SECP256K1_BASE 0   /* 2^256 - 2^32 - 977 */
+#define P2GPU_FIELD_SECP256K1_SCALAR 1 /* 0xFFFFFFFF FFFFFFFF FFFFFFFF FFFFFFFE BAAEDCE6 AF48A03B BFD25E8C D0364141 */
 int p2gpu_witness_plan_create_genv(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, const p2gpu_generator_v *generators,
                                    size_t n_generators, const uint32_t *cells /* [n_cells][2] = (row, col) */, size_t n_cells,
                                    p2gpu_witness_plan **out);
