@@ -107,9 +107,10 @@ def virtual(pkg, kind, field=BASE, la=L, lb=L):
     else:
         ta, tb = _inputs(b, la), _inputs(b, lb)
         getattr(b, kind + "_nonnative")(ta, tb, field)
-    ev = [e for e in b.events if e[0] in pkg.translate.NONNATIVE_EVENTS]
-    assert len(ev) == 1 and list(ev[0][1]) == ta and list(ev[0][2]) == tb
-    return b, ta, tb, list(ev[0][3]), list(ev[0][4])
+    (ev,) = [e for e in b.events if e.kind in pkg.translate.NONNATIVE_EVENTS]
+    a, b_, first, second = ev.groups
+    assert list(a) == ta and list(b_) == tb
+    return b, ta, tb, list(first), list(second)
 
 
 def operands(c, x, y=0):

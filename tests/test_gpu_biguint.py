@@ -121,7 +121,7 @@ def test_prove_bytes_and_device_witness(pkg, orc, gpu, cases, name):
 
 def _virtual(pkg, la=4, lb=4):
     c = bi.div_rem_virtual(pkg, la, lb)
-    return c, c[0]._layout()[0]
+    return c, c[0].blob()
 
 
 @pytest.mark.gpu

@@ -114,7 +114,7 @@ def test_less_or_equal_check(pkg, orc, gpu, bound):
     """test_memory_operations.rs:123-179 cut to the bounds 0 .. 8: every value <= bound proves to the oracle's bytes; every
     value above it, up to 8, is a contradiction the device walk names."""
     b, t = moi.less_or_equal_circuit(pkg, bound)
-    blob = b._layout()[0]
+    blob = b.blob()
     cd, oc = pkg.CircuitData(blob), orc.OracleCircuit(blob)
     plan = None
     for value in range(9):
@@ -144,7 +144,7 @@ EDGES = [(0, 0), (P - 1, P - 1), (0, P - 1), (P - 1, 0), (1, 0), (1 << 32, (1 <<
 def test_edge_operands_of_the_equality_body(pkg, gpu, compile):
     """(x, y) as seeds of the `is_equal` circuit: the matrix is the host event loop's (equal = (x == y), inv = 0 or 1 / (x - y))."""
     b0 = moi.is_equal_circuit(pkg)[0]
-    cd = pkg.CircuitData(b0._layout()[0])
+    cd = pkg.CircuitData(b0.blob())
     plan = cd.witness_plan(b0.seed_cells(), compile=compile, generators=b0.generators())
     for x, y in EDGES:
         b, blob, wires, _ = _is_equal_case(pkg, x, y)
@@ -199,7 +199,7 @@ def test_batch_of_the_write_circuit(pkg, gpu, compile):
     assert blob[:256].view(np.uint32)[2] <= 6
 
     def cell_of(w):
-        return cb0.builder._layout()[4][cb0.builder.find(cb0.witness_target_map[w])][0]
+        return cb0.builder.cells_of(cb0.witness_target_map[w])[0]
 
     cd = pkg.CircuitData(blob)
     plan = cd.witness_plan(cells, compile=compile, generators=cb0.witness_generators())

@@ -126,7 +126,7 @@ def test_edge_operands_on_the_device(pkg, gpu, compile):
     for (kind, la, lb), members in _shapes().items():
         for field in ni.FIELDS:
             c0 = ni.virtual(pkg, kind, field, la, lb)
-            blob = c0[0]._layout()[0]
+            blob = c0[0].blob()
             (_, groups, _), = c0[0].generators()
             cd = pkg.CircuitData(blob)
             assert cd.degree <= 1 << 7
@@ -164,7 +164,7 @@ def test_contradictions_are_named(pkg, gpu, compile):
     wrong one is named at that cell, and the table shows that the seed holds the writer bit."""
     c = ni.virtual(pkg, "inv", ni.SCALAR)
     (_, (cx, _, cinv, cdiv), _), = c[0].generators()
-    cd = pkg.CircuitData(c[0]._layout()[0])
+    cd = pkg.CircuitData(c[0].blob())
     plan = cd.witness_plan(c[0].seed_cells(), compile=compile, generators=c[0].generators())
     assert _refused(pkg, plan, c[0].seed_values(ni.operands(c, 0)), 0) == tuple(cx[0])
     c2 = ni.virtual(pkg, "inv", ni.SCALAR)
@@ -174,7 +174,7 @@ def test_contradictions_are_named(pkg, gpu, compile):
 
     c = ni.chain(pkg, ni.BASE)
     gens = c[0].generators()
-    cd = pkg.CircuitData(c[0]._layout()[0])
+    cd = pkg.CircuitData(c[0].blob())
     plan = cd.witness_plan(c[0].seed_cells(), compile=compile, generators=gens)
     assert gens[2][0] == "nonnative_inv"
     assert _refused(pkg, plan, c[0].seed_values(ni.chain_operands(c, ni.X256, ni.Y256, ni.X256, ni.V256)), 2) == tuple(gens[2][1][0][0])
@@ -184,7 +184,7 @@ def test_contradictions_are_named(pkg, gpu, compile):
     c = ni.virtual(pkg, "inv", ni.BASE, la=4)
     (_, (cx, _, cinv, cdiv), _), = c[0].generators()
     assert len(cinv) == 4 and pow(3, -1, ni.ORDER[ni.BASE]) >> 128
-    cd = pkg.CircuitData(c[0]._layout()[0])
+    cd = pkg.CircuitData(c[0].blob())
     plan = cd.witness_plan(c[0].seed_cells(), compile=compile, generators=c[0].generators())
     assert _refused(pkg, plan, c[0].seed_values(ni.operands(c, 3)), 0) == tuple(cinv[-1])
     plan.close()
@@ -193,7 +193,7 @@ def test_contradictions_are_named(pkg, gpu, compile):
     c = ni.virtual(pkg, "mul", ni.BASE)
     gens = c[0].generators()
     (_, (ca, cb, cprod, cover), _), = gens
-    cd = pkg.CircuitData(c[0]._layout()[0])
+    cd = pkg.CircuitData(c[0].blob())
     c2 = ni.virtual(pkg, "mul", ni.BASE)
     _, wires = c2[0].build(ni.operands(c2, ni.X256, ni.Y256))
     cells, values = _seeds(c2[0], wires, extra=[cprod[1]])
@@ -215,7 +215,7 @@ def test_an_operand_of_the_order_or_above_is_unsatisfiable(pkg, gpu):
     named = []
     for compile in ("host", "device"):
         c = ni.virtual(pkg, "add", ni.BASE)
-        cd = pkg.CircuitData(c[0]._layout()[0])
+        cd = pkg.CircuitData(c[0].blob())
         plan = cd.witness_plan(c[0].seed_cells(), compile=compile, generators=c[0].generators())
         values = c[0].seed_values(ni.operands(c, ni.ORDER[ni.BASE] + 5, ni.Y256))
         with pytest.raises(pkg.P2GpuError) as e:
@@ -240,7 +240,7 @@ def test_refused_lists_from_both_compilers(pkg, gpu):
     c = ni.virtual(pkg, "mul", ni.BASE)
     b = c[0]
     (_, groups, _), = b.generators()
-    cd = pkg.CircuitData(b._layout()[0])
+    cd = pkg.CircuitData(b.blob())
     n, R = cd.degree, cd.num_routed_wires
     outside = (groups[0], groups[1], groups[2][:2] + ((groups[2][2][0], R),) + groups[2][3:], groups[3])
     lists = [
@@ -289,7 +289,7 @@ def test_batch_of_the_chain(pkg, gpu, compile):
     assert B == 9
     c0 = ni.chain(pkg, ni.BASE)
     cells, gens = c0[0].seed_cells(), c0[0].generators()
-    cd = pkg.CircuitData(c0[0]._layout()[0])
+    cd = pkg.CircuitData(c0[0].blob())
     plan = cd.witness_plan(cells, compile=compile, generators=gens)
     m = ni.ORDER[ni.BASE]
     values, want = [], []

@@ -239,7 +239,7 @@ def test_sha256_compression_batch(pkg, gpu):
     bad = list(values)
     bad[3] = 1 << 32
     batch = [values, inputs[0] + values[24:], inputs[1] + values[24:], bad]
-    out_cells = [cb.builder._layout()[4][cb.builder.find(cb.witness_target_map[24 + i])][0] for i in range(8)]
+    out_cells = [cb.builder.cells_of(cb.witness_target_map[24 + i])[0] for i in range(8)]
     cd = pkg.CircuitData(blob)
     routed = int(blob[:256].view(np.uint32)[4])
 

@@ -114,7 +114,7 @@ def test_range_and_xor_opcodes(pkg, gpu):
     assert plan.prove(values).to_bytes() == cd.prove(wires).to_bytes()
     # seeds over derived classes are compared: the outputs 3 and 4 seeded as well (5 is a seed already)
     tm = cb.witness_target_map
-    extra = [cb.builder._layout()[4][cb.builder.find(tm[w])][-1] for w in (3, 4)]
+    extra = [cb.builder.cells_of(tm[w])[-1] for w in (3, 4)]
     assert not set(extra) & set(cells)
     plan2 = cd.witness_plan(cells + extra)
     assert np.array_equal(_matrix(plan2.generate(values + [prog["outputs"][3], prog["outputs"][4]])), wires)
@@ -173,7 +173,7 @@ def test_sha256_compression(pkg, gpu):
     assert hashlib.sha256(blob.tobytes()).hexdigest() == g["blob_sha256"]
     cd = pkg.CircuitData(blob)
     # (output word 24 is seeded as well -- the solver knows it -- so that ONE plan serves the right and the wrong output)
-    out_cell = cb.builder._layout()[4][cb.builder.find(cb.witness_target_map[24])][0]
+    out_cell = cb.builder.cells_of(cb.witness_target_map[24])[0]
     cells, values = cells + [out_cell], values + [g["outputs"][0]]
     plan = cd.witness_plan(cells)
     info = plan.info()
@@ -196,7 +196,7 @@ def test_sha256_compression(pkg, gpu):
     state2 = [int(x) for x in rng.integers(0, 1 << 32, size=8)]
     want2 = test_translate._sha256_compress(state2, block2)
     w2 = _matrix(plan.generate(block2 + state2 + values[24:-1] + [want2[0]]))
-    out_cells = [cb.builder._layout()[4][cb.builder.find(cb.witness_target_map[24 + i])][0] for i in range(8)]
+    out_cells = [cb.builder.cells_of(cb.witness_target_map[24 + i])[0] for i in range(8)]
     assert [int(w2[c, r]) for r, c in out_cells] == want2
     assert hashlib.sha256(_matrix(plan.generate(values)).tobytes()).hexdigest() == g["wires_sha256"]
     plan.close()
@@ -248,8 +248,7 @@ def test_plan_errors(pkg, gpu):
     _raises(pkg, E_ARG, lambda: cd.witness_plan(cells + [cells[1]]), "row %d, column %d" % cells[1], "twice")
     # witness 2 feeds the AND and the XOR: without its seed its class is stuck
     msg = _raises(pkg, E_ARG, lambda: cd.witness_plan(cells[:2] + cells[3:]), "row", "seed is missing")
-    lay = cb.builder._layout()[4]
-    stuck_cells = lay[cb.builder.find(cb.witness_target_map[2])]
+    stuck_cells = cb.builder.cells_of(cb.witness_target_map[2])
     assert any("(row %d, column %d)" % rc in msg for rc in stuck_cells), (msg, stuck_cells)
     # a verifier-only handle, a device group
     lib = pkg.load_library()

@@ -212,7 +212,7 @@ def test_errors(pkg, gpu):
     _errors_agree(pkg, cd, cells + [(n, 0)], f"row {n}, column 0")
     _errors_agree(pkg, cd, cells + [cells[1]], "row %d, column %d" % cells[1], "twice")
     msg = _errors_agree(pkg, cd, cells[:2] + cells[3:], "seed is missing")
-    stuck_cells = cb.builder._layout()[4][cb.builder.find(cb.witness_target_map[2])]
+    stuck_cells = cb.builder.cells_of(cb.witness_target_map[2])
     assert any("(row %d, column %d)" % rc in msg for rc in stuck_cells), (msg, stuck_cells)
     cd.close()
     kw, seeds = wgi.arithmetic_cycle()

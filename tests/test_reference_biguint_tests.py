@@ -139,15 +139,14 @@ def test_generator_cells_and_seeds(pkg):
     b.is_equal(c[1][0], c[2][0])
     gens = b.generators()
     assert [g[0] for g in gens] == ["biguint_divrem", "equality"]
-    cells = b._layout()[4]
     assert [len(g) for g in gens[0][1]] == [4, 2, 3, 2]
     for grp, targets in zip(gens[0][1], c[1:]):
-        assert list(grp) == [cells[b.find(t)][0] for t in targets]
+        assert list(grp) == [b.cells_of(t)[0] for t in targets]
     seeds = set(b.seed_cells())
-    assert all(cells[b.find(t)][0] in seeds for t in c[1] + c[2])
-    assert not any(cell in seeds for t in list(c[3]) + list(c[4]) for cell in cells[b.find(t)])
+    assert all(b.cells_of(t)[0] in seeds for t in c[1] + c[2])
+    assert not any(cell in seeds for t in list(c[3]) + list(c[4]) for cell in b.cells_of(t))
     b2 = bi.builder(pkg)
-    b2.events.append(("divrem", (b2.add_virtual_target(),), (b2.one(),), (b2.add_virtual_target(),), (b2.add_virtual_target(),)))
+    b2._listed_generator("divrem", (b2.add_virtual_target(),), (b2.one(),), (b2.add_virtual_target(),), (b2.add_virtual_target(),))
     b2.mul(b2.one(), b2.add_virtual_target())
     with pytest.raises(ValueError, match="lies in no gate row"):
         b2.generators()

@@ -54,9 +54,9 @@ def test_is_equal_generator_cells(pkg):
     b, tx, ty, te = moi.is_equal_circuit(pkg)
     (kind, cl), = b.generators()
     assert kind == "equality" and len(cl) == 4
-    cells = b._layout()[4]
-    (ev,) = [e for e in b.events if e[0] == "equal"]
-    assert cells[b.find(ev[4])] == [cl[3]] and cl[2] == cells[b.find(te)][0]
+    (ev,) = [e for e in b.events if e.kind == "equal"]
+    equal, inv = ev.outs
+    assert equal == te and b.cells_of(inv) == [cl[3]] and cl[2] == b.cells_of(te)[0]
     assert all(b.rows[r]["kind"] == "arith" for r, _ in cl)
 
 

@@ -58,7 +58,7 @@ def run_v(exe, tmp_path, blob, seeds, recs, cells):
 
 class Circuit:
     def __init__(self, b):
-        self.b, self.blob, self.cells = b, b._layout()[0], b._layout()[4]
+        self.b, self.blob, self.cells = b, b.blob(), b._layout().cells
         self.d = int(np.frombuffer(bytes(np.ascontiguousarray(self.blob)[:256]), dtype=np.uint32)[2])
         self.seeds = b.seed_cells()
         self.gens = b.generators()
@@ -139,7 +139,7 @@ def test_a_slot_named_twice(printer, circuits, tmp_path):  # noqa: F811
     c = circuits["virtual"]
     x = c.gens[0][1][0][0]                       # a's first limb: a seed's cell
     y = ((1 << c.d) - 1, 79)                     # a routed cell of the last row that no class and no row op holds
-    assert c.b._layout()[4] and all(tuple(y) != tuple(cell) for cl in c.cells.values() for cell in cl)
+    assert c.b._layout().cells and all(tuple(y) != tuple(cell) for cl in c.cells.values() for cell in cl)
     recs = np.concatenate([c.recs, np.array([[1, 1, 1, 1, 1]], dtype=np.uint32)])
     flat = np.concatenate([c.flat, np.array([x, x, y, y], dtype=np.uint32)])
     got = run_v(printer, tmp_path, c.blob, c.seeds, recs, flat)
@@ -187,7 +187,7 @@ def test_an_equality_only_list_gives_the_bytes_of_the_record_form(pkg, printer, 
     """{1, 1, 1, 1} shapes through the new list: cell_slot, ops, level_off and the table are the three-argument form's bytes,
     with the offsets 0, 4, 8, .. in between."""
     b = moi.translated(pkg, moi.WRITE).builder
-    blob, seeds, gens = b._layout()[0], b.seed_cells(), b.generators()
+    blob, seeds, gens = b.blob(), b.seed_cells(), b.generators()
     assert [k for k, _ in gens] == ["equality"] * 2
     old = run_printer(printer, tmp_path, blob, seeds, [(0, cl) for _, cl in gens])
     new = run_v(printer, tmp_path, blob, seeds, *records(gens))

@@ -67,19 +67,18 @@ class Circuit:
 
     def __init__(self, builder):
         self.b = builder
-        self.blob = builder._layout()[0]
-        self.cells = builder._layout()[4]
+        self.blob = builder.blob()
         self.d = int(np.frombuffer(bytes(np.ascontiguousarray(self.blob)[:256]), dtype=np.uint32)[2])
         self.seeds = builder.seed_cells()
         self.gens = [(0, cl) for kind, cl in builder.generators() if kind == "equality"]
-        self.events = [e for e in builder.events if e[0] == "equal"]
+        self.events = [e for e in builder.events if e.kind == "equal"]
         assert len(self.gens) == len(self.events) >= 1
 
     def key(self, cell):
         return (cell[1] << self.d) | cell[0]
 
     def class_cells(self, target):
-        return self.cells[self.b.find(target)]
+        return self.b.cells_of(target)
 
 
 @pytest.fixture(scope="module")
@@ -103,12 +102,12 @@ def test_plan_with_generators_follows_the_stated_rules(printer, circuits, tmp_pa
         assert lv[(g, OP_EQUALITY, 0)] == 1
         assert not table[g, 0] & W and not table[g, 1] & W and table[g, 2] & W and table[g, 3] & W
         # its writer bits are not in cell_slot: no cell of `equal`'s class, nor `inv`'s one cell, is a row op's output
-        for row, col in c.class_cells(ev[3]) + c.class_cells(ev[4]):
+        for row, col in c.class_cells(ev.outs[0]) + c.class_cells(ev.outs[1]):
             assert cell_slot[col, row] != 0xFFFFFFFF and not cell_slot[col, row] & W
         # every cell a generator names has a slot
         assert all(cell_slot[col, row] != 0xFFFFFFFF for row, col in cl)
         # the ArithmeticGate operation that reads `inv` (mul(diff, inv)) sits above the generator
-        (row, col), = c.class_cells(ev[4])
+        (row, col), = c.class_cells(ev.outs[1])
         assert col % 4 == 1 and lv[(row, OP_ARITHMETIC, col // 4)] > lv[(g, OP_EQUALITY, 0)]
 
 
@@ -130,7 +129,7 @@ def test_without_the_list_a_seed_is_missing(printer, circuits, tmp_path, name):
     one `equal`'s classes have, where the circuit has several).  `inv` is one cell outside every class: without its generator
     it has no slot and is nobody's to miss."""
     c = circuits[name]
-    equal_cells = [cell for ev in c.events for cell in c.class_cells(ev[3])]
+    equal_cells = [cell for ev in c.events for cell in c.class_cells(ev.outs[0])]
     got = run_printer(printer, tmp_path, c.blob, c.seeds)
     assert got[0] == "refused" and "a seed is missing" in got[1], got
     assert "(row %d, column %d)" % min(equal_cells, key=c.key) in got[1], (got[1], equal_cells)

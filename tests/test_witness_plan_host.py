@@ -116,7 +116,7 @@ def test_refusals(pkg, printer, tmp_path):
     refused(blob, cells + [(n, 0)], f"row {n}, column 0")
     refused(blob, cells + [cells[1]], "row %d, column %d" % cells[1], "twice")
     msg = refused(blob, cells[:2] + cells[3:], "seed is missing")
-    stuck_cells = cb.builder._layout()[4][cb.builder.find(cb.witness_target_map[2])]
+    stuck_cells = cb.builder.cells_of(cb.witness_target_map[2])
     assert any("(row %d, column %d)" % rc in msg for rc in stuck_cells), (msg, stuck_cells)
     kw, seeds = wgi.arithmetic_cycle()
     refused(pkg.build_blob(**kw), seeds, "dependency cycle", "row 0")

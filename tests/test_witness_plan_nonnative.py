@@ -25,7 +25,7 @@ def records(generators):
 
 class Circuit:
     def __init__(self, b):
-        self.b, self.blob, self.cells = b, b._layout()[0], b._layout()[4]
+        self.b, self.blob, self.cells = b, b.blob(), b._layout().cells
         self.d = int(np.frombuffer(bytes(np.ascontiguousarray(self.blob)[:256]), dtype=np.uint32)[2])
         self.seeds = b.seed_cells()
         self.gens = b.generators()

@@ -27,7 +27,7 @@ def bitwise_member(pkg, k):
         blob, wires = cb.build(prog["witness"])
         tm = cb.witness_target_map
         for w, v in prog["outputs"].items():               # (the matrix holds the outputs this module computed)
-            r, c = cb.builder._layout()[4][cb.builder.find(tm[w])][0]
+            r, c = cb.builder.cells_of(tm[w])[0]
             assert int(wires[c, r]) == v
         cells, values = wgi.seeds_from_wires(cb, wires)
         assert values[:4] == [prog["witness"][w] for w in (0, 1, 2, 5)]      # the input seeds come first, in witness order
