@@ -292,7 +292,8 @@ def _memory_operand(e, constant):
 
 def to_translator_opcodes(circuit, memory=False):
     """The opcode list ``translate.CircuitBuilderFromAcirToPlonky2.translate_circuit`` takes, for the opcodes it
-    restates (AssertZero, RANGE, AND, XOR, Sha256Compression); BrilligCall and Directive are dropped as the
+    restates (AssertZero, RANGE, AND, XOR, Sha256Compression, EcdsaSecp256k1 -- mod.rs:166-180: ("ecdsa_secp256k1", pkx, pky,
+    signature, hashed_message, output), witnesses only); BrilligCall and Directive are dropped as the
     reference drops them (mod.rs:98-104); anything else raises NotImplementedError naming the opcode.
     ``memory=True``: MemoryInit / MemoryOp become ("memory_init", block_id, [witnesses]) and ("memory_op", block_id,
     operation, index_witness, value_witness) (mod.rs:105-117; the predicate is dropped as the reference drops it);
@@ -317,6 +318,9 @@ def to_translator_opcodes(circuit, memory=False):
                 out.append((n.lower(), body["lhs"][0], body["rhs"][0], body["output"], body["lhs"][1]))
             elif n == "Sha256Compression":
                 out.append(("sha256_compression", [w for w, _ in body["inputs"]], [w for w, _ in body["hash_values"]], body["outputs"]))
+            elif n == "EcdsaSecp256k1":
+                out.append(("ecdsa_secp256k1",) + tuple([w for w, _ in body[key]] for key in ("public_key_x", "public_key_y", "signature", "hashed_message"))
+                           + (body["output"],))
             else:
                 raise NotImplementedError("BlackBoxFuncCall::%s" % n)
         else:

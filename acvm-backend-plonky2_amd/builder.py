@@ -68,11 +68,17 @@ def _ra_body(ev, vs):
 
 
 def _split_body(ev, vs):
+    base, rows, whole = ev.args                       # whole: the limbs must take all of the integer (split_le_base)
     v, out = vs[0], []
-    for num_limbs in ev.args:                         # per row: the sum, then its limbs
-        part = v & ((1 << num_limbs) - 1)
-        v >>= num_limbs
-        out += [part] + [(part >> j) & 1 for j in range(num_limbs)]
+    for num_limbs in rows:                            # per row: the sum, then its limbs
+        v, part = divmod(v, base ** num_limbs)
+        limbs, rest = [], part
+        for _ in range(num_limbs):
+            rest, limb = divmod(rest, base)
+            limbs.append(limb)
+        out += [part] + limbs
+    if whole and v:                                   # BaseSplitGenerator: "Integer too large to fit in given number of limbs"
+        raise ValueError("unsatisfiable: split_le_base: the integer does not fit its limbs")
     return out
 
 
@@ -119,8 +125,9 @@ ROW_KINDS = {
                                                  (G_POSEIDON, (0, 0, 0, 0), 7, 0)),
                         lambda g: list(zip(g["in"] + g["out"] + [g["swap"]], range(25))), _fill_poseidon),
     "ra": RowKind(lambda g: (g["bits"],), _ra_spec, _ra_cells, _fill_ra),
-    "basesum": RowKind(lambda g: (g["L"],),
-                       lambda b, L: (2, "BaseSumGate { num_limbs: %d } + Base: 2" % L, (G_BASE_SUM, (2, L, 0, 0), 2, 0)),
+    # UNPINNED: the id as plonky2 0.2.2 prints it, format!("{self:?} + Base: {B}"), as recollected; degree() = B
+    "basesum": RowKind(lambda g: (g["base"], g["L"]),
+                       lambda b, base, L: (base, "BaseSumGate { num_limbs: %d } + Base: %d" % (L, base), (G_BASE_SUM, (base, L, 0, 0), base, 0)),
                        lambda g: list(zip([g["sum"]] + g["limbs"], range(1 + g["L"])))),
 }
 SPECIAL_ROWS = {("noop",): (0, "NoopGate", (G_NOOP, (0, 0, 0, 0), 0, 0)),
@@ -268,6 +275,13 @@ class CircuitBuilder:
     def mul_const_add(self, c, x, y):
         return self.mul_add(self.constant(c), x, y)
 
+    def add_many(self, terms):
+        """gadgets/arithmetic.rs `add_many` -- UNPINNED (recollection of plonky2 0.2.2): a fold with `add` from `zero()`."""
+        acc = self.zero()
+        for t in terms:
+            acc = self.add(acc, t)
+        return acc
+
     # -- booleans (gadgets/arithmetic.rs, gadgets/select.rs) ---------------------------------------
     def assert_bool(self, b):
         self.connect(self.mul_sub(b, b, b), self.zero())
@@ -336,8 +350,8 @@ class CircuitBuilder:
         return self._ra_copy(self.rows[r], index, v)
 
     # -- gadgets/split_join.rs ----------------------------------------------------------------------
-    def _base_sum_row(self, num_limbs):
-        row = {"kind": "basesum", "L": num_limbs, "sum": self.add_virtual_target(),
+    def _base_sum_row(self, num_limbs, base=2):
+        row = {"kind": "basesum", "base": base, "L": num_limbs, "sum": self.add_virtual_target(),
                "limbs": [self.add_virtual_target() for _ in range(num_limbs)]}
         self.rows.append(row)
         return row
@@ -355,8 +369,17 @@ class CircuitBuilder:
             acc = self.mul_const_add(pow(2, BASE_SUM_LIMBS, P), acc, g["sum"])
         self.connect(acc, integer)
         self.events.append(Generator("split", (integer,), tuple(t for g in gates for t in [g["sum"]] + g["limbs"]), tuple(bits),
-                                     span=k, args=(BASE_SUM_LIMBS,) * k))
+                                     span=k, args=(2, (BASE_SUM_LIMBS,) * k, False)))
         return bits[:num_bits]
+
+    def split_le_base(self, x, num_limbs, base=4):
+        """gadgets/split_base.rs `split_le_base::<B>` -- UNPINNED (recollection of plonky2 0.2.2): one BaseSumGate<B> row of
+        `num_limbs` limbs, `x` connected to its sum wire, the limb wires returned; nothing else is constrained.  The generator is
+        the row's own BaseSplitGenerator, which panics when x does not fit."""
+        row = self._base_sum_row(num_limbs, base)
+        self.connect(x, row["sum"])
+        self.events.append(Generator("split", (x,), tuple([row["sum"]] + row["limbs"]), tuple(row["limbs"]), args=(base, (num_limbs,), True)))
+        return list(row["limbs"])
 
     def le_sum(self, bits):
         bits = list(bits)
@@ -557,7 +580,8 @@ class CircuitBuilder:
         """The generators that are no gate's own, for CircuitData.witness_plan(..., generators=): ("equality", (cell_x, cell_y,
         cell_equal, cell_inv)), ("biguint_divrem", (a_cells, b_cells, div_cells, rem_cells)) and, for the four nonnative
         generators, ("nonnative_add" | "_sub" | "_mul" | "_inv", (a_cells, b_cells, first target's cells, second target's cells),
-        field name) in creation order; a target's cell -- a limb's too -- is the first cell of its copy class."""
+        field name), and ("glv_decompose", (k_cells, (), k1's then k2's cells, (k1_neg cell, k2_neg cell))), in creation order; a
+        target's cell -- a limb's too -- is the first cell of its copy class."""
         cells = self._layout().cells
 
         def first_cells(group, missing):

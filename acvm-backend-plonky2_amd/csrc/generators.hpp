@@ -10,6 +10,7 @@
 // (gadgets/split_join.rs: the sum is computed from the bits), every other body is what fill_witness_kernel always ran.
 #pragma once
 #include "bigdiv.hpp"
+#include "glv.hpp"
 #include "internal.hpp"
 #include "nonnative.hpp"
 #include "poseidon.hpp"
@@ -180,6 +181,24 @@ __device__ void gen_nonnative_inv(A &a, const uint32_t shape[4], uint32_t field)
   nn_store(a, out, shape[2], NN_LIMBS, [&](uint32_t i) { return inv[i]; });
   f.mul_divmod(x, inv);
   nn_store(a, out + shape[2], shape[3], f.w.nq, [&](uint32_t i) { return f.w.quotient_word(i); });
+}
+
+// GLVDecompositionGenerator (plonky2_ecdsa/curve/gadgets/glv.rs:258-285, registered by `decompose_secp256k1_scalar` :131): no
+// gate's own.  Its accessor numbers the cells k[0 .. lk) (read), then k1's four limbs, k2's four, k1_neg, k2_neg (set); shape
+// {lk, 0, 8, 2} as the plan checked it.  K = fold(k) mod N, N the scalar field's order; glv.hpp decomposes it.  A magnitude above
+// 128 bits (none is known: the lattice basis keeps both below 2^128) rejects on that target's top limb, by nn_store's rule.  Not
+// forced inline, for the reason gen_biguint_divrem is not.
+template <class A>
+__device__ void gen_glv_decompose(A &a, const uint32_t shape[4]) {
+  const uint32_t lk = shape[0], out = lk + shape[1], half = shape[2] / 2;
+  Glv g;
+  uint32_t k[NN_LIMBS];
+  nn_load(a, g.f, 0, lk, k);
+  g.decompose(k);
+  nn_store(a, out, half, NN_LIMBS, [&](uint32_t i) { return g.k1[i]; });
+  nn_store(a, out + half, half, NN_LIMBS, [&](uint32_t i) { return g.k2[i]; });
+  a.set(out + 2 * half, g.k1_neg ? 1 : 0);
+  a.set(out + 2 * half + 1, g.k2_neg ? 1 : 0);
 }
 
 // prc: the 360 round constants (wave-uniform index -> scalar loads)

@@ -13,15 +13,17 @@ enum : uint32_t {
   // from the plan's generator table
   OP_EQUALITY, OP_BIGUINT_DIVREM,
   // the four nonnative generators: their record keeps the field where a row op keeps its operation index (code | field << 8)
-  OP_NONNATIVE_ADD, OP_NONNATIVE_SUB, OP_NONNATIVE_MUL, OP_NONNATIVE_INV
+  OP_NONNATIVE_ADD, OP_NONNATIVE_SUB, OP_NONNATIVE_MUL, OP_NONNATIVE_INV,
+  // the GLV decomposition generator of `decompose_secp256k1_scalar`: no field (its field is the secp256k1 scalar field)
+  OP_GLV_DECOMPOSE
 };
 static_assert(OP_EQUALITY == 13 && OP_BIGUINT_DIVREM == 14 && OP_NONNATIVE_ADD == 15 && OP_NONNATIVE_SUB == 16 && OP_NONNATIVE_MUL == 17 &&
-                  OP_NONNATIVE_INV == 18,
+                  OP_NONNATIVE_INV == 18 && OP_GLV_DECOMPOSE == 19,
               "appended: the recorded plans keep their codes");
 // an op whose record names a generator of the plan's list, not a row
-P2_HD bool op_is_listed_generator(uint32_t code) { return code >= OP_EQUALITY && code <= OP_NONNATIVE_INV; }
+P2_HD bool op_is_listed_generator(uint32_t code) { return code >= OP_EQUALITY && code <= OP_GLV_DECOMPOSE; }
 // one of the generators whose word arrays live in private memory: the walk kernel's form with those arms runs them (genwit.hip)
-P2_HD bool op_is_bigint_generator(uint32_t code) { return code >= OP_BIGUINT_DIVREM && code <= OP_NONNATIVE_INV; }
+P2_HD bool op_is_bigint_generator(uint32_t code) { return code >= OP_BIGUINT_DIVREM && code <= OP_GLV_DECOMPOSE; }
 
 // The columns of one op: `in` then `out`, each the concatenation of two half-open ranges [a0, b0) ++ [a1, b1) in the order the
 // schedule lists them (an empty range has a == b).  Columns >= R are gate-internal: the compilers skip them.

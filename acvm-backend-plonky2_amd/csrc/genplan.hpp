@@ -12,7 +12,7 @@ namespace classes {
 struct Scratch;  // devclasses.hpp
 }
 
-// x: the row (OP_SEED: the seed's index, OP_EQUALITY .. OP_NONNATIVE_INV: the generator's), y: code | sub << 8 (the slot / copy inside the row): HostPlan's 64-bit word
+// x: the row (OP_SEED: the seed's index, OP_EQUALITY .. OP_GLV_DECOMPOSE: the generator's), y: code | sub << 8 (the slot / copy inside the row): HostPlan's 64-bit word
 typedef uint2 OpRec;
 static_assert(sizeof(PlanSeed) == sizeof(uint2), "the kernels read a seed cell as a uint2 (row, col)");
 

@@ -92,7 +92,7 @@ struct GenSlots {
 // The div-rem generator, called and not inlined: its word arrays (bigdiv.hpp, 53 words and the loop state) are private memory
 // of THIS frame.  A call in the kernel still costs every other arm (the SHA-256 walk 15.5 -> 23.8 ms: profiles/
 // device_witness.md), so the big-integer arms exist only in the walk kernel's BIGINT = true form, which runs the plans that list such a
-// generator (or a nonnative one, below); every other plan runs the form without them.  Lanes of one op run it with different trip counts.
+// generator (or a nonnative one or the GLV decomposition, below); every other plan runs the form without them.  Lanes of one op run it with different trip counts.
 static_assert(BIGDIV_MAX_A == PLAN_DIVREM_MAX_A && BIGDIV_MAX_B == PLAN_DIVREM_MAX_B, "the plan admits the shapes the division's arrays hold");
 __device__ __noinline__ void run_biguint_divrem(const WalkArgs &a, uint32_t g, uint32_t pos, uint32_t b) {
   const uint32_t sw = a.gen_shape[g];
@@ -116,6 +116,15 @@ __device__ __noinline__ void run_nonnative(const WalkArgs &a, uint32_t code, uin
   }
 }
 
+// The GLV decomposition generator behind a call of its own, for the same reason (glv.hpp: NonNative and four more numbers).
+static_assert(GLV_LIMBS == PLAN_GLV_LIMBS, "the plan admits the shape the decomposition writes");
+__device__ __noinline__ void run_glv_decompose(const WalkArgs &a, uint32_t g, uint32_t pos, uint32_t b) {
+  const uint32_t sw = a.gen_shape[g];
+  const uint32_t shape[4] = {sw & 0xFF, (sw >> 8) & 0xFF, (sw >> 16) & 0xFF, sw >> 24};
+  GenSlots w{a, a.gen_table + a.gen_off[g], pos, b};
+  gen_glv_decompose(w, shape);
+}
+
 template <bool BIGINT>
 __device__ __forceinline__ void run_op(const WalkArgs &a, uint32_t pos, uint32_t b) {
   const OpRec op = a.ops[pos];
@@ -135,6 +144,7 @@ __device__ __forceinline__ void run_op(const WalkArgs &a, uint32_t pos, uint32_t
   }
   if (BIGINT && op_is_bigint_generator(code)) {  // (a plan with such an op runs the BIGINT form: walk_and_scatter)
     if (code == OP_BIGUINT_DIVREM) run_biguint_divrem(a, op.x, pos, b);
+    else if (code == OP_GLV_DECOMPOSE) run_glv_decompose(a, op.x, pos, b);
     else run_nonnative(a, code, sub, op.x, pos, b);
     return;
   }

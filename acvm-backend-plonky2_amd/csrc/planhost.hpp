@@ -79,9 +79,13 @@ constexpr uint32_t PLAN_DIVREM_MAX_A = 32, PLAN_DIVREM_MAX_B = 16;  // bigdiv.hp
 //   inv        {lx, 0, lx, lx}: x (read), inv, div (set)
 constexpr uint32_t PLAN_GEN_NONNATIVE_ADD = 2, PLAN_GEN_NONNATIVE_SUB = 3, PLAN_GEN_NONNATIVE_MUL = 4, PLAN_GEN_NONNATIVE_INV = 5;
 constexpr uint32_t PLAN_NONNATIVE_LIMBS = 8, PLAN_NONNATIVE_MAX = 16, PLAN_NONNATIVE_FIELDS = 2;
+// the GLV decomposition generator (plonky2_ecdsa/curve/gadgets/glv.rs:117-149, :258-285): {lk, 0, 8, 2}, 1 <= lk <= 16: k's limbs
+// (read), k1's four limbs then k2's four, k1_neg then k2_neg (set).  Its kind word takes no field.  Kind numbers 6 and 7 stay
+// unknown kinds (reserved): the kind is 8, its op code the next one, OP_GLV_DECOMPOSE
+constexpr uint32_t PLAN_GEN_GLV_DECOMPOSE = 8, PLAN_GLV_LIMBS = 4;
 static_assert(OP_BIGUINT_DIVREM == OP_EQUALITY + PLAN_GEN_BIGUINT_DIVREM && OP_NONNATIVE_ADD == OP_EQUALITY + PLAN_GEN_NONNATIVE_ADD &&
-                  OP_NONNATIVE_INV == OP_EQUALITY + PLAN_GEN_NONNATIVE_INV,
-              "PlanGenList::code: the listed kinds and their op codes run in one order");
+                  OP_NONNATIVE_INV == OP_EQUALITY + PLAN_GEN_NONNATIVE_INV && OP_GLV_DECOMPOSE == OP_NONNATIVE_INV + 1,
+              "PlanGenList::code: the listed kinds up to the nonnative ones and their op codes run in one order, the GLV kind's follows");
 struct PlanGeneratorV {
   uint32_t kind;
   uint32_t shape[4];
@@ -89,6 +93,7 @@ struct PlanGeneratorV {
 // whether a record's kind word is a known one: the kind in bits 0-7, the field in bits 8-15 (the nonnative kinds only), nothing above
 inline bool plan_generator_kind_ok(uint32_t word) {
   const uint32_t kind = word & 0xFF, field = (word >> 8) & 0xFF;
+  if (word == PLAN_GEN_GLV_DECOMPOSE) return true;
   if (word >> 16 || kind > PLAN_GEN_NONNATIVE_INV) return false;
   return kind >= PLAN_GEN_NONNATIVE_ADD ? field < PLAN_NONNATIVE_FIELDS : field == 0;
 }
@@ -102,7 +107,7 @@ struct PlanGenList {
   uint32_t n_cells() const { return off.back(); }
   uint32_t ins(size_t g) const { return gens[g].shape[0] + gens[g].shape[1]; }
   // the op record's code and the field beside it: code | field << 8 is the word behind the list index
-  uint32_t code(size_t g) const { return OP_EQUALITY + (gens[g].kind & 0xFF); }
+  uint32_t code(size_t g) const { return gens[g].kind == PLAN_GEN_GLV_DECOMPOSE ? OP_GLV_DECOMPOSE : OP_EQUALITY + (gens[g].kind & 0xFF); }
   uint32_t field(size_t g) const { return gens[g].kind >> 8; }
   uint32_t code_word(size_t g) const { return code(g) | field(g) << 8; }
   // la | lb << 8 | ld << 16 | lr << 24: what the walk reads of a generator beside its table words
@@ -121,7 +126,7 @@ struct PlanInput {
 };
 
 // cell_slot [R][n]; ops by (level, creation order), one 64-bit word each: row | (code | sub << 8) << 32 (OP_SEED: the seed's
-// index for the row, OP_EQUALITY .. OP_NONNATIVE_INV: the generator's, sub the field); level_off [levels + 1]; gen_off [generators + 1] and
+// index for the row, OP_EQUALITY .. OP_GLV_DECOMPOSE: the generator's, sub the field); level_off [levels + 1]; gen_off [generators + 1] and
 // gen_table [gen_off[generators]], one word per cell a generator names: cell key (col << d | row) | PLAN_WRITER = this naming
 // writes the cell's slot (four words per generator when all are equality generators: [generators][4])
 struct HostPlan {
@@ -217,6 +222,7 @@ inline bool plan_generator_shape_ok(uint32_t word, const uint32_t shape[4]) {
   if (kind == PLAN_GEN_NONNATIVE_ADD || kind == PLAN_GEN_NONNATIVE_SUB) return la <= MAX && lb <= MAX && la + lb >= 1 && ld == L && lr == 1;
   if (kind == PLAN_GEN_NONNATIVE_MUL) return la <= MAX && lb <= MAX && la + lb >= L && ld == L && lr == la + lb - L;
   if (kind == PLAN_GEN_NONNATIVE_INV) return la >= 1 && la <= MAX && lb == 0 && ld == la && lr == la;
+  if (kind == PLAN_GEN_GLV_DECOMPOSE) return la >= 1 && la <= MAX && lb == 0 && ld == 2 * PLAN_GLV_LIMBS && lr == 2;
   // div_rem_biguint (biguint.rs:236-244): rem has b's limbs, div a_len - b_len + 1, or none when b_len > a_len + 1
   return la >= 1 && la <= PLAN_DIVREM_MAX_A && lb >= 1 && lb <= PLAN_DIVREM_MAX_B && lr == lb && ld == (lb > la + 1 ? 0 : la - lb + 1);
 }

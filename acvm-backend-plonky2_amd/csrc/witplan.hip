@@ -123,7 +123,8 @@ int plan_new(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, size_
   static_assert(sizeof(p2gpu_generator) == sizeof(PlanGenerator) && P2GPU_GEN_EQUALITY == PLAN_GEN_EQUALITY, "planhost.hpp restates the record");
   static_assert(sizeof(p2gpu_generator_v) == sizeof(PlanGeneratorV) && P2GPU_GEN_BIGUINT_DIVREM == PLAN_GEN_BIGUINT_DIVREM, "planhost.hpp restates the record");
   static_assert(P2GPU_GEN_NONNATIVE_ADD == PLAN_GEN_NONNATIVE_ADD && P2GPU_GEN_NONNATIVE_SUB == PLAN_GEN_NONNATIVE_SUB && P2GPU_GEN_NONNATIVE_MUL == PLAN_GEN_NONNATIVE_MUL &&
-                    P2GPU_GEN_NONNATIVE_INV == PLAN_GEN_NONNATIVE_INV && P2GPU_FIELD_SECP256K1_BASE == 0 && P2GPU_FIELD_SECP256K1_SCALAR == 1,
+                    P2GPU_GEN_NONNATIVE_INV == PLAN_GEN_NONNATIVE_INV && P2GPU_FIELD_SECP256K1_BASE == 0 && P2GPU_FIELD_SECP256K1_SCALAR == 1 &&
+                    P2GPU_GEN_GLV_DECOMPOSE == PLAN_GEN_GLV_DECOMPOSE,
                 "planhost.hpp restates the kinds");
   if (out) *out = nullptr;
   if (!c || !out || (n_seeds && !seed_cells) || n_generators >= ((size_t)1 << 32) || n_generator_cells >= ((size_t)1 << 32)) return P2GPU_E_ARG;

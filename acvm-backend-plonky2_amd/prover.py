@@ -443,7 +443,8 @@ class CircuitData:
         ``generators``: the generators that are no gate's own, [("equality", (cell_x, cell_y, cell_equal, cell_inv))] with
         (row, col) cells, and ("biguint_divrem", (a_cells, b_cells, div_cells, rem_cells)) with the limbs' cells, least
         significant first, and ("nonnative_add" | "nonnative_sub" | "nonnative_mul" | "nonnative_inv", (a_cells, b_cells, first
-        target's cells, second target's cells), "secp256k1_base" | "secp256k1_scalar") for the four nonnative generators
+        target's cells, second target's cells), "secp256k1_base" | "secp256k1_scalar") for the four nonnative generators, and
+        ("glv_decompose", (k_cells, (), the cells of k1's then k2's limbs, (k1_neg cell, k2_neg cell))) for the GLV decomposition
         (``translate.CircuitBuilder.generators()``); the plan then comes from
         ``p2gpu_witness_plan_create_gen`` / ``_build_gen``, or from ``_create_genv`` / ``_build_genv`` when a generator has
         another number of cells than four or names a field."""
@@ -530,13 +531,16 @@ class WitnessPlan:
     # word is kind | field << 8
     NONNATIVE_KINDS = {"nonnative_add": 2, "nonnative_sub": 3, "nonnative_mul": 4, "nonnative_inv": 5}
     NONNATIVE_FIELDS = {"secp256k1_base": 0, "secp256k1_scalar": 1}
+    # the GLV decomposition, given as (kind, groups) like the first two: p2gpu.h P2GPU_GEN_GLV_DECOMPOSE (6 and 7 are reserved).
+    # A table of its own: GENERATOR_KINDS is stated as exactly those two kinds by the tests of the _genv ABI
+    GLV_KINDS = {"glv_decompose": 8}
 
     @classmethod
     def _kind_word(cls, gen):
         """The kind word of a generator (kind, cells) or (kind, cells, field); a kind or a field may be given by its number."""
         kind = gen[0]
         if isinstance(kind, str):
-            kind = cls.GENERATOR_KINDS[kind] if kind in cls.GENERATOR_KINDS else cls.NONNATIVE_KINDS.get(kind, kind)
+            kind = cls.GENERATOR_KINDS[kind] if kind in cls.GENERATOR_KINDS else cls.NONNATIVE_KINDS.get(kind, cls.GLV_KINDS.get(kind, kind))
         if len(gen) > 2:
             field = cls.NONNATIVE_FIELDS.get(gen[2], gen[2]) if isinstance(gen[2], str) else gen[2]
             if isinstance(kind, str) or isinstance(field, str):

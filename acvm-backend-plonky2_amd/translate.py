@@ -18,15 +18,18 @@ Mirrors, with the reference's names:
     -- recollection of an un-vendored crate, checked by what can be checked here: every circuit it emits is satisfiable only
     by the right values (the reference's own SHA-256 compression vector, tests/test_sha256_internal.rs:481-549, comes out of
     it), and the oracle and the GPU prove it to identical bytes;
+  * ``EcdsaSecp256k1Translator`` (ecdsa_secp256k1_translator.rs:38-121), quirks kept (see the class);
   * in gadgets_u32.py, gadgets_biguint.py and gadgets_nonnative.py the three traits of the reference's own tree above it
-    (plonky2_ecdsa/biguint), as mixins: their docstrings say what is pinned.
+    (plonky2_ecdsa/biguint), and in gadgets_curve.py and gadgets_glv.py the split, curve and GLV traits above those
+    (plonky2_ecdsa/biguint/gadgets/split_nonnative.rs, plonky2_ecdsa/curve/gadgets), as mixins: their docstrings say what is pinned.
 This module composes them into `CircuitBuilder`, keeps the translators and re-exports every name callers reach as `translate.X`.
 
 What it is NOT: an ACIR *reader*.  The reference deserialises gzip + bincode `Program` bytes through the acvm
 crate (noir_and_plonky2_serialization.rs:42-64); no compiled program exists in the tree to test a reader on, so
 programs are given as Python data: [("assert_zero", mul_terms, linear, q_c), ("sha256_compression", inputs16,
 hash8, outputs8), ("range", w, num_bits), ("and" | "xor", lhs, rhs, output, num_bits), ("memory_init", block_id, [witnesses]),
-("memory_op", block_id, operation, index_witness, value_witness)] (mod.rs:105-155).
+("memory_op", block_id, operation, index_witness, value_witness), ("ecdsa_secp256k1", pkx32, pky32, signature64, hashed_message32,
+output)] (mod.rs:105-180).
 
 Host-side Python by design: translation runs once per circuit, off the hot path (north_star keeps this layer in
 Rust; this file exists so that the named SHA256 circuit can be built and proved without it).
@@ -37,6 +40,8 @@ from . import builder
 from .builder import (BASE_SUM_LIMBS, G_ARITHMETIC, G_BASE_SUM, G_CONSTANT, G_NOOP, G_POSEIDON, G_PUBLIC_INPUT,  # noqa: F401
                       G_RANDOM_ACCESS, GENERATORS, NUM_CONSTANTS, NUM_OPS, NUM_ROUTED, NUM_WIRES, ROW_KINDS, Generator, Layout, P)
 from .gadgets_biguint import CircuitBuilderBiguint
+from .gadgets_curve import SECP256K1_GENERATOR_X, SECP256K1_GENERATOR_Y, CircuitBuilderCurve, CircuitBuilderSplit  # noqa: F401
+from .gadgets_glv import A1, A2, B2, GLV_BETA, GLV_S, MINUS_B1, CircuitBuilderGlv, decompose_secp256k1_scalar  # noqa: F401
 from .gadgets_nonnative import NONNATIVE_EVENTS, NONNATIVE_FIELDS, CircuitBuilderNonNative  # noqa: F401
 from .gadgets_u32 import (G_COMPARISON, G_U32_ADD_MANY, G_U32_ARITHMETIC, G_U32_RANGE_CHECK, G_U32_SUBTRACTION,  # noqa: F401
                           MAX_NUM_ADDENDS, U32_MAX, CircuitBuilderU32)
@@ -44,10 +49,12 @@ from .prover import WitnessPlan
 
 GEN_EQUALITY, GEN_BIGUINT_DIVREM = (WitnessPlan.GENERATOR_KINDS[k] for k in ("equality", "biguint_divrem"))      # p2gpu.h P2GPU_GEN_*
 GEN_NONNATIVE_ADD, GEN_NONNATIVE_SUB, GEN_NONNATIVE_MUL, GEN_NONNATIVE_INV = (WitnessPlan.NONNATIVE_KINDS[k] for k in NONNATIVE_EVENTS.values())
+GEN_GLV_DECOMPOSE = WitnessPlan.GLV_KINDS["glv_decompose"]
 
 
-class CircuitBuilder(CircuitBuilderNonNative, CircuitBuilderBiguint, CircuitBuilderU32, builder.CircuitBuilder):
-    """plonky2's CircuitBuilder with the three traits the reference's tree implements on it."""
+class CircuitBuilder(CircuitBuilderGlv, CircuitBuilderCurve, CircuitBuilderSplit, CircuitBuilderNonNative, CircuitBuilderBiguint, CircuitBuilderU32,
+                     builder.CircuitBuilder):
+    """plonky2's CircuitBuilder with the traits the reference's tree implements on it."""
 
 
 class BinaryDigitsTarget:
@@ -191,6 +198,60 @@ class MemoryOperationsTranslator:
             raise ValueError("Backend encountered unknown memory operation code (nor 0 or 1)")
 
 
+class EcdsaSecp256k1Translator:
+    """ecdsa_secp256k1_translator.rs:38-121, quirks kept: each 32-byte string is read LITTLE-endian -- limb i is
+    b[4i] + 2^8 b[4i+1] + 2^16 b[4i+2] + 2^24 b[4i+3], limb 0 the least significant -- and the output is `cmp_biguint(r, R.x)`,
+    which is r <= R.x, not equality.  So the circuit proves r <= R.x for R = (h / s) G + (r / s) Q over those readings, not the
+    ECDSA verification of the big-endian values.  The public key is not checked to be on the curve, as upstream."""
+
+    def __init__(self, translator, hashed_msg, public_key_x, public_key_y, signature, output):
+        self.translator, self.builder = translator, translator.builder
+        self.hashed_msg, self.public_key_x, self.public_key_y = list(hashed_msg), list(public_key_x), list(public_key_y)
+        self.signature, self.output = list(signature), output
+        assert len(self.hashed_msg) == len(self.public_key_x) == len(self.public_key_y) == 32 and len(self.signature) == 64
+
+    # :38-59
+    def translate(self):
+        b = self.builder
+        public_key = self._public_key_target()
+        r = self._32_bytes_to_field_element(self.signature[:32], "secp256k1_scalar")
+        s = self._32_bytes_to_field_element(self.signature[32:], "secp256k1_scalar")
+        h = self._32_bytes_to_field_element(self.hashed_msg, "secp256k1_scalar")
+        r_point = self._calculate_r(public_key, r, s, h)
+        does_signature_verify = b.cmp_biguint(r, r_point[0])
+        b.connect(does_signature_verify, self.translator._target(self.output))
+
+    # :61-87
+    def _calculate_r(self, public_key, r, s, h):
+        b, field = self.builder, "secp256k1_scalar"
+        s1 = b.inv_nonnative(s, field)
+        u_1 = b.mul_nonnative(h, s1, field)
+        u_2 = b.mul_nonnative(r, s1, field)
+        generator = b.curve_generator_constant()
+        r_factor_1 = b.glv_mul(generator, u_1)
+        r_factor_2 = b.glv_mul(public_key, u_2)
+        return b.curve_add(r_factor_1, r_factor_2)
+
+    # :89-93
+    def _public_key_target(self):
+        x = self._32_bytes_to_field_element(self.public_key_x, "secp256k1_base")
+        y = self._32_bytes_to_field_element(self.public_key_y, "secp256k1_base")
+        return x, y
+
+    # :95-121
+    def _32_bytes_to_field_element(self, byte_witnesses, field):
+        b = self.builder
+        byte_targets = [self.translator._target(w) for w in byte_witnesses]
+        u32_limbs = []
+        for i in range(8):
+            target_0 = byte_targets[4 * i]
+            target_1 = b.mul_const(1 << 8, byte_targets[4 * i + 1])
+            target_2 = b.mul_const(1 << 16, byte_targets[4 * i + 2])
+            target_3 = b.mul_const(1 << 24, byte_targets[4 * i + 3])
+            u32_limbs.append(b.add_many([target_0, target_1, target_2, target_3]))
+        return b.biguint_to_nonnative(u32_limbs, field)
+
+
 class CircuitBuilderFromAcirToPlonky2:
     """mod.rs:37-330, for programs given as Python data (see the module docstring)."""
 
@@ -298,6 +359,9 @@ class CircuitBuilderFromAcirToPlonky2:
                 MemoryOperationsTranslator(self.builder, self.witness_target_map, self.memory_blocks).translate_memory_init(op[2], op[1])
             elif op[0] == "memory_op":
                 MemoryOperationsTranslator(self.builder, self.witness_target_map, self.memory_blocks).translate_memory_op(*op[1:])
+            elif op[0] == "ecdsa_secp256k1":      # mod.rs:166-180, :203-216
+                pkx, pky, signature, hashed_message, output = op[1:]
+                EcdsaSecp256k1Translator(self, hashed_message, pkx, pky, signature, output).translate()
             else:
                 raise NotImplementedError(op[0])
 
@@ -318,7 +382,7 @@ class CircuitBuilderFromAcirToPlonky2:
         return b.seed_cells(), b.seed_values({t: v for t, v in vals.items() if b.find(t) in roots})
 
     def witness_generators(self):
-        """The generators that are no gate's own (the equality generators of the memory writes), for
+        """The generators that are no gate's own (the equality generators of the memory writes, the big-integer ones of ECDSA), for
         CircuitData.witness_plan(cells, generators=...) beside witness_seeds()."""
         return self.builder.generators()
 

@@ -253,13 +253,26 @@ typedef struct { uint32_t kind; uint32_t shape[4]; } p2gpu_generator_v;
  * cell; a value with more digits than its target has limbs -> that target's top limb (a target without limbs: the generator's
  * first cell).  The op record is list index | (code | field << 8) << 32, codes 15 .. 18 in the order above.  An unknown kind, as
  * above and with the whole word in the message: a field other than these two, a field on kinds 0 and 1, a bit above 15, a kind
- * above 5. */
+ * above 5 (but for P2GPU_GEN_GLV_DECOMPOSE, below). */
 #define P2GPU_GEN_NONNATIVE_ADD 2
 #define P2GPU_GEN_NONNATIVE_SUB 3
 #define P2GPU_GEN_NONNATIVE_MUL 4
 #define P2GPU_GEN_NONNATIVE_INV 5
 #define P2GPU_FIELD_SECP256K1_BASE 0   /* 2^256 - 2^32 - 977 */
 #define P2GPU_FIELD_SECP256K1_SCALAR 1 /* 0xFFFFFFFF FFFFFFFF FFFFFFFF FFFFFFFE BAAEDCE6 AF48A03B BFD25E8C D0364141 */
+/* ---- the GLV decomposition generator ----
+ * The GLVDecompositionGenerator that `decompose_secp256k1_scalar` registers (plonky2_ecdsa/curve/gadgets/glv.rs:117-149; generator
+ * :258-285, its arithmetic :50-88; the Rust side lists it at that call site).
+ *   P2GPU_GEN_GLV_DECOMPOSE  {lk, 0, 8, 2}, 1 <= lk <= 16: k's limbs (read); k1's four limbs, then k2's four; k1_neg, k2_neg (set).
+ *                            K = fold(k) mod N, N the order of the secp256k1 scalar field (P2GPU_FIELD_SECP256K1_SCALAR's modulus);
+ *                            c1 = round(B2 K / N), c2 = round(MINUS_B1 K / N) (N is odd: no ties); k1_raw = K - c1 A1 - c2 A2,
+ *                            k2_raw = c1 MINUS_B1 - c2 B2 modulo N; a raw value above (N - 1) / 2 is negative, and its magnitude
+ *                            N - raw is what is set, as 32-bit digits; the signs are 0 or 1.
+ * The kind word takes no field: it is 8, and any bit above bit 7 makes it an unknown kind, with the whole word in the message.  The
+ * kind numbers 6 and 7 are reserved and stay unknown kinds.  A magnitude with more digits than four limbs -> that target's top
+ * limb (P2GPU_E_UNSATISFIED, as above).  The op record is list index | 19 << 32.  Every other refusal is worded as above: shape,
+ * cell count, cell outside the routed cells. */
+#define P2GPU_GEN_GLV_DECOMPOSE 8
 int p2gpu_witness_plan_create_genv(p2gpu_circuit *c, const uint32_t *seed_cells, size_t n_seeds, const p2gpu_generator_v *generators,
                                    size_t n_generators, const uint32_t *cells /* [n_cells][2] = (row, col) */, size_t n_cells,
                                    p2gpu_witness_plan **out);
