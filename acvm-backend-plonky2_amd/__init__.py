@@ -13,6 +13,7 @@ with ``__graft_entry__.load_package()`` which registers it as
 from .prover import (  # noqa: F401
     CircuitData,
     WitnessPlan,
+    WitnessReport,
     build_blob,
     VerifierCircuitData,
     ProofWithPublicInputs,

@@ -130,6 +130,10 @@ ROW_KINDS = {
                        lambda b, base, L: (base, "BaseSumGate { num_limbs: %d } + Base: %d" % (L, base), (G_BASE_SUM, (base, L, 0, 0), base, 0)),
                        lambda g: list(zip([g["sum"]] + g["limbs"], range(1 + g["L"])))),
 }
+# The rows that hold several operations, for explain(): (constraints per operation -- an operation's constraints follow each other
+# in the gate's evaluation order, csrc/gates.hpp --, row -> the targets of every operation)
+ROW_OPS = {"arith": (lambda g: 1, lambda g: g["ops"]),
+           "ra": (lambda g: g["bits"] + 2, lambda g: [[idx, claimed] + lst for idx, claimed, lst in g["copies"]])}
 SPECIAL_ROWS = {("noop",): (0, "NoopGate", (G_NOOP, (0, 0, 0, 0), 0, 0)),
                 ("const",): (1, "ConstantGate { num_consts: 2 }", (G_CONSTANT, (2, 0, 0, 0), 1, 2)),
                 ("pi",): (1, "PublicInputGate", (G_PUBLIC_INPUT, (0, 0, 0, 0), 1, 0))}
@@ -597,6 +601,51 @@ class CircuitBuilder:
             if kind.plan is not None:
                 out.append((kind.plan, first_cells(ev.groups, kind.missing)) + ((ev.field,) if ev.field is not None else ()))
         return out
+
+    # -- a WitnessReport (CircuitData.check_witness) in the builder's own words ----------------------------
+    def row_of(self, row):
+        """(what the circuit's row `row` is to the builder, its creating row dict or None): a row of self.rows by its kind, the
+        PublicInputGate row, a ConstantGate row, padding."""
+        lay = self._layout()
+        if row < len(lay.rows):
+            return lay.rows[row]["kind"], lay.rows[row]
+        if row == lay.pi_row:
+            return "pi", None
+        in_extra_wires = min(len(lay.constants), sum(g["extra"] for g in lay.rows if g["kind"] == "ra"))
+        const_rows = (len(lay.constants) - in_extra_wires + 1) // 2
+        return ("const" if row <= lay.pi_row + const_rows else "noop"), None
+
+    def _class_name(self, cell):
+        """A routed cell by its copy class: the class's first target, its size and its first cell (cells_of)."""
+        for rt, cl in self._layout().cells.items():
+            if cell in cl:
+                const = next((c for t, c in self.const_of.items() if self.find(t) == rt), None)
+                return "target %d%s (class of %d cells from %s)" % (rt, "" if const is None else " = constant %d" % const, len(cl), cl[0])
+        return "no target"
+
+    def explain(self, report):
+        """A short string: the report's first failing row as the builder made it -- the creating row's kind, the operation inside
+        it where the row holds several, the targets routed there -- and its first broken copy as the copy classes (cells_of) of
+        the two cells."""
+        parts = []
+        if report.first_gate is not None:
+            row, _, _, constraint, value = report.first_gate
+            kind, g = self.row_of(row)
+            text = "row %d is a %s row: constraint %d = 0x%x" % (row, kind, constraint, value)
+            if g is not None and kind in ROW_OPS:
+                per_op, ops_of = ROW_OPS[kind]
+                k, ops = constraint // per_op(g), ops_of(g)
+                text += ", operation %d" % k + (" on targets %s" % (tuple(ops[k]),) if k < len(ops) else " (unused)")
+            elif g is not None:
+                text += ", targets %s" % (tuple(t for t, _ in ROW_KINDS[kind].cells(g)),)
+            parts.append(text)
+        if report.first_copy is not None:
+            (r0, c0), (r1, c1), (v0, v1) = report.first_copy
+            parts.append("copy: cell (%d, %d) = 0x%x of %s differs from cell (%d, %d) = 0x%x of %s"
+                         % (r0, c0, v0, self._class_name((r0, c0)), r1, c1, v1, self._class_name((r1, c1))))
+        if report.first_noncanonical is not None:
+            parts.append("cell (%d, %d) holds no canonical field element" % report.first_noncanonical)
+        return "; ".join(parts) if parts else "the witness satisfies the circuit"
 
     def value_of(self, t):
         return self.values[self.find(t)]

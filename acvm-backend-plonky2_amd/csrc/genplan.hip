@@ -514,30 +514,15 @@ struct PlanCtx {
 
 // ---- 1. decode sigma ----
 int PlanCtx::decode() {
-  std::vector<gl_t> kpow(2 * (size_t)R);
-  for (uint32_t col = 0; col < R; col++) {
-    gl_t t = c->k_is[col];
-    for (uint32_t i = 0; i < d; i++) t = gl_sqr(t);
-    kpow[col] = t;
-    kpow[R + col] = gl_inv(c->k_is[col]);
-  }
-  gl_t *d_kpow = S.alloc<gl_t>(2 * (size_t)R);
-  gl_t *wkeys = S.alloc<gl_t>(2 * n);
-  uint32_t *wrows = S.alloc<uint32_t>(2 * n);
   partner = S.alloc<uint32_t>(tot);
   parent = S.alloc<uint32_t>(tot);
   list = S.alloc<unsigned long long>(tot);
   cell_slot = S.alloc<uint32_t>(tot);
   d_seeds = S.alloc<uint2>(NS);
-  if (!d_kpow || !wkeys || !wrows || !partner || !parent || !list || !cell_slot || !d_seeds)
-    return fail("scratch (classes)", hipErrorOutOfMemory);
-  if (!ok(hipMemcpyAsync(d_kpow, kpow.data(), 16 * (size_t)R, hipMemcpyHostToDevice, st), "copy the coset powers")) return P2GPU_E_DEVICE;
+  if (!partner || !parent || !list || !cell_slot || !d_seeds) return fail("scratch (classes)", hipErrorOutOfMemory);
   if (NS && !ok(hipMemcpyAsync(d_seeds, seeds.data(), sizeof(uint2) * NS, hipMemcpyHostToDevice, st), "copy the seed cells")) return P2GPU_E_DEVICE;
-  hipLaunchKernelGGL(plan_powers_kernel, dim3(grid_for(n)), dim3(TPB), 0, st, c->tw_fwd.p, d, wkeys, wrows);
-  const auto sort = S.radix_sort_pairs(wkeys, wkeys + n, wrows, wrows + n, n, 0u, 64u, st);
-  if (!ok(sort.e, sort.step)) return P2GPU_E_DEVICE;
-  hipLaunchKernelGGL(plan_decode_kernel, dim3(grid_for(tot)), dim3(TPB), 0, st, c->d_sigmas.p, c->d_kis.p, d_kpow, c->tw_fwd.p, wkeys + n,
-                     wrows + n, d, R, partner, ctr + C_BAD_SIGMA);
+  const char *step = "decode sigma";
+  if (!ok(sigma_partners(c, S, partner, ctr + C_BAD_SIGMA, &step), step)) return P2GPU_E_DEVICE;
   return P2GPU_OK;
 }
 
@@ -703,6 +688,35 @@ int PlanCtx::unreached() {
 }  // namespace
 
 namespace p2 {
+
+hipError_t sigma_partners(p2gpu_circuit *c, classes::Scratch &S, uint32_t *partner, unsigned long long *bad, const char **step) {
+  const uint32_t R = c->R, d = c->d;
+  const size_t n = c->n, tot = (size_t)R * n;
+  hipStream_t st = c->stream;
+  std::vector<gl_t> kpow(2 * (size_t)R);
+  for (uint32_t col = 0; col < R; col++) {
+    gl_t t = c->k_is[col];
+    for (uint32_t i = 0; i < d; i++) t = gl_sqr(t);
+    kpow[col] = t;
+    kpow[R + col] = gl_inv(c->k_is[col]);
+  }
+  gl_t *d_kpow = S.alloc<gl_t>(2 * (size_t)R);
+  gl_t *wkeys = S.alloc<gl_t>(2 * n);
+  uint32_t *wrows = S.alloc<uint32_t>(2 * n);
+  *step = "scratch (decode sigma)";
+  if (!d_kpow || !wkeys || !wrows) return hipErrorOutOfMemory;
+  *step = "copy the coset powers";
+  // (pageable host memory: the copy has left kpow when the call returns)
+  if (hipError_t e = hipMemcpyAsync(d_kpow, kpow.data(), 16 * (size_t)R, hipMemcpyHostToDevice, st)) return e;
+  hipLaunchKernelGGL(plan_powers_kernel, dim3(grid_for(n)), dim3(TPB), 0, st, c->tw_fwd.p, d, wkeys, wrows);
+  const auto sort = S.radix_sort_pairs(wkeys, wkeys + n, wrows, wrows + n, n, 0u, 64u, st);
+  *step = sort.step;
+  if (sort.e != hipSuccess) return sort.e;
+  hipLaunchKernelGGL(plan_decode_kernel, dim3(grid_for(tot)), dim3(TPB), 0, st, c->d_sigmas.p, c->d_kis.p, d_kpow, c->tw_fwd.p, wkeys + n,
+                     wrows + n, d, R, partner, bad);
+  *step = "decode sigma";
+  return hipSuccess;
+}
 
 int plan_compile_device(p2gpu_circuit *c, const std::vector<PlanSeed> &seeds, const PlanGenList &gens, classes::Scratch &S, PlanArrays &out) {
   PlanCtx x(c, seeds, gens, S);

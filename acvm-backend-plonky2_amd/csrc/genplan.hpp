@@ -34,6 +34,13 @@ inline int plan_refuse(const p2gpu_circuit *c, const PlanRefusal &r) {
   return P2GPU_E_ARG;
 }
 
+// The decode of the handle's sigma columns, shared by the plan compiler and the witness check (check.hip): partner [R][n] (device,
+// the caller's) <- for every routed cell x, numbered key = col << d | row as sigma is laid out, the key sigma[x] names;
+// PLAN_UNSET for a fixed point and for a refused value (>= p, or naming no routed cell), the smallest refused key through an
+// atomicMin on *bad (a device word the caller presets to UINT64_MAX).  The tables it needs (the cosets' n-th powers, the sorted
+// powers of w) live in S; everything is enqueued on c->stream, d >= 1.  A failing runtime call comes back with its step's words.
+hipError_t sigma_partners(p2gpu_circuit *c, classes::Scratch &S, uint32_t *partner, unsigned long long *bad, const char **step);
+
 // The plan of circuit c for `seeds` (already through plan_seeds) and `gens` (already through plan_generators), compiled on c->stream.  The arrays of `out` live in S,
 // which the caller releases once plan_finish has copied them.  Refusals carry p2gpu_witness_plan_create's codes and words.
 int plan_compile_device(p2gpu_circuit *c, const std::vector<PlanSeed> &seeds, const PlanGenList &gens, classes::Scratch &S, PlanArrays &out);

@@ -344,4 +344,16 @@ int p2gpu_prove_seeds(p2gpu_witness_plan *p, const uint64_t *seed_values, const 
   return prove_impl(c, c->wires_vals.p, pis, n_pi, proof_out, proof_len, tm, now_ms() - t0);
 } P2GPU_CATCH
 
+int p2gpu_check_seeds(p2gpu_witness_plan *p, const uint64_t *seed_values, const uint64_t *pis, uint32_t n_pi, p2gpu_witness_report *report,
+                      uint16_t *row_status, uint8_t *cell_flags) try {
+  if (!p || !report || (p->n_seeds && !seed_values)) return P2GPU_E_ARG;
+  p2gpu_circuit *c = p->c;  // (a plan exists on a plain prover handle only)
+  if (int rc = check_public_inputs(c, pis, n_pi)) return rc;
+  {
+    ProfGuard pg(c);
+    if (int rc = generate(p, seed_values, c->wires_vals.p)) return rc;
+  }
+  return check_witness_impl(c, c->wires_vals.p, 1, pis, n_pi, report, row_status, cell_flags);
+} P2GPU_CATCH
+
 }  // extern "C"

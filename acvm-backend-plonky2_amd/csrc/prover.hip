@@ -62,19 +62,6 @@ double lap(Proof &P) {
 // columns of the four oracles together
 uint32_t committed_cols(const p2gpu_circuit *c) { return c->NC + c->R + c->W + c->K * (1 + c->PP) + c->K * c->QF; }
 
-int check_public_inputs(const p2gpu_circuit *c, const uint64_t *pis, uint32_t n_pi) {
-  if (n_pi != c->num_pi || (n_pi && !pis)) {
-    set_err("expected %u public inputs, got %u", c->num_pi, n_pi);
-    return P2GPU_E_ARG;
-  }
-  for (uint32_t i = 0; i < n_pi; i++)
-    if (pis[i] >= GL_P) {
-      set_err("public input %u is not a canonical field element", i);
-      return P2GPU_E_ARG;
-    }
-  return 0;
-}
-
 // ---- 1. wires commitment ----
 int commit_wires(p2gpu_circuit *c, Proof &P) {
   g_hp.mark("start");

@@ -28,6 +28,25 @@ inline int prover_handle(const p2gpu_circuit *c) {
   return P2GPU_E_ARG;
 }
 
+// the public inputs of one witness against the circuit's count, each a canonical field element (0: acceptable)
+inline int check_public_inputs(const p2gpu_circuit *c, const uint64_t *pis, uint32_t n_pi) {
+  if (n_pi != c->num_pi || (n_pi && !pis)) {
+    set_err("expected %u public inputs, got %u", c->num_pi, n_pi);
+    return P2GPU_E_ARG;
+  }
+  for (uint32_t i = 0; i < n_pi; i++)
+    if (pis[i] >= GL_P) {
+      set_err("public input %u is not a canonical field element", i);
+      return P2GPU_E_ARG;
+    }
+  return 0;
+}
+
+// ---- check.hip ----
+// p2gpu_check_witness_dev behind its argument checks: `batch` witnesses [batch][W][n] resident on c's device, c a plain prover handle
+int check_witness_impl(p2gpu_circuit *c, const gl_t *wires_dev, size_t batch, const uint64_t *pis, uint32_t n_pi,
+                       p2gpu_witness_report *reports, uint16_t *row_status, uint8_t *cell_flags);
+
 // ---- prover.hip ----
 // P2GPU_TRACE=1: synchronise after every phase and report progress on stderr (debugging aid)
 bool trace_on();

@@ -2,7 +2,7 @@
 range_check_u32.rs, multiple_comparison.rs) over its five gates (biguint/gates/*.rs: shapes, wire positions, degrees and ids are
 read off that source, so they are pinned), as a mixin of builder.CircuitBuilder, with the gates' generators and row kinds.
 A U32Target is a target that is assumed to hold 32 bits.  Only `find_slot`, plonky2's row sharing, is UNPINNED (see `_u32_op`)."""
-from .builder import GENERATORS, NUM_ROUTED, P, ROW_KINDS, CircuitBuilder, Generator, GeneratorKind, RowKind, op_cells
+from .builder import GENERATORS, NUM_ROUTED, P, ROW_KINDS, ROW_OPS, CircuitBuilder, Generator, GeneratorKind, RowKind, op_cells
 
 G_U32_ARITHMETIC, G_U32_ADD_MANY, G_U32_SUBTRACTION, G_U32_RANGE_CHECK, G_COMPARISON = 7, 8, 9, 10, 11   # p2gpu.h gate kinds
 MAX_NUM_ADDENDS, U32_MAX = 16, 0xFFFFFFFF      # gates/add_many_u32.rs:24
@@ -122,6 +122,11 @@ ROW_KINDS.update({
                         lambda g: list(zip(g["limbs"], range(len(g["limbs"])))), _fill_u32range),
     "cmp": RowKind(lambda g: (g["bits"], g["chunks"]), _cmp_spec, lambda g: [(g["a"], 0), (g["b"], 1), (g["res"], 2)], _fill_cmp),
 })
+
+
+# constraints per operation (gates.hpp: 2 + 32 limbs + 2, 1 + 18 + 2, 1 + 16 + 2; per range-checked limb 1 + 16)
+ROW_OPS.update({"u32arith": (lambda g: 36, lambda g: g["ops"]), "u32addmany": (lambda g: 21, lambda g: g["ops"]),
+                "u32sub": (lambda g: 19, lambda g: g["ops"]), "u32range": (lambda g: 17, lambda g: [[t] for t in g["limbs"]])})
 
 
 class CircuitBuilderU32:

@@ -41,6 +41,56 @@ class _Timings(ctypes.Structure):
     ]
 
 
+class _WitnessReport(ctypes.Structure):
+    """p2gpu_witness_report"""
+    _fields_ = [
+        ("gate_rows_failed", ctypes.c_uint64),
+        ("copy_cells_failed", ctypes.c_uint64),
+        ("noncanonical_cells", ctypes.c_uint64),
+        ("gate_row", ctypes.c_uint32),
+        ("gate_index", ctypes.c_uint32),
+        ("gate_kind", ctypes.c_uint32),
+        ("constraint", ctypes.c_uint32),
+        ("constraint_value", ctypes.c_uint64),
+        ("copy_cell", ctypes.c_uint32 * 2),
+        ("copy_partner", ctypes.c_uint32 * 2),
+        ("copy_values", ctypes.c_uint64 * 2),
+        ("noncanonical_cell", ctypes.c_uint32 * 2),
+    ]
+
+
+GATE_KIND_NAMES = ("NoopGate", "ConstantGate", "PublicInputGate", "ArithmeticGate", "BaseSumGate", "RandomAccessGate", "PoseidonGate",
+                   "U32ArithmeticGate", "U32AddManyGate", "U32SubtractionGate", "U32RangeCheckGate", "ComparisonGate")
+
+
+class WitnessReport:
+    """What ``p2gpu_check_witness`` found in one wire matrix.  `first_gate`: (row, gate index, gate kind, constraint, value) of
+    the lowest failing row and its lowest failing constraint; `first_copy`: ((row, col), (row, col) of sigma of it, the two
+    values) of the flagged cell with the lowest key col << degree_bits | row; `first_noncanonical`: (row, col); each None where
+    its count is 0.  With details: `row_status` [degree] uint16 (the first failing constraint of every row, 0xFFFF: none) and
+    `cell_flags` [num_routed_wires][degree] uint8 (1: a flagged copy cell), else None.  `message`: the library's words for the
+    first finding ("" for a clean report of a lone call)."""
+
+    def __init__(self, raw, row_status=None, cell_flags=None, message=""):
+        self.gate_rows_failed, self.copy_cells_failed = int(raw.gate_rows_failed), int(raw.copy_cells_failed)
+        self.noncanonical_cells = int(raw.noncanonical_cells)
+        self.first_gate = (int(raw.gate_row), int(raw.gate_index), int(raw.gate_kind), int(raw.constraint),
+                           int(raw.constraint_value)) if self.gate_rows_failed else None
+        self.first_copy = (tuple(int(x) for x in raw.copy_cell), tuple(int(x) for x in raw.copy_partner),
+                           tuple(int(x) for x in raw.copy_values)) if self.copy_cells_failed else None
+        self.first_noncanonical = tuple(int(x) for x in raw.noncanonical_cell) if self.noncanonical_cells else None
+        self.row_status, self.cell_flags, self.message = row_status, cell_flags, message
+
+    @property
+    def ok(self):
+        return not (self.gate_rows_failed or self.copy_cells_failed or self.noncanonical_cells)
+
+    def __repr__(self):
+        return "WitnessReport(ok)" if self.ok else "WitnessReport(gate_rows_failed=%d, copy_cells_failed=%d, noncanonical_cells=%d, first_gate=%r, " \
+            "first_copy=%r, first_noncanonical=%r)" % (self.gate_rows_failed, self.copy_cells_failed, self.noncanonical_cells, self.first_gate,
+                                                       self.first_copy, self.first_noncanonical)
+
+
 _ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64)
 
 
@@ -107,6 +157,9 @@ def load_library():
     lib.p2gpu_generate_witness.argtypes = [vp, vp, vp]
     lib.p2gpu_generate_witness_batch.argtypes = [vp, vp, sz, vp, vp, vp]
     lib.p2gpu_prove_seeds.argtypes = [vp, vp, vp, ctypes.c_uint32, u8p, ctypes.POINTER(sz), ctypes.POINTER(_Timings)]
+    lib.p2gpu_check_witness_dev.argtypes = [vp, vp, sz, vp, ctypes.c_uint32, vp, vp, vp]
+    lib.p2gpu_check_witness.argtypes = [vp, vp, vp, ctypes.c_uint32, vp, vp, vp]
+    lib.p2gpu_check_seeds.argtypes = [vp, vp, vp, ctypes.c_uint32, vp, vp, vp]
     lib.p2gpu_verify.argtypes = [vp, u8p, sz]
     lib.p2gpu_circuit_export_vk.argtypes = [vp, u8p, ctypes.POINTER(sz)]
     lib.p2gpu_circuit_export_vk_plonky2.argtypes = [vp, u8p, ctypes.POINTER(sz)]
@@ -427,6 +480,72 @@ class CircuitData:
         t = {f: getattr(tm, f) for f, _ in _Timings._fields_}
         return ProofWithPublicInputs(out[:plen.value].tobytes(), t)
 
+    def _check_call(self, call, batch, public_inputs, details):
+        """Run call(pis pointer, n_pi, reports pointer, row_status pointer, cell_flags pointer) -> rc of one of the check entry
+        points over `batch` witnesses; [WitnessReport].  A report that is not clean does not raise: -5 is the answer asked for."""
+        rows = [[int(v) for v in p] for p in public_inputs]
+        if len({len(r) for r in rows}) != 1:
+            raise P2GpuError(-7, "every witness takes the same number of public inputs")
+        pis = _u64(np.array(rows, dtype=np.uint64).reshape(batch, len(rows[0])))
+        reports = (_WitnessReport * batch)()
+        status = np.zeros((batch, self.degree), dtype=np.uint16) if details else None
+        flags = np.zeros((batch, self.num_routed_wires, self.degree), dtype=np.uint8) if details else None
+        rc = call(pis.ctypes.data if pis.size else None, pis.shape[1], reports, status.ctypes.data if details else None,
+                  flags.ctypes.data if details else None)
+        # (-5 with every count zero is no report: the level walk in front of p2gpu_check_seeds refused the values)
+        if rc != -5 or not any(r.gate_rows_failed or r.copy_cells_failed or r.noncanonical_cells for r in reports):
+            _check(rc)
+        msg = self._lib.p2gpu_last_error().decode(errors="replace") if rc else ""
+        return [WitnessReport(reports[b], status[b] if details else None, flags[b] if details else None, msg) for b in range(batch)]
+
+    def check_witness(self, wires, public_inputs=(), details=False):
+        """``p2gpu_check_witness`` / ``_dev``: which gate rows and copy constraints the witness matrix [num_wires][degree] breaks
+        and which of its words are no canonical field elements, found on the GPU; a :class:`WitnessReport`.  `wires` as
+        :meth:`prove` takes it: numpy uint64 on the host, a torch tensor on the circuit's GPU or any object with a
+        ``__cuda_array_interface__`` there (read in place).  ``details=True`` also brings back the per-row and per-cell results."""
+        expect = self.num_wires * self.degree
+        ptr = None
+        if hasattr(wires, "data_ptr") and getattr(wires, "is_cuda", False):
+            import torch
+
+            if wires.numel() != expect or wires.element_size() != 8 or not wires.is_contiguous():
+                raise P2GpuError(-7, "wires tensor must be contiguous int64/uint64 [num_wires][degree]")
+            if wires.device.index != self.device_index():
+                raise P2GpuError(-7, f"wires tensor lives on cuda:{wires.device.index}, the circuit on cuda:{self.device_index()}")
+            torch.cuda.current_stream(wires.device).synchronize()   # (the library reads on the handle's own stream)
+            ptr = wires.data_ptr()
+        elif hasattr(wires, "__cuda_array_interface__"):
+            cai = wires.__cuda_array_interface__
+            if int(np.prod(cai["shape"])) * np.dtype(cai["typestr"]).itemsize != 8 * expect:
+                raise P2GpuError(-7, f"the device buffer must hold [num_wires={self.num_wires}][degree={self.degree}] 64-bit words")
+            ptr = cai["data"][0]
+        if ptr is not None:
+            return self._check_call(lambda pis, n_pi, rep, st, fl: self._lib.p2gpu_check_witness_dev(
+                self._h, ctypes.c_void_p(ptr), 1, pis, n_pi, rep, st, fl), 1, [public_inputs], details)[0]
+        w = _u64(wires)
+        if w.size != expect:
+            raise P2GpuError(-7, f"wires must be [num_wires={self.num_wires}][degree={self.degree}]")
+        return self._check_call(lambda pis, n_pi, rep, st, fl: self._lib.p2gpu_check_witness(
+            self._h, w.ctypes.data, pis, n_pi, rep, st, fl), 1, [public_inputs], details)[0]
+
+    def check_witness_batch(self, wires_dev, public_inputs=None, details=False):
+        """The same for a torch tensor [batch][num_wires][degree] on the circuit's GPU (the layout of
+        ``WitnessPlan.generate_batch``), `public_inputs` one list per witness; [WitnessReport]."""
+        import torch
+
+        if not (hasattr(wires_dev, "data_ptr") and getattr(wires_dev, "is_cuda", False)) or wires_dev.dim() != 3 or not wires_dev.is_contiguous() \
+                or wires_dev.element_size() != 8 or wires_dev[0].numel() != self.num_wires * self.degree:
+            raise P2GpuError(-7, "wires tensor must be contiguous int64/uint64 [batch][num_wires][degree] on the GPU")
+        if wires_dev.device.index != self.device_index():
+            raise P2GpuError(-7, f"wires tensor lives on cuda:{wires_dev.device.index}, the circuit on cuda:{self.device_index()}")
+        batch = wires_dev.shape[0]
+        pis = [()] * batch if public_inputs is None else list(public_inputs)
+        if len(pis) != batch:
+            raise P2GpuError(-7, f"{batch} lists of public inputs expected, {len(pis)} given")
+        torch.cuda.current_stream(wires_dev.device).synchronize()
+        return self._check_call(lambda p, n_pi, rep, st, fl: self._lib.p2gpu_check_witness_dev(
+            self._h, ctypes.c_void_p(wires_dev.data_ptr()), batch, p, n_pi, rep, st, fl), batch, pis, details)
+
     def fill_witness(self, wires_dev):
         """Run the gates' row-local generators on a device wire matrix (torch tensor, in place)."""
         if not (hasattr(wires_dev, "data_ptr") and getattr(wires_dev, "is_cuda", False)):
@@ -698,6 +817,19 @@ class WitnessPlan:
             except P2GpuError as e:
                 out.append(e)
         return out
+
+    def check(self, values, public_inputs=(), details=False):
+        """``p2gpu_check_seeds``: generate into the handle's own buffer, then ``CircuitData.check_witness`` on it: does the level
+        walk's output satisfy the gates and the copies?  A witness the walk itself refuses raises as :meth:`generate` does."""
+        v = self._values(values)
+        return self._cd._check_call(lambda pis, n_pi, rep, st, fl: self._lib.p2gpu_check_seeds(
+            self._h, v.ctypes.data if v.size else None, pis, n_pi, rep, st, fl), 1, [public_inputs], details)[0]
+
+    def check_batch(self, values_list, public_inputs=None, details=False):
+        """`generate_batch`, then one ``p2gpu_check_witness_dev`` over all its matrices.  Returns ([WitnessReport], the wire
+        matrices, the walk's status per member); the report of a member the walk refused describes the incomplete matrix."""
+        wires, status, _ = self.generate_batch(values_list)
+        return self._cd.check_witness_batch(wires, public_inputs, details), wires, status
 
     def prove(self, values, public_inputs=()):
         """``p2gpu_prove_seeds``: generate into the handle's own buffer, then the resident proof path."""

@@ -346,7 +346,9 @@ class CircuitBuilderFromAcirToPlonky2:
             self.witness_target_map[w] = t
         for w in sorted(set(private_parameters)):
             self._target(w)
+        self.opcode_first_row = []            # per opcode: the builder rows that existed when its translation began, then their final count (explain)
         for op in opcodes:
+            self.opcode_first_row.append(len(self.builder.rows))
             if op[0] == "assert_zero":
                 self.translate_assert_zero(*op[1:])
             elif op[0] == "sha256_compression":
@@ -364,6 +366,7 @@ class CircuitBuilderFromAcirToPlonky2:
                 EcdsaSecp256k1Translator(self, hashed_message, pkx, pky, signature, output).translate()
             else:
                 raise NotImplementedError(op[0])
+        self.opcode_first_row.append(len(self.builder.rows))      # (the rows build() adds behind them are no opcode's)
 
     def build(self, acir_witness):
         """acir_witness: {witness index: value} for every witness the solver would hand over (at least the
@@ -389,6 +392,17 @@ class CircuitBuilderFromAcirToPlonky2:
     def blob(self):
         """The circuit blob alone (build() without the witness)."""
         return self.builder.blob()
+
+    def explain(self, report):
+        """``CircuitBuilder.explain`` of a WitnessReport, with the ACIR opcode whose translation created the failing row.  (A row
+        that holds several operations is shared: its later operations may serve later opcodes)"""
+        text = self.builder.explain(report)
+        if report.first_gate is not None and report.first_gate[0] < len(self.builder.rows):
+            first = getattr(self, "opcode_first_row", [])
+            i = sum(1 for r in first if r <= report.first_gate[0]) - 1
+            if 0 <= i < len(first) - 1:
+                text += "; the row was created by ACIR opcode %d" % i
+        return text
 
     def public_inputs(self):
         """Values of the registered public inputs, in order (after build): what p2gpu_prove takes beside the wires."""

@@ -30,6 +30,9 @@
  *   p2gpu_generate_witness_batch
  *                          <- the same for many value sets of one circuit at once (the reference has no counterpart: it
  *                             calls `prove` once per witness)
+ *   p2gpu_check_witness / p2gpu_check_witness_dev / p2gpu_check_seeds
+ *                          <- the panic of plonky2's witness generator that names a partition (iop/generator.rs), for a matrix
+ *                             that arrives complete: which gate row and which copy constraint a witness breaks
  *   p2gpu_last_error       <- the `anyhow::Error` text the reference unwraps
  *   p2gpu_ifft_batch / p2gpu_lde_batch / p2gpu_commit_values
  *                          <- plonky2 PolynomialValues::ifft,
@@ -316,6 +319,50 @@ int p2gpu_generate_witness_batch(p2gpu_witness_plan *p, const uint64_t *seed_val
  * holds the time the witness took. */
 int p2gpu_prove_seeds(p2gpu_witness_plan *p, const uint64_t *seed_values, const uint64_t *public_inputs, uint32_t n_pi,
                       uint8_t *proof_out, size_t *proof_len, p2gpu_timings *opt_timings);
+
+/* ---- why a witness is wrong: the gate rows and copy constraints it breaks, found on the GPU ----
+ * The prover's self-check answers P2GPU_E_UNSATISFIED after the commitments and names nothing; these entry points evaluate the
+ * circuit on the n base rows of a wire matrix and say where it fails (the reference's user gets a panic of plonky2's witness
+ * generator that names a partition; there is no counterpart for a matrix that arrives complete).  All of it is decided on the
+ * device, per witness, from the handle's own tables:
+ *   gates      row r fails when a constraint of gates[row_gate[r]] -- unfiltered, with the row's gate constants and the
+ *              Poseidon hash of the witness's public inputs, the prover's `public_inputs_hash` -- is non-zero; constraints are
+ *              numbered in the order the gate emits them (csrc/gates.hpp eval_gate, the reference's order)
+ *   copies     routed cell x is flagged when its value differs from the value of sigma(x), sigma decoded from the handle's
+ *              sigma columns (the decode of the witness plan); a cell sigma maps to itself is never flagged
+ *   canonicity a word >= p anywhere in the matrix is counted and named; the two checks above use it reduced once (v - p)
+ * Cells are ordered by the key col << degree_bits | row, as sigma is laid out.  Witnesses of a batch do not affect each other.
+ * The scratch (sigma's partner cells, the per-row and per-cell results, the counters) is allocated per call and released
+ * before it returns; nothing is kept on the handle. */
+typedef struct {
+  uint64_t gate_rows_failed;    /* rows with at least one non-zero constraint */
+  uint64_t copy_cells_failed;   /* routed cells x with value(x) != value(sigma(x)) */
+  uint64_t noncanonical_cells;  /* cells of the whole matrix with a word >= p */
+  uint32_t gate_row, gate_index, gate_kind, constraint;  /* lowest failing row; lowest failing constraint in it */
+  uint64_t constraint_value;
+  uint32_t copy_cell[2], copy_partner[2];   /* (row, col): the flagged cell with the lowest key col << d | row, and sigma of it */
+  uint64_t copy_values[2];                  /* the matrix's words in those two cells */
+  uint32_t noncanonical_cell[2];            /* lowest key */
+} p2gpu_witness_report;                      /* the "first" fields are UINT32_MAX / 0 where the count is 0 */
+/* wires_dev: device, [batch][num_wires][n] (the layout of p2gpu_generate_witness_batch), only read.  Returns P2GPU_OK when every
+ * report is clean; P2GPU_E_UNSATISFIED when one is not, p2gpu_last_error then words the first finding of the lowest failing
+ * witness -- gates before copies before canonicity: "row 3 (U32SubtractionGate, gate 6): constraint 2 = 0x...",
+ * "copy (2, 8) = 0x... != (3, 0) = 0x..." with cells as (row, col), "cell (5, 1) = 0x... is not a canonical field element" --
+ * behind "witness <b> of the batch: " when batch > 1; P2GPU_E_ARG, decided before any device call: a null handle, matrix or
+ * reports, batch == 0, n_pi different from the circuit's (or a public input >= p), a verifier-only handle, a device group.  The
+ * reports are complete either way. */
+int p2gpu_check_witness_dev(p2gpu_circuit *c, const uint64_t *wires_dev, size_t batch,
+                            const uint64_t *public_inputs /* host, [batch][n_pi] */, uint32_t n_pi,
+                            p2gpu_witness_report *reports /* host, [batch] */,
+                            uint16_t *row_status /* host, [batch][n]: first failing constraint of the row, 0xFFFF = none; may be NULL */,
+                            uint8_t *cell_flags /* host, [batch][num_routed_wires][n]: 1 = flagged copy cell; may be NULL */);
+/* the same for one matrix in host memory: an upload, then the device form with batch == 1 */
+int p2gpu_check_witness(p2gpu_circuit *c, const uint64_t *wires /* host, [num_wires][n] */, const uint64_t *public_inputs,
+                        uint32_t n_pi, p2gpu_witness_report *report, uint16_t *row_status, uint8_t *cell_flags);
+/* p2gpu_generate_witness into the handle's own buffer (as p2gpu_prove_seeds does), then the check of that matrix.  A witness the
+ * level walk already refuses comes back with p2gpu_generate_witness's code and words, the report untouched. */
+int p2gpu_check_seeds(p2gpu_witness_plan *p, const uint64_t *seed_values, const uint64_t *public_inputs, uint32_t n_pi,
+                      p2gpu_witness_report *report, uint16_t *row_status, uint8_t *cell_flags);
 
 /* ---- N2: prover-side precompute of `builder.build::<C>()` (host code; circuit_translation/mod.rs:80-82) ----
  * From the gate instances and the copy constraints: selector columns + groups (gates/selectors.rs), the
