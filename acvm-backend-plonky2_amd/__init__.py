@@ -14,6 +14,7 @@ from .prover import (  # noqa: F401
     CircuitData,
     WitnessPlan,
     WitnessReport,
+    VerifyReport,
     build_blob,
     VerifierCircuitData,
     ProofWithPublicInputs,

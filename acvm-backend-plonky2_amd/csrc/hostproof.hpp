@@ -1,8 +1,9 @@
-// hostproof.hpp -- host-side pieces shared by the verifier (verify.hip) and the proof
-// (de)compression (proofio.hip): a bounds-checked byte cursor, KeccakHash<25> leaf / path hashing,
-// alpha-power reduction and the closed-form coset interpolation of a FRI fold.
+// hostproof.hpp -- host-side pieces shared by the verifier (verify.hip, verifydev.hip) and the proof
+// (de)compression (proofio.hip): a bounds-checked byte cursor,
+// alpha-power reduction, the coset interpolation of a FRI fold and the handle's view for the verifier core (verifycore.hpp).
 #pragma once
 #include "circuit.hpp"
+#include "verifycore.hpp"
 
 namespace p2 {
 
@@ -50,51 +51,30 @@ struct Cursor {
   }
 };
 
-// hash/merkle_proofs.rs verify_merkle_proof_to_cap
-inline bool merkle_path_ok(const gl_t *leaf, size_t n, size_t index, const std::vector<dig_t> &siblings,
-                    const std::vector<dig_t> &cap) {
-  dig_t cur = leaf_digest(leaf, n);
-  for (const dig_t &s : siblings) {
-    cur = (index & 1) ? node_digest(s, cur) : node_digest(cur, s);
-    index >>= 1;
-  }
-  return index < cap.size() && dig_eq(cur, cap[index]);
-}
-
-// sum_j alpha^j v_j
-template <class It>
-ext_t reduce_with_powers(It first, It last, ext_t alpha) {
-  ext_t acc = ext_from(0);
-  while (last != first) {
-    --last;
-    acc = ext_add(ext_mul(acc, alpha), *last);
-  }
-  return acc;
-}
-
-// Value at beta of the degree < a interpolant through (s g^j, y_j), j < a = 2^ab, g of order a.
-// The nodes are the roots of X^a - s^a, so the barycentric weights are x_j / (a s^a):
-//   P(beta) = (beta^a - s^a) / (a s^a) * sum_j y_j x_j / (beta - x_j).
-// (fri/verifier.rs compute_evaluation does the same interpolation with a generic routine.)
+// the closed-form coset interpolation of a FRI fold (verifycore.hpp interpolate_coset_fn) on an array of values
 inline ext_t interpolate_coset(gl_t s, unsigned ab, const ext_t *y_natural, ext_t beta) {
-  const uint32_t a = 1u << ab;
-  const gl_t g = gl_root(ab);
-  gl_t sa = s;
-  ext_t ba = beta;
-  for (unsigned i = 0; i < ab; i++) {
-    sa = gl_sqr(sa);
-    ba = ext_mul(ba, ba);
-  }
-  ext_t acc = ext_from(0);
-  gl_t x = s;
-  for (uint32_t j = 0; j < a; j++) {
-    const ext_t diff = ext_sub(beta, ext_from(x));
-    if (diff.c0 == 0 && diff.c1 == 0) return y_natural[j];
-    acc = ext_add(acc, ext_mul(ext_scale(y_natural[j], x), ext_inv(diff)));
-    x = gl_mul(x, g);
-  }
-  const gl_t scale = gl_inv(gl_mul((gl_t)a, sa));
-  return ext_mul(ext_scale(ext_sub(ba, ext_from(sa)), scale), acc);
+  return vc::interpolate_coset_fn(s, ab, [&](uint32_t j) { return y_natural[j]; }, beta);
 }
+
+// the verifier's share of a handle as the core takes it (host pointers, valid while the handle lives)
+inline vc::CircuitView view_of(const p2gpu_circuit *c) {
+  vc::CircuitView v;
+  memset(&v, 0, sizeof v);
+  v.d = c->d; v.W = c->W; v.R = c->R; v.NC = c->NC; v.num_selectors = c->num_selectors; v.K = c->K; v.QF = c->QF; v.PP = c->PP;
+  v.nchunks = c->nchunks; v.rate_bits = c->rate_bits; v.cap_h = c->cap_h; v.pow_bits = c->pow_bits; v.num_queries = c->num_queries;
+  v.n_steps = c->n_steps;
+  for (int i = 0; i < 8; i++) v.arity[i] = c->arity[i];
+  v.num_gates = c->num_gates; v.num_pi = c->num_pi; v.max_gate_constraints = c->max_gate_constraints; v.hasher = c->hasher;
+  v.gates = c->gates.data(); v.k_is = c->k_is.data(); v.cs_cap = c->cs.cap.data(); v.prc = c->poseidon_rc_gate;
+  v.circuit_digest = c->circuit_digest;
+  return v;
+}
+
+// ---- verify.hip: what p2gpu_verify_batch_host and p2gpu_verify_batch (verifydev.hip) share ----
+// the refusals that need no device (P2GPU_E_ARG; 0: the call may go on)
+int verify_batch_args(const p2gpu_circuit *c, const uint8_t *proofs, const size_t *offsets, size_t batch, const p2gpu_verify_report *reports);
+void verify_report_fill(p2gpu_verify_report *r, const vc::Verdict &v);
+int verify_batch_finish(size_t batch, const size_t *offsets, const vc::Layout &L, const p2gpu_verify_report *reports);
+vc::Verdict verify_one_host(const vc::CircuitView &v, const vc::Layout &L, const uint8_t *proof, size_t len, std::vector<ext_t> &terms);
 
 }  // namespace p2

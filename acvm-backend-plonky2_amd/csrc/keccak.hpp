@@ -227,6 +227,7 @@ P2_HD KeccakCoopLane keccak_coop_lane(uint32_t lane) {
   return c;
 }
 // (lo, hi) = this lane's 64-bit word of the state; lanes 25..31 of a half carry garbage nobody reads
+#if defined(__HIPCC__)  // (a plain C++ compiler includes this header for the host forms: csrc/tests/verifycore_check.cpp)
 __device__ __forceinline__ void keccak_f1600_coop(uint32_t &lo, uint32_t &hi, const KeccakCoopLane &c) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr uint64_t RC[24] = {
@@ -257,6 +258,7 @@ __device__ __forceinline__ void keccak_f1600_coop(uint32_t &lo, uint32_t &hi, co
   (void)lo, (void)hi, (void)c;  // host pass of hipcc: parsed only
 #endif
 }
+#endif
 
 // BytesHash<25>::to_vec: 7-byte little-endian chunks -> 4 field elements
 P2_HD void dig_to_elems(const dig_t &d, gl_t out[4]) {

@@ -1,9 +1,12 @@
-// verify.hip -- proof verification, host code only (no kernel in this file).
+// verify.hip -- proof verification on the host (no kernel in this file): the verifier-only handle, the verifier key, and the
+// host entry points of the verifier core -- p2gpu_verify (one proof), p2gpu_verify_batch_host (a plain loop over a batch) and
+// p2gpu_verify_reason (the wording of a report).  The checks themselves are in verifycore.hpp, written once for the host and
+// the device; p2gpu_verify_batch runs the same functions as kernels (verifydev.hip).
 //
 // The reference's `verify` action (plonky2-backend/src/actions/verify_action.rs:11-17,
 // VerifierCircuitData::verify) and the assertion every in-tree test ends with
 // (`circuit_data.verify(proof)`, e.g. circuit_translation/tests/factories/utils.rs:26-27) check a
-// proof in a few milliseconds of scalar work; so does this file -- it is what SURVEY.md 8(b) calls
+// proof in a few milliseconds of scalar work; so does p2gpu_verify -- it is what SURVEY.md 8(b) calls
 // `p2gpu-verify`, and it needs no GPU: a handle made by p2gpu_verifier_create holds only the
 // verifier's share of the circuit (parameters, gate table, constants_sigmas cap, circuit digest,
 // k_is) -- the counterpart of the VK file written by actions/write_vk_action.rs:65-81.
@@ -16,91 +19,71 @@
 // (tests/test_reference_proofs.py::test_product_verifier_accepts_reference_proof).
 #include "hostproof.hpp"
 #include "prover_internal.hpp"
-#include <cstdarg>
+#include <algorithm>
 #include <cstdio>
 
 using namespace p2;
 
 namespace p2 {
 
-namespace {
-struct CollectOut {
-  std::vector<ext_t> *v;
-  void emit(ext_t c) { v->push_back(c); }
-};
-}  // namespace
-
-// The verifier's plonk identity at zeta, on the opened values (plonk/verifier.rs
-// verify_with_challenges + vanishing_poly.rs eval_vanishing_poly over the extension):
-//   vanishing_c(zeta) == Z_H(zeta) * sum_m zeta^(n m) * t_{c,m}(zeta)        for each challenge c.
+// The verifier's plonk identity at zeta, on the opened values (verifycore.hpp plonk_identity_core).
 // `op` = constants, sigmas, wires, zs, partial products, quotient chunks, then zs_next.
 // It fails exactly when the witness does not satisfy the circuit (with overwhelming
 // probability); upstream only finds that out in its witness generator, which stays in Rust, so
 // the prover runs this as its self-check too.
 bool plonk_identity_holds(const p2gpu_circuit *c, const std::vector<ext_t> &op, const gl_t *betas, const gl_t *gammas,
                           const gl_t *alphas, ext_t zeta, const gl_t pih[4]) {
-  const uint32_t K = c->K, R = c->R, W = c->W, NC = c->NC, QF = c->QF, PP = c->PP, nchunks = c->nchunks;
-  const uint32_t ncs = NC + R, nzp = K * (1 + PP), nall = ncs + W + nzp + K * QF;
-  const ext_t *o_const = op.data(), *o_sig = o_const + NC, *o_wires = o_sig + R, *o_zs = o_wires + W;
-  const ext_t *o_pp = o_zs + K, *o_quot = o_pp + K * PP, *o_zs_next = op.data() + nall;
-  ext_t zn = zeta;
-  for (uint32_t i = 0; i < c->d; i++) zn = ext_mul(zn, zn);
-  const ext_t z_h = ext_sub(zn, ext_from(1));
-  const ext_t l0 = ext_mul(z_h, ext_inv(ext_scale(ext_sub(zeta, ext_from(1)), (gl_t)c->n)));
-  std::vector<ext_t> terms;
-  for (uint32_t k = 0; k < K; k++) terms.push_back(ext_mul(l0, ext_sub(o_zs[k], ext_from(1))));
-  for (uint32_t k = 0; k < K; k++)
-    for (uint32_t m = 0; m < nchunks; m++) {
-      const ext_t prev = m == 0 ? o_zs[k] : o_pp[k * PP + m - 1];
-      const ext_t next = m == nchunks - 1 ? o_zs_next[k] : o_pp[k * PP + m];
-      ext_t np = ext_from(1), dp = ext_from(1);
-      for (uint32_t j = m * QF; j < (m + 1) * QF && j < R; j++) {
-        const ext_t s_id = ext_scale(zeta, c->k_is[j]);
-        np = ext_mul(np, ext_add(ext_add(o_wires[j], ext_scale(s_id, betas[k])), ext_from(gammas[k])));
-        dp = ext_mul(dp, ext_add(ext_add(o_wires[j], ext_scale(o_sig[j], betas[k])), ext_from(gammas[k])));
-      }
-      terms.push_back(ext_sub(ext_mul(prev, np), ext_mul(next, dp)));
+  const vc::CircuitView v = view_of(c);
+  std::vector<ext_t> terms(vc::identity_terms(v));
+  return vc::plonk_identity_at(v, vc::Openings{op.data(), nullptr, 0, 0, 0, 0}, vc::Strided<ext_t>{terms.data(), 1}, betas, gammas, alphas, zeta, pih);
+}
+
+// ---- what the batch entry points share (p2gpu_verify_batch_host below, p2gpu_verify_batch in verifydev.hip) ----
+int verify_batch_args(const p2gpu_circuit *c, const uint8_t *proofs, const size_t *offsets, size_t batch, const p2gpu_verify_report *reports) {
+  if (!c || !proofs || !offsets || !reports || batch == 0) return P2GPU_E_ARG;
+  for (size_t b = 0; b < batch; b++)
+    if (offsets[b + 1] < offsets[b]) {
+      set_err("p2gpu_verify_batch: offsets decrease at proof %zu", b);
+      return P2GPU_E_ARG;
     }
-  std::vector<ext_t> gate_terms(c->max_gate_constraints, ext_from(0)), cons;
-  ext_t pih_e[4];
-  for (int i = 0; i < 4; i++) pih_e[i] = ext_from(pih[i]);
-  auto Wf = [&](uint32_t col) { return o_wires[col]; };
-  auto LC = [&](uint32_t i) { return o_const[c->num_selectors + i]; };
-  for (uint32_t gi = 0; gi < c->num_gates; gi++) {
-    const GateDesc &g = c->gates[gi];
-    if (!g.num_constraints) continue;
-    const ext_t f = gate_filter<ExtOps>(g, gi, c->num_selectors, o_const[g.sel_index]);
-    cons.clear();
-    CollectOut out{&cons};
-    eval_gate<ExtOps, true>(g, Wf, LC, pih_e, c->poseidon_rc_gate, out);
-    for (size_t k = 0; k < cons.size() && k < gate_terms.size(); k++)
-      gate_terms[k] = ext_add(gate_terms[k], ext_mul(f, cons[k]));
+  if (!c->group.empty()) {
+    set_err("p2gpu_verify_batch: a device group verifies nothing as a group: use a plain handle (p2gpu_circuit_create_on) or a verifier-only one");
+    return P2GPU_E_ARG;
   }
-  terms.insert(terms.end(), gate_terms.begin(), gate_terms.end());
-  for (uint32_t k = 0; k < K; k++) {
-    ext_t van = ext_from(0), qz = ext_from(0);
-    for (size_t t = terms.size(); t-- > 0;) van = ext_add(ext_scale(van, alphas[k]), terms[t]);
-    for (uint32_t m = QF; m-- > 0;) qz = ext_add(ext_mul(qz, zn), o_quot[k * QF + m]);
-    if (!ext_eq(van, ext_mul(z_h, qz))) return false;
+  if (c->cs.cap.size() != (size_t)1 << c->cap_h) return P2GPU_E_ARG;
+  return 0;
+}
+
+void verify_report_fill(p2gpu_verify_report *r, const vc::Verdict &v) {
+  r->status = v.reason ? P2GPU_E_VERIFY : P2GPU_OK;
+  r->reason = v.reason;
+  r->query = v.query;
+  r->index = v.index;
+}
+
+// p2gpu_last_error for the lowest failing proof, in p2gpu_verify's words; the batch's return code
+int verify_batch_finish(size_t batch, const size_t *offsets, const vc::Layout &L, const p2gpu_verify_report *reports) {
+  for (size_t b = 0; b < batch; b++) {
+    const p2gpu_verify_report &r = reports[b];
+    if (r.status == P2GPU_OK) continue;
+    char text[400], who[48] = "";
+    if (r.reason == vc::VR_LENGTH) vc::reason_text(r.reason, offsets[b + 1] - offsets[b], L.want, text, sizeof text);
+    else vc::reason_text(r.reason, r.query, r.index, text, sizeof text);
+    if (batch > 1) snprintf(who, sizeof who, "proof %zu of the batch: ", b);
+    set_err("%sproof rejected: %s", who, text);
+    return P2GPU_E_VERIFY;
   }
-  return true;
+  return P2GPU_OK;
+}
+
+vc::Verdict verify_one_host(const vc::CircuitView &v, const vc::Layout &L, const uint8_t *proof, size_t len, std::vector<ext_t> &terms) {
+  gl_t sponge[12];
+  vc::HeadRecord rec;
+  terms.resize(vc::identity_terms(v));
+  return v.hasher ? vc::verify_one<1>(v, L, proof, len, sponge, terms.data(), &rec) : vc::verify_one<0>(v, L, proof, len, sponge, terms.data(), &rec);
 }
 
 }  // namespace p2
-
-namespace {
-
-int reject(const char *fmt, ...) {
-  char buf[400];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  set_err("proof rejected: %s", buf);
-  return P2GPU_E_VERIFY;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -178,163 +161,40 @@ int p2gpu_circuit_export_vk(const p2gpu_circuit *c, uint8_t *out, size_t *len) t
 
 int p2gpu_verify(const p2gpu_circuit *c, const uint8_t *proof, size_t len) try {
   if (!c || !proof) return P2GPU_E_ARG;
-  use_hasher(c);
-  const uint32_t K = c->K, R = c->R, W = c->W, NC = c->NC, QF = c->QF, PP = c->PP, d = c->d;
-  const uint32_t ncs = NC + R, nzp = K * (1 + PP), nq = K * QF, nall = ncs + W + nzp + nq;
-  const unsigned lgN = d + c->rate_bits;
-  const size_t ncap = (size_t)1 << c->cap_h;
-  if (c->cs.cap.size() != ncap) return P2GPU_E_ARG;
-
-  // ---- 1. shape: everything but the queries has a fixed position ----
-  Cursor in{proof, len};
-  std::vector<dig_t> wires_cap, zs_cap, quot_cap;
-  in.digests(wires_cap, ncap);
-  in.digests(zs_cap, ncap);
-  in.digests(quot_cap, ncap);
-  // opening set as serialised: constants, sigmas, wires, zs, zs_next, partial products, quotient
-  std::vector<ext_t> op(nall + K);  // kept in the prover's order: ..., zs, pp, quotient | zs_next
-  for (uint32_t j = 0; j < ncs + W + K; j++) op[j] = in.ext();
-  for (uint32_t k = 0; k < K; k++) op[nall + k] = in.ext();
-  for (uint32_t j = ncs + W + K; j < nall; j++) op[j] = in.ext();
-  std::vector<std::vector<dig_t>> step_caps(c->n_steps);
-  for (auto &sc : step_caps) in.digests(sc, ncap);
-  if (!in.ok) return reject("truncated or non-canonical header (caps / openings)");
-  const uint32_t oracle_cols[4] = {ncs, W, nzp, nq};
-  size_t query_bytes = 0, final_len = c->n;
-  const size_t hb = hh_bytes();
-  for (int o = 0; o < 4; o++) query_bytes += 8 * (size_t)oracle_cols[o] + 1 + hb * (size_t)(lgN - c->cap_h);
-  {
-    unsigned lg = lgN;
-    for (uint32_t s = 0; s < c->n_steps; s++) {
-      const unsigned ab = c->arity[s];
-      if (ab < 1 || ab > MAX_ARITY_BITS || lg < ab + c->cap_h || (final_len >> ab) == 0) return reject("bad reduction arity in circuit");
-      lg -= ab;
-      final_len >>= ab;
-      query_bytes += ((size_t)16 << ab) + 1 + hb * (size_t)(lg - c->cap_h);
-    }
-  }
-  const size_t queries_at = in.at;
-  const size_t tail_at = queries_at + query_bytes * c->num_queries;
-  const size_t want = tail_at + 16 * final_len + 8 + 8 * (size_t)c->num_pi;
-  if (want != len) return reject("length %zu, expected %zu for this circuit", len, want);
-  in.at = tail_at;
-  std::vector<ext_t> final_poly(final_len);
-  for (auto &e : final_poly) e = in.ext();
-  const uint64_t pow_witness = in.felt();  // canonical, like every other field element (upstream reduces it; a non-canonical encoding is not a second valid proof here)
-  std::vector<gl_t> pis(c->num_pi);
-  for (auto &v : pis) v = in.felt();
-  if (!in.ok) return reject("non-canonical field element in final polynomial / public inputs");
-
-  // ---- 2. transcript (plonk/get_challenges.rs; order: SURVEY.md C.4) ----
-  gl_t pih[4];
-  poseidon_hash_no_pad_host(pis.data(), pis.size(), pih, c->poseidon_rc);
-  Challenger ch;
-  ch.observe_digest(c->circuit_digest);
-  for (int i = 0; i < 4; i++) ch.observe(pih[i]);
-  ch.observe_cap(wires_cap);
-  gl_t betas[2], gammas[2], alphas[2];
-  for (uint32_t k = 0; k < K; k++) betas[k] = ch.get();
-  for (uint32_t k = 0; k < K; k++) gammas[k] = ch.get();
-  ch.observe_cap(zs_cap);
-  for (uint32_t k = 0; k < K; k++) alphas[k] = ch.get();
-  ch.observe_cap(quot_cap);
-  const ext_t zeta = ch.get_ext();
-  for (uint32_t j = 0; j < nall + K; j++) ch.observe_ext(op[j]);
-  const ext_t alpha = ch.get_ext();
-  std::vector<ext_t> fold_betas(c->n_steps);
-  for (uint32_t s = 0; s < c->n_steps; s++) {
-    ch.observe_cap(step_caps[s]);
-    fold_betas[s] = ch.get_ext();
-  }
-  for (auto &e : final_poly) ch.observe_ext(e);
-  ch.observe(pow_witness);
-  const gl_t pow_response = ch.get();
-  std::vector<size_t> qidx(c->num_queries);
-  for (auto &x : qidx) x = (size_t)(ch.get() & (c->N - 1));  // N is a power of two: same as % N
-
-  // ---- 3. plonk identity at zeta ----
-  {
-    ext_t zn = zeta;
-    for (uint32_t i = 0; i < d; i++) zn = ext_mul(zn, zn);
-    if (zn.c0 == 1 && zn.c1 == 0) return reject("zeta lies in the subgroup");
-  }
-  if (!plonk_identity_holds(c, op, betas, gammas, alphas, zeta, pih))
-    return reject("vanishing(zeta) != Z_H(zeta) * quotient(zeta)");
-
-  // ---- 4. FRI ----
-  if (c->pow_bits && (pow_response >> (64 - c->pow_bits)) != 0) return reject("proof-of-work response has too few leading zeros");
-  const ext_t opened0 = reduce_with_powers(op.begin(), op.begin() + nall, alpha);        // batch at zeta
-  const ext_t opened1 = reduce_with_powers(op.begin() + nall, op.end(), alpha);          // Z at g zeta
-  const ext_t g_zeta = ext_scale(zeta, gl_root(d));
-  const ext_t alpha_k = ext_pow(alpha, K);
-  const std::vector<dig_t> *init_caps[4] = {&c->cs.cap, &wires_cap, &zs_cap, &quot_cap};
-  std::vector<gl_t> row(nall);
-  std::vector<dig_t> sib;
-  in.at = queries_at;
-  for (uint32_t qi = 0; qi < c->num_queries; qi++) {
-    const size_t x0 = qidx[qi];
-    // initial oracles: the row of each tree at leaf x0
-    size_t t = 0;
-    for (int o = 0; o < 4; o++) {
-      const uint8_t *leaf = in.take(8 * (size_t)oracle_cols[o]);
-      const uint8_t *plen = in.take(1);
-      if (!leaf || !plen || *plen != lgN - c->cap_h) return reject("query %u: malformed initial opening %d", qi, o);
-      memcpy(&row[t], leaf, 8 * (size_t)oracle_cols[o]);
-      for (uint32_t j = 0; j < oracle_cols[o]; j++)
-        if (row[t + j] >= GL_P) return reject("query %u: non-canonical leaf element", qi);
-      in.digests(sib, *plen);
-      if (!in.ok || !merkle_path_ok(&row[t], oracle_cols[o], x0, sib, *init_caps[o]))
-        return reject("query %u: Merkle path of initial oracle %d does not lead to its cap", qi, o);
-      t += oracle_cols[o];
-    }
-    // the queried point: leaf x0 holds natural LDE row bitrev(x0), i.e. g w_N^bitrev(x0), g = GL_GEN
-    size_t e = 0;
-    for (unsigned b = 0; b < lgN; b++) e |= ((x0 >> b) & 1) << (lgN - 1 - b);
-    unsigned lg = lgN;
-    gl_t shift = GL_GEN;
-    const gl_t x_pt = gl_mul(shift, gl_pow(gl_root(lg), e));
-    // fri_combine_initial: (F0(x) - F0(zeta)) / (x - zeta) * alpha^K + (F1(x) - F1(g zeta)) / (x - g zeta)
-    ext_t acc0 = ext_from(0), acc1 = ext_from(0);
-    for (size_t j = nall; j-- > 0;) acc0 = ext_add(ext_mul(acc0, alpha), ext_from(row[j]));
-    for (size_t j = K; j-- > 0;) acc1 = ext_add(ext_mul(acc1, alpha), ext_from(row[ncs + W + j]));
-    ext_t cur = ext_mul(ext_sub(acc0, opened0), ext_inv(ext_sub(ext_from(x_pt), zeta)));
-    cur = ext_add(ext_mul(cur, alpha_k), ext_mul(ext_sub(acc1, opened1), ext_inv(ext_sub(ext_from(x_pt), g_zeta))));
-    // commit-phase folds
-    size_t x = x0;
-    for (uint32_t s = 0; s < c->n_steps; s++) {
-      const unsigned ab = c->arity[s];
-      const uint32_t a = 1u << ab;
-      ext_t y_leaf[1 << MAX_ARITY_BITS], y_nat[1 << MAX_ARITY_BITS];
-      gl_t flat[128];
-      for (uint32_t i = 0; i < a; i++) {
-        y_leaf[i] = in.ext();
-        flat[2 * i] = y_leaf[i].c0;
-        flat[2 * i + 1] = y_leaf[i].c1;
-      }
-      const uint8_t *plen = in.take(1);
-      if (!in.ok || !plen || *plen != lg - ab - c->cap_h) return reject("query %u: malformed fold step %u", qi, s);
-      in.digests(sib, *plen);
-      const size_t leaf_index = x >> ab, within = x & (a - 1);
-      if (!ext_eq(y_leaf[within], cur)) return reject("query %u: fold step %u does not continue the previous value", qi, s);
-      if (!in.ok || !merkle_path_ok(flat, 2 * (size_t)a, leaf_index, sib, step_caps[s]))
-        return reject("query %u: Merkle path of fold step %u does not lead to its cap", qi, s);
-      // leaf slot i holds the point s g^bitrev(i), s = shift * w^(e mod 2^(lg-ab))
-      for (uint32_t i = 0; i < a; i++) y_nat[bitrev32(i, ab)] = y_leaf[i];
-      e &= ((size_t)1 << (lg - ab)) - 1;
-      const gl_t s_pt = gl_mul(shift, gl_pow(gl_root(lg), e));
-      cur = interpolate_coset(s_pt, ab, y_nat, fold_betas[s]);
-      for (unsigned i = 0; i < ab; i++) shift = gl_sqr(shift);
-      lg -= ab;
-      x = leaf_index;
-    }
-    // final polynomial at the folded point
-    const gl_t x_last = gl_mul(shift, gl_pow(gl_root(lg), e));
-    ext_t fe = ext_from(0);
-    for (size_t i = final_len; i-- > 0;) fe = ext_add(ext_scale(fe, x_last), final_poly[i]);
-    if (!ext_eq(fe, cur)) return reject("query %u: final polynomial disagrees with the folded value", qi);
-  }
-  if (!in.ok || in.at != tail_at) return reject("query section has the wrong size");
-  return P2GPU_OK;
+  if (c->cs.cap.size() != (size_t)1 << c->cap_h) return P2GPU_E_ARG;
+  const vc::CircuitView v = view_of(c);
+  const vc::Layout L = vc::make_layout(v);
+  std::vector<ext_t> terms;
+  const vc::Verdict vd = verify_one_host(v, L, proof, len, terms);
+  if (!vd.reason) return P2GPU_OK;
+  char text[400];
+  if (vd.reason == vc::VR_LENGTH) vc::reason_text(vd.reason, len, L.want, text, sizeof text);
+  else vc::reason_text(vd.reason, vd.query, vd.index, text, sizeof text);
+  set_err("proof rejected: %s", text);
+  return P2GPU_E_VERIFY;
 } P2GPU_CATCH
+
+// the core in a plain loop on the calling thread: no device is touched
+int p2gpu_verify_batch_host(const p2gpu_circuit *c, const uint8_t *proofs, const size_t *offsets, size_t batch, p2gpu_verify_report *reports) try {
+  if (int rc = verify_batch_args(c, proofs, offsets, batch, reports)) return rc;
+  const vc::CircuitView v = view_of(c);
+  const vc::Layout L = vc::make_layout(v);
+  std::vector<ext_t> terms;
+  for (size_t b = 0; b < batch; b++) {
+    const size_t len = offsets[b + 1] - offsets[b];
+    verify_report_fill(&reports[b], verify_one_host(v, L, proofs + offsets[b], len, terms));
+  }
+  return verify_batch_finish(batch, offsets, L, reports);
+} P2GPU_CATCH
+
+int p2gpu_verify_reason(const p2gpu_verify_report *r, char *out, size_t cap) {
+  if (!r || !out || cap == 0) return P2GPU_E_ARG;
+  const int n = vc::reason_text(r->reason, r->query, r->index, out, cap);
+  if (n < 0 || (size_t)n >= cap) {
+    set_err("p2gpu_verify_reason: the text needs %d bytes", n + 1);
+    return P2GPU_E_BUFFER;
+  }
+  return P2GPU_OK;
+}
 
 }  // extern "C"

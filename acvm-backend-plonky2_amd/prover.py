@@ -59,6 +59,30 @@ class _WitnessReport(ctypes.Structure):
     ]
 
 
+class _VerifyReport(ctypes.Structure):
+    """p2gpu_verify_report"""
+    _fields_ = [("status", ctypes.c_int32), ("reason", ctypes.c_uint32), ("query", ctypes.c_uint32), ("index", ctypes.c_uint32)]
+
+
+class VerifyReport:
+    """The verdict on one proof of a batch (``p2gpu_verify_batch``).  `ok`; `reason`: the P2GPU_VR_* code of the check that
+    failed (0: none); `query`, `index`: the query and the initial oracle or fold step the reason names, None where it names
+    none (for a wrong length: the length given and the length the circuit fixes); `message`: the words of ``verify``'s error
+    behind "proof rejected: " ("accepted" for a valid proof)."""
+
+    def __init__(self, raw, message):
+        self.ok, self.reason, self.message = raw.status == 0, int(raw.reason), message
+        self.query = None if raw.query == 0xFFFFFFFF else int(raw.query)
+        self.index = None if raw.index == 0xFFFFFFFF else int(raw.index)
+
+    def __eq__(self, other):
+        return isinstance(other, VerifyReport) and (self.ok, self.reason, self.query, self.index, self.message) == \
+            (other.ok, other.reason, other.query, other.index, other.message)
+
+    def __repr__(self):
+        return "VerifyReport(ok)" if self.ok else "VerifyReport(reason=%d, query=%r, index=%r, %r)" % (self.reason, self.query, self.index, self.message)
+
+
 GATE_KIND_NAMES = ("NoopGate", "ConstantGate", "PublicInputGate", "ArithmeticGate", "BaseSumGate", "RandomAccessGate", "PoseidonGate",
                    "U32ArithmeticGate", "U32AddManyGate", "U32SubtractionGate", "U32RangeCheckGate", "ComparisonGate")
 
@@ -161,6 +185,9 @@ def load_library():
     lib.p2gpu_check_witness.argtypes = [vp, vp, vp, ctypes.c_uint32, vp, vp, vp]
     lib.p2gpu_check_seeds.argtypes = [vp, vp, vp, ctypes.c_uint32, vp, vp, vp]
     lib.p2gpu_verify.argtypes = [vp, u8p, sz]
+    lib.p2gpu_verify_batch.argtypes = [vp, u8p, vp, sz, vp]
+    lib.p2gpu_verify_batch_host.argtypes = [vp, u8p, vp, sz, vp]
+    lib.p2gpu_verify_reason.argtypes = [vp, ctypes.c_char_p, sz]
     lib.p2gpu_circuit_export_vk.argtypes = [vp, u8p, ctypes.POINTER(sz)]
     lib.p2gpu_circuit_export_vk_plonky2.argtypes = [vp, u8p, ctypes.POINTER(sz)]
     lib.p2gpu_verifier_create_plonky2.argtypes = [u8p, sz, ctypes.c_int, ctypes.POINTER(vp)]
@@ -617,6 +644,11 @@ class CircuitData:
         rejected (the failed check is the message), returns None when it is accepted."""
         _verify(self._lib, self._h, proof)
 
+    def verify_batch(self, proofs):
+        """``p2gpu_verify_batch`` on this handle's device and stream: one :class:`VerifyReport` per proof.  An invalid proof
+        raises nothing; P2GpuError is for argument and device errors."""
+        return _verify_batch(self._lib, self._h, proofs, True)
+
     def verifier_data(self):
         """``circuit_data.verifier_data()``: the verifier's share of the circuit."""
         return VerifierCircuitData(self.verifier_blob())
@@ -802,10 +834,11 @@ class WitnessPlan:
             _check(rc)
         return out, [int(s) for s in status], [(int(r), int(c)) if s else None for s, (r, c) in zip(status, bad)]
 
-    def prove_batch(self, values_list, public_inputs=None):
+    def prove_batch(self, values_list, public_inputs=None, verify=False):
         """`generate_batch`, then the resident proof (``CircuitData.prove`` on the member's matrix) of every good member, in
         order.  `public_inputs`: one list per member.  Returns per member the ``ProofWithPublicInputs``, or the ``P2GpuError``
-        a lone ``prove`` would have raised."""
+        a lone ``prove`` would have raised.  verify=True: also one ``CircuitData.verify_batch`` over the proofs just made;
+        returns (that list, the :class:`VerifyReport` per member, None where there is no proof)."""
         wires, status, bad = self.generate_batch(values_list)
         out = []
         for b, st in enumerate(status):
@@ -816,7 +849,14 @@ class WitnessPlan:
                 out.append(self._cd.prove(wires[b], public_inputs[b] if public_inputs is not None else ()))
             except P2GpuError as e:
                 out.append(e)
-        return out
+        if not verify:
+            return out
+        made = [i for i, o in enumerate(out) if not isinstance(o, P2GpuError)]
+        reports = [None] * len(out)
+        if made:
+            for i, r in zip(made, self._cd.verify_batch([out[i] for i in made])):
+                reports[i] = r
+        return out, reports
 
     def check(self, values, public_inputs=(), details=False):
         """``p2gpu_check_seeds``: generate into the handle's own buffer, then ``CircuitData.check_witness`` on it: does the level
@@ -858,6 +898,24 @@ def _verify(lib, handle, proof):
     data = proof.to_bytes() if hasattr(proof, "to_bytes") else bytes(proof)
     buf = np.frombuffer(data, dtype=np.uint8)
     _check(lib.p2gpu_verify(handle, buf.ctypes.data if buf.size else None, buf.size))
+
+
+def _verify_batch(lib, handle, proofs, device):
+    datas = [p.to_bytes() if hasattr(p, "to_bytes") else bytes(p) for p in proofs]
+    offsets = np.zeros(len(datas) + 1, dtype=np.uintp)
+    offsets[1:] = np.cumsum([len(d) for d in datas], dtype=np.uint64)
+    buf = np.frombuffer(b"".join(datas) or b"\0", dtype=np.uint8)
+    reports = (_VerifyReport * max(len(datas), 1))()
+    fn = lib.p2gpu_verify_batch if device else lib.p2gpu_verify_batch_host
+    rc = fn(handle, buf.ctypes.data, offsets.ctypes.data, len(datas), ctypes.byref(reports))
+    if rc not in (0, -9):
+        _check(rc)
+    text = ctypes.create_string_buffer(400)
+    out = []
+    for r in reports[:len(datas)]:
+        _check(lib.p2gpu_verify_reason(ctypes.byref(r), text, len(text)))
+        out.append(VerifyReport(r, text.value.decode(errors="replace")))
+    return out
 
 
 def _convert(fn, handle, data):
@@ -954,6 +1012,13 @@ class VerifierCircuitData(_ProofFormats):
 
     def verify(self, proof):
         _verify(self._lib, self._h, proof)
+
+    def verify_batch(self, proofs, device=True):
+        """One :class:`VerifyReport` per proof.  device=True: ``p2gpu_verify_batch`` on the first device of ``init`` (the
+        handle keeps no device state: its few kilobytes are uploaded per call); device=False: ``p2gpu_verify_batch_host``, the
+        same checks in a plain loop on this thread.  An invalid proof raises nothing; P2GpuError is for argument and device
+        errors (without a GPU, device=True raises: there is no silent fall-back)."""
+        return _verify_batch(self._lib, self._h, proofs, device)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

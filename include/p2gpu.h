@@ -410,6 +410,58 @@ int p2gpu_circuit_export_blob(const p2gpu_circuit *c, uint8_t *out, size_t *len)
  * on the uncompressed proof bytes p2gpu_prove writes.  Returns P2GPU_OK or P2GPU_E_VERIFY (the failed
  * check is in p2gpu_last_error).  Accepts a prover handle or a verifier-only one. */
 int p2gpu_verify(const p2gpu_circuit *c, const uint8_t *proof, size_t len);
+
+/* ---- a batch of proofs of one circuit, with a verdict per proof ----
+ * The checks are p2gpu_verify's, in its order, and so is every verdict: the same functions (csrc/verifycore.hpp) run as
+ * kernels -- one lane per proof for the transcript, the plonk identity at zeta and the proof-of-work bits, one lane per
+ * (proof, query) for the Merkle paths, the folds and the final polynomial.
+ *   status  P2GPU_OK or P2GPU_E_VERIFY
+ *   reason  P2GPU_VR_*: the check that failed (0: none); there is one per rejection of p2gpu_verify
+ *   query   the query the reason names, index: the initial oracle or the fold step it names; UINT32_MAX where it names none.
+ *           For P2GPU_VR_LENGTH the two hold the length given and the length the circuit fixes.
+ * proofs: host bytes; proof b is proofs[offsets[b] .. offsets[b + 1]) (uncompressed, as p2gpu_prove writes it: decompress
+ * the on-disk format first); reports: host, [batch], complete whatever the return value is.
+ * Returns P2GPU_OK when every proof is valid and P2GPU_E_VERIFY when one is not: p2gpu_last_error then words the lowest
+ * failing proof exactly as p2gpu_verify would, behind "proof <b> of the batch: " when batch > 1.  Proofs of a batch do not
+ * affect each other.  A proof whose length is not the circuit's is answered on the host (truncated or non-canonical header,
+ * else the length) and never uploaded.  P2GPU_E_ARG, decided before any device call: a null pointer, batch == 0, decreasing
+ * offsets, a device group (use a plain handle).
+ * p2gpu_verify_batch accepts a plain prover handle (its device and stream) and a verifier-only handle (the handle stays free
+ * of device state: its few kilobytes -- gate table, cap, digest, k_is, round constants -- are uploaded per call to the first
+ * device of p2gpu_init).  Scratch and the upload of the proofs are allocated per call and released before it returns.
+ * The handle is const with one exception: on a prover handle whose "profile" knob is set, the two kernels are timed like every
+ * other launch on its stream and added to its kernel statistics (p2gpu_kernel_stats) -- so, like every call on a prover handle,
+ * it must not run while another thread uses the same handle.  A verifier-only handle is never written.
+ * Without a HIP device: P2GPU_E_DEVICE -- it never falls back to the host loop.
+ * p2gpu_verify_batch_host runs the same core in a plain loop on the calling thread and touches no device: the core's test
+ * bed and its sanitised build, not a fallback.
+ * p2gpu_verify_reason writes the wording of a report, NUL-terminated: the text behind "proof rejected: " in p2gpu_verify's
+ * message for that proof ("accepted" for reason 0); P2GPU_E_BUFFER when cap is too small. */
+#define P2GPU_VR_OK 0
+#define P2GPU_VR_HEADER 1          /* truncated or non-canonical header (caps / openings) */
+#define P2GPU_VR_ARITY 2           /* the circuit's reduction arities do not fit its size */
+#define P2GPU_VR_LENGTH 3          /* not the length the circuit fixes */
+#define P2GPU_VR_TAIL 4            /* non-canonical final polynomial, PoW witness or public input */
+#define P2GPU_VR_ZETA 5            /* zeta lies in the subgroup */
+#define P2GPU_VR_IDENTITY 6        /* vanishing(zeta) != Z_H(zeta) * quotient(zeta) */
+#define P2GPU_VR_POW 7             /* proof-of-work bits */
+#define P2GPU_VR_QUERY_INIT_SHAPE 8   /* query, oracle: path-length byte of an initial opening */
+#define P2GPU_VR_QUERY_LEAF 9         /* query: non-canonical leaf element */
+#define P2GPU_VR_QUERY_INIT_PATH 10   /* query, oracle: Merkle path of an initial oracle */
+#define P2GPU_VR_QUERY_STEP_SHAPE 11  /* query, step: non-canonical fold value or path-length byte */
+#define P2GPU_VR_QUERY_FOLD 12        /* query, step: the step does not continue the previous value */
+#define P2GPU_VR_QUERY_STEP_PATH 13   /* query, step: Merkle path of a fold step */
+#define P2GPU_VR_QUERY_FINAL 14       /* query: final polynomial at the folded point */
+#define P2GPU_VR_QUERY_SIZE 15        /* (query section of the wrong size: unreachable once the length is the circuit's) */
+typedef struct {
+  int32_t status;
+  uint32_t reason, query, index;
+} p2gpu_verify_report;
+int p2gpu_verify_batch(const p2gpu_circuit *c, const uint8_t *proofs, const size_t *offsets /* [batch + 1] */, size_t batch,
+                       p2gpu_verify_report *reports);
+int p2gpu_verify_batch_host(const p2gpu_circuit *c, const uint8_t *proofs, const size_t *offsets /* [batch + 1] */, size_t batch,
+                            p2gpu_verify_report *reports);
+int p2gpu_verify_reason(const p2gpu_verify_report *r, char *out, size_t cap);
 /* The verifier's share of a circuit -- header, gate table, constants_sigmas cap, circuit digest, k_is
  * (the blob prefix up to the constants table, flags 0b11) -- like the VK file of
  * actions/write_vk_action.rs:65-81.  out == NULL: only report the size in *len. */
