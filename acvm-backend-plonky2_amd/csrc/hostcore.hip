@@ -1,6 +1,6 @@
 // hostcore.hip -- the kernel-free core of libp2gpu: error text, circuit-blob parsing and validation,
-// handle getters and destruction.  Everything here (and verify.hip, proofio.hip) is plain host code
-// that never launches a kernel, so the three files also build WITHOUT device code under
+// handle getters and destruction.  Everything here (and verify.hip, proofio.hip, vkio.hip) is plain host code
+// that never launches a kernel, so the four files also build WITHOUT device code under
 // -fsanitize=address,undefined (`make asan` -> libp2gpu_host_asan.so) for the fuzz tests: these are
 // the parsers that read untrusted bytes on machines with no GPU (the reference's `verify` action,
 // plonky2-backend/src/actions/verify_action.rs:11-17, reader noir_and_plonky2_serialization.rs:16-33).

@@ -1,13 +1,13 @@
-// hostproof.hpp -- host-side pieces shared by the verifier (verify.hip, verifydev.hip) and the proof
-// (de)compression (proofio.hip): a bounds-checked byte cursor,
-// alpha-power reduction, the coset interpolation of a FRI fold and the handle's view for the verifier core (verifycore.hpp).
+// hostproof.hpp -- host-side pieces shared by the verifier (verify.hip, verifydev.hip), the proof (de)compression (proofio.hip)
+// and the verifier-key file format (vkio.hip): a bounds-checked byte cursor for input of variable length, a growing byte sink
+// with the two-call output convention of the C ABI, and the handle's view for the verifier core (verifycore.hpp).
 #pragma once
 #include "circuit.hpp"
 #include "verifycore.hpp"
 
 namespace p2 {
 
-// bounds-checked cursor over the proof bytes
+// bounds-checked cursor over input bytes whose parts have no fixed place (a compressed proof, a verifier-key file)
 struct Cursor {
   const uint8_t *p;
   size_t len, at = 0;
@@ -31,30 +31,33 @@ struct Cursor {
     if (v >= GL_P) ok = false;
     return v;
   }
-  ext_t ext() {
-    gl_t a = felt(), b = felt();
-    return ext_make(a, b);
-  }
-  dig_t digest() {
-    dig_t d;
-    memset(&d, 0, sizeof d);
-    if (const uint8_t *q = take(hh_bytes())) memcpy(d.w, q, hh_bytes());
-    // PoseidonHash digests are 4 field elements: w and w + p hash alike, so only the canonical encoding is a proof
-    if (g_hh.kind)
-      for (int i = 0; i < 4; i++)
-        if (d.w[i] >= GL_P) ok = false;
-    return d;
-  }
-  void digests(std::vector<dig_t> &v, size_t n) {
-    v.resize(n);
-    for (auto &d : v) d = digest();
-  }
 };
 
-// the closed-form coset interpolation of a FRI fold (verifycore.hpp interpolate_coset_fn) on an array of values
-inline ext_t interpolate_coset(gl_t s, unsigned ab, const ext_t *y_natural, ext_t beta) {
-  return vc::interpolate_coset_fn(s, ab, [&](uint32_t j) { return y_natural[j]; }, beta);
+// growing output bytes, and how an entry point hands them over: `out == NULL` asks for the size
+struct Out {
+  std::vector<uint8_t> v;
+  void put(const void *p, size_t n) {
+    const uint8_t *q = (const uint8_t *)p;
+    v.insert(v.end(), q, q + n);
+  }
+  void u8(uint8_t x) { v.push_back(x); }
+  void u32(uint32_t x) { put(&x, 4); }
+  void u64(uint64_t x) { put(&x, 8); }
+  void dig(const dig_t &d) { put(d.w, hh_bytes()); }
+};
+inline int emit(const std::vector<uint8_t> &v, uint8_t *out, size_t *out_len) {
+  if (!out || *out_len < v.size()) {
+    const bool probe = out == nullptr;
+    *out_len = v.size();
+    if (probe) return P2GPU_OK;
+    set_err("output buffer too small: %zu bytes needed", v.size());
+    return P2GPU_E_BUFFER;
+  }
+  memcpy(out, v.data(), v.size());
+  *out_len = v.size();
+  return P2GPU_OK;
 }
+inline int emit(const Out &o, uint8_t *out, size_t *out_len) { return emit(o.v, out, out_len); }
 
 // the verifier's share of a handle as the core takes it (host pointers, valid while the handle lives)
 inline vc::CircuitView view_of(const p2gpu_circuit *c) {

@@ -4,7 +4,9 @@
 // VK: the verifier's share of a circuit blob (header | gate table | cap | k_is, as p2gpu_circuit_export_vk writes it).
 // Cases, in this order: the proof as it is; the proof cut (or zero-extended) to every LEN; COUNT single-bit flips drawn from SEED
 // by step() below.  Every case is verified in a heap block of exactly its own length, so that a read past its end is the
-// sanitizer's to find.  OUT: per case "reason query index", then "counts" and the number of cases per reason code.
+// sanitizer's to find.  OUT: per case "reason query index well_formed", then "counts" and the number of cases per reason code.
+// Checked here, by abort: a case that is not well_formed() is not accepted, and on the proof as it is head_challenges() alone
+// leaves the HeadRecord that verify_head() leaves.
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -83,9 +85,21 @@ int main(int argc, char **argv) {
     if (flip_at >= 0) p[flip_at] ^= (uint8_t)(1u << bit);
     gl_t sponge[12];
     vc::HeadRecord rec;
+    std::memset(&rec, 0, sizeof rec);
     const vc::Verdict v = c.hasher ? vc::verify_one<1>(c, L, p, len, sponge, terms.data(), &rec) : vc::verify_one<0>(c, L, p, len, sponge, terms.data(), &rec);
+    const bool wf = c.hasher ? vc::well_formed<1>(c, L, p, len) : vc::well_formed<0>(c, L, p, len);
+    if (!wf && !v.reason) { std::fprintf(stderr, "accepted, but not well-formed\n"); std::abort(); }
+    if (src == proof.data() && len == proof.size() && flip_at < 0) {  // the proof as it is: the transcript alone leaves verify_head's record
+      gl_t betas[vc::VC_MAX_CHALLENGES], gammas[vc::VC_MAX_CHALLENGES], alphas[vc::VC_MAX_CHALLENGES], pih[4];
+      vc::HeadRecord mine;
+      std::memset(&mine, 0, sizeof mine);
+      const vc::Strided<gl_t> sp{sponge, 1};
+      if (c.hasher) vc::head_challenges<1>(c, L, p, sp, betas, gammas, alphas, pih, &mine);
+      else vc::head_challenges<0>(c, L, p, sp, betas, gammas, alphas, pih, &mine);
+      if (std::memcmp(&mine, &rec, sizeof rec)) { std::fprintf(stderr, "head_challenges and verify_head leave different records\n"); std::abort(); }
+    }
     std::free(p);
-    std::printf("%u %u %u\n", v.reason, v.query, v.index);
+    std::printf("%u %u %u %d\n", v.reason, v.query, v.index, (int)wf);
     counts[v.reason < vc::VR_COUNT ? v.reason : 0]++;
   };
   run(proof.data(), proof.size(), proof.size(), -1, 0);

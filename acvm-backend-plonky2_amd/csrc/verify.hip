@@ -103,7 +103,7 @@ int p2gpu_verifier_create(const uint8_t *blob, size_t len, p2gpu_circuit **out) 
     memset(&c->cs.cap[i], 0, sizeof(dig_t));
     memcpy(c->cs.cap[i].w, cap_in + 32 * i, c->hasher ? 32 : 25);
   }
-  if (c->hasher) {  // Poseidon digests are field elements: canonical encodings only (as Cursor::digest() asks of a proof)
+  if (c->hasher) {  // Poseidon digests are field elements: canonical encodings only (as verifycore.hpp ld_digest asks of a proof)
     bool canon = true;
     for (auto &dg : c->cs.cap)
       for (int i = 0; i < 4; i++) canon &= dg.w[i] < GL_P;

@@ -6,7 +6,8 @@
 //                                       HeadRecord (challenges, reduced openings, query indices) behind
 //   verify_query  per proof and query:  the four initial Merkle paths, the combined quotient value, every fold, the final
 //                                       polynomial at the folded point
-// Both return a reason code (0: passed); reason_text() below holds the wording of every code, once.
+// Both return a reason code (0: passed); reason_text() below holds the wording of every code, once.  Their parts that the proof
+// formats need too (proofio.hip) have names of their own: well_formed, head_challenges, query_initial, fold_step.
 //
 // WHAT NO PROOF BYTE CAN DO: move a read.  The length of a proof is fixed by its circuit (make_layout: `want`), and a proof
 // of another length never reaches these functions (shape_reason answers for it).  After that every read of the proof is at
@@ -109,6 +110,11 @@ struct Layout {
   size_t init_at[4];             // inside a query: leaf | length byte | siblings, per oracle
   size_t step_at[VC_MAX_STEPS];  // inside a query: 2^arity values | length byte | siblings, per step
   uint32_t bad_arity;
+  // inside the proof: query q's opening of oracle o (cols[o] words) or of fold step s (2^ab values) | length byte | siblings
+  P2_HD size_t leaf_at(size_t q, uint32_t o) const { return queries_at + query_bytes * q + init_at[o]; }
+  P2_HD size_t leaf_len_at(size_t q, uint32_t o) const { return leaf_at(q, o) + 8 * (size_t)cols[o]; }
+  P2_HD size_t vals_at(size_t q, uint32_t s) const { return queries_at + query_bytes * q + step_at[s]; }
+  P2_HD size_t vals_len_at(size_t q, uint32_t s, unsigned ab) const { return vals_at(q, s) + ((size_t)16 << ab); }
 };
 
 inline Layout make_layout(const CircuitView &c) {
@@ -426,6 +432,10 @@ struct Openings {
     return ld_ext(p, open_at + 16 * (size_t)pos);
   }
 };
+// the opened values of proof p
+P2_HD Openings proof_openings(const CircuitView &c, const Layout &L, const uint8_t *p) {
+  return Openings{nullptr, p, L.open_at, L.nall - L.nq - L.nzp + c.K, L.nall, c.K};
+}
 VC_FN bool plonk_identity_at(const CircuitView &c, const Openings &op, Strided<ext_t> terms, const gl_t *betas, const gl_t *gammas, const gl_t *alphas,
                              ext_t zeta, const gl_t *pih) {
   return plonk_identity_core(c, op, terms, betas, gammas, alphas, zeta, pih);
@@ -486,14 +496,38 @@ P2_HD uint32_t shape_reason(const CircuitView &c, const Layout &L, const uint8_t
   return L.bad_arity ? VR_ARITY : VR_LENGTH;
 }
 
+// "These bytes are a proof of this circuit's shape", without cryptography: the length, and every check of verify_head and
+// verify_query that needs no challenge -- what the proof formats (proofio.hip) ask before they take a proof apart.  The PoW
+// witness is a u64 to them, so it alone may be no field element here (verify_head answers VR_TAIL for it).
 template <int HK>
-P2_HD uint32_t verify_head(const CircuitView &c, const Layout &L, const uint8_t *p, Strided<gl_t> sponge, Strided<ext_t> terms, HeadRecord *rec) {
+P2_HD bool well_formed(const CircuitView &c, const Layout &L, const uint8_t *p, size_t len) {
+  if (L.bad_arity || len != L.want || !header_canonical<HK>(c, L, p, len)) return false;
+  bool ok = canonical_words(p, L.tail_at, 2 * L.final_len) && canonical_words(p, L.pis_at, c.num_pi);
+  for (uint32_t qi = 0; qi < c.num_queries; qi++) {
+    for (uint32_t o = 0; o < 4; o++) {
+      const size_t len_at = L.leaf_len_at(qi, o);
+      ok &= p[len_at] == L.init_len && canonical_words(p, L.leaf_at(qi, o), L.cols[o]);
+      if constexpr (HK) ok &= canonical_words(p, len_at + 1, 4 * (size_t)L.init_len);
+    }
+    for (uint32_t s = 0; s < c.n_steps; s++) {
+      const uint32_t ab = c.arity[s], levels = L.step_lg[s] - ab - c.cap_h;
+      const size_t len_at = L.vals_len_at(qi, s, ab);
+      ok &= canonical_words(p, L.vals_at(qi, s), (size_t)2 << ab) && p[len_at] == levels;
+      if constexpr (HK) ok &= canonical_words(p, len_at + 1, 4 * (size_t)levels);
+    }
+  }
+  return ok;
+}
+
+// Steps 2 and 3 of verify_head: the public-input hash and the transcript.  Everything the transcript yields goes to betas,
+// gammas, alphas ([VC_MAX_CHALLENGES] each), pih and *rec; returns the proof-of-work response.  Checks nothing: the header
+// and the tail are read as they lie.
+template <int HK>
+P2_HD gl_t head_challenges(const CircuitView &c, const Layout &L, const uint8_t *p, Strided<gl_t> sponge, gl_t *betas, gl_t *gammas, gl_t *alphas,
+                           gl_t pih[4], HeadRecord *rec) {
   const uint32_t K = c.K, nall = L.nall;
-  // 1. canonicity of everything in a fixed position
-  if (!header_canonical<HK>(c, L, p, L.want)) return VR_HEADER;
-  if (!canonical_words(p, L.tail_at, 2 * L.final_len + 1 + c.num_pi)) return VR_TAIL;
+  for (uint32_t k = 0; k < VC_MAX_CHALLENGES; k++) betas[k] = gammas[k] = alphas[k] = 0;
   // 2. the public-input hash (hash_n_to_m_no_pad, PoseidonHash whatever the circuit's hasher is)
-  gl_t pih[4];
   {
     gl_t st[12];
     for (int i = 0; i < 12; i++) st[i] = 0;
@@ -514,7 +548,6 @@ P2_HD uint32_t verify_head(const CircuitView &c, const Layout &L, const uint8_t 
   for (int i = 0; i < 4; i++) ch.observe(pih[i]);
   const size_t cap_bytes = (size_t)L.hb * L.ncap;
   ch.observe_cap(p, 0, L.ncap, L.hb);
-  gl_t betas[VC_MAX_CHALLENGES] = {0, 0}, gammas[VC_MAX_CHALLENGES] = {0, 0}, alphas[VC_MAX_CHALLENGES] = {0, 0};
   for (uint32_t k = 0; k < VC_MAX_CHALLENGES; k++)
     if (k < K) betas[k] = ch.get();
   for (uint32_t k = 0; k < VC_MAX_CHALLENGES; k++)
@@ -524,7 +557,7 @@ P2_HD uint32_t verify_head(const CircuitView &c, const Layout &L, const uint8_t 
     if (k < K) alphas[k] = ch.get();
   ch.observe_cap(p, 2 * cap_bytes, L.ncap, L.hb);
   const ext_t zeta = ch.get_ext();
-  const Openings op{nullptr, p, L.open_at, L.nall - L.nq - L.nzp + K, L.nall, K};
+  const Openings op = proof_openings(c, L, p);
   for (uint32_t j = 0; j < nall + K; j++) ch.observe_ext(op(j));
   const ext_t alpha = ch.get_ext();
   for (uint32_t s = 0; s < c.n_steps; s++) {
@@ -536,16 +569,7 @@ P2_HD uint32_t verify_head(const CircuitView &c, const Layout &L, const uint8_t 
   const gl_t pow_response = ch.get();
   const uint32_t mask = (uint32_t)(((size_t)1 << L.lgN) - 1);  // N is a power of two: same as % N
   for (uint32_t q = 0; q < c.num_queries; q++) rec->qidx[q] = (uint32_t)ch.get() & mask;
-  // 4. zeta^n != 1
-  {
-    ext_t zn = zeta;
-    for (uint32_t i = 0; i < c.d; i++) zn = ext_mul(zn, zn);
-    if (zn.c0 == 1 && zn.c1 == 0) return VR_ZETA;
-  }
-  // 5. the plonk identity at zeta
-  if (!plonk_identity_at(c, op, terms, betas, gammas, alphas, zeta, pih)) return VR_IDENTITY;
-  // 6. proof-of-work
-  if (c.pow_bits && (pow_response >> (64 - c.pow_bits)) != 0) return VR_POW;
+  // the openings reduced with alpha, as fri_combine_initial subtracts them
   ext_t o0 = ext_from(0), o1 = ext_from(0);
   for (uint32_t j = nall; j-- > 0;) o0 = ext_add(ext_mul(o0, alpha), op(j));
   for (uint32_t j = K; j-- > 0;) o1 = ext_add(ext_mul(o1, alpha), op(nall + j));
@@ -555,21 +579,71 @@ P2_HD uint32_t verify_head(const CircuitView &c, const Layout &L, const uint8_t 
   rec->g_zeta = ext_scale(zeta, gl_root(c.d));
   rec->opened0 = o0;
   rec->opened1 = o1;
+  return pow_response;
+}
+
+template <int HK>
+P2_HD uint32_t verify_head(const CircuitView &c, const Layout &L, const uint8_t *p, Strided<gl_t> sponge, Strided<ext_t> terms, HeadRecord *rec) {
+  // 1. canonicity of everything in a fixed position
+  if (!header_canonical<HK>(c, L, p, L.want)) return VR_HEADER;
+  if (!canonical_words(p, L.tail_at, 2 * L.final_len + 1 + c.num_pi)) return VR_TAIL;
+  // 2, 3. the public-input hash and the transcript
+  gl_t betas[VC_MAX_CHALLENGES], gammas[VC_MAX_CHALLENGES], alphas[VC_MAX_CHALLENGES], pih[4];
+  const gl_t pow_response = head_challenges<HK>(c, L, p, sponge, betas, gammas, alphas, pih, rec);
+  // 4. zeta^n != 1
+  {
+    ext_t zn = rec->zeta;
+    for (uint32_t i = 0; i < c.d; i++) zn = ext_mul(zn, zn);
+    if (zn.c0 == 1 && zn.c1 == 0) return VR_ZETA;
+  }
+  // 5. the plonk identity at zeta
+  if (!plonk_identity_at(c, proof_openings(c, L, p), terms, betas, gammas, alphas, rec->zeta, pih)) return VR_IDENTITY;
+  // 6. proof-of-work
+  if (c.pow_bits && (pow_response >> (64 - c.pow_bits)) != 0) return VR_POW;
   return VR_OK;
 }
 
 // ---- per proof and query ---------------------------------------------------------------------------------------------------
+// fri_combine_initial for query qi, from its four leaves: the value the first fold must continue.  *e_out: the exponent of
+// the queried point g w_N^e (leaf x0 holds natural LDE row bitrev(x0), g = GL_GEN)
+P2_HD ext_t query_initial(const CircuitView &c, const Layout &L, const uint8_t *p, const HeadRecord *rec, uint32_t qi, size_t *e_out) {
+  const uint32_t K = c.K, lgN = L.lgN;
+  const size_t x0 = rec->qidx[qi] & (uint32_t)(((size_t)1 << lgN) - 1);
+  const ext_t alpha = rec->alpha;
+  size_t e = 0;
+  for (unsigned b = 0; b < lgN; b++) e |= ((x0 >> b) & 1) << (lgN - 1 - b);
+  const gl_t x_pt = gl_mul(GL_GEN, gl_pow(gl_root(lgN), e));
+  // (F0(x) - F0(zeta)) / (x - zeta) * alpha^K + (F1(x) - F1(g zeta)) / (x - g zeta)
+  ext_t acc0 = ext_from(0), acc1 = ext_from(0);
+  for (uint32_t o = 4; o-- > 0;) {
+    const size_t leaf_at = L.leaf_at(qi, o);
+    for (uint32_t j = L.cols[o]; j-- > 0;) acc0 = ext_add(ext_mul(acc0, alpha), ext_from(ld64(p, leaf_at + 8 * (size_t)j)));
+  }
+  for (uint32_t j = K; j-- > 0;) acc1 = ext_add(ext_mul(acc1, alpha), ext_from(ld64(p, L.leaf_at(qi, 2) + 8 * (size_t)j)));
+  ext_t cur = ext_mul(ext_sub(acc0, rec->opened0), ext_inv(ext_sub(ext_from(x_pt), rec->zeta)));
+  cur = ext_add(ext_mul(cur, rec->alpha_k), ext_mul(ext_sub(acc1, rec->opened1), ext_inv(ext_sub(ext_from(x_pt), rec->g_zeta))));
+  *e_out = e;
+  return cur;
+}
+// One fold (fri/verifier.rs compute_evaluation): the 2^ab values at vals_at, a leaf of the tree over the domain of 2^lg points
+// with coset shift `shift`, interpolated at beta.  Leaf slot i holds the point s g^bitrev(i), s = shift * w^(e mod 2^(lg-ab));
+// *e is reduced to that exponent.
+P2_HD ext_t fold_step(const uint8_t *p, size_t vals_at, unsigned ab, unsigned lg, gl_t shift, size_t *e, ext_t beta) {
+  auto y_nat = [&](uint32_t j) { return ld_ext(p, vals_at + 16 * (size_t)bitrev32(j, ab)); };
+  *e &= ((size_t)1 << (lg - ab)) - 1;
+  const gl_t s_pt = gl_mul(shift, gl_pow(gl_root(lg), *e));
+  return interpolate_coset_fn(s_pt, ab, y_nat, beta);
+}
+
 // *index: the oracle or the step the reason names (VR_NONE: none)
 template <int HK>
 P2_HD uint32_t verify_query(const CircuitView &c, const Layout &L, const uint8_t *p, const HeadRecord *rec, uint32_t qi, uint32_t *index) {
   *index = VR_NONE;
-  const uint32_t K = c.K, lgN = L.lgN, hb = L.hb;
-  const size_t q_at = L.queries_at + L.query_bytes * qi;
+  const uint32_t lgN = L.lgN, hb = L.hb;
   const size_t x0 = rec->qidx[qi] & (uint32_t)(((size_t)1 << lgN) - 1);
-  const ext_t alpha = rec->alpha;
   // the four initial oracles: the row of each tree at leaf x0
   for (uint32_t o = 0; o < 4; o++) {
-    const size_t leaf_at = q_at + L.init_at[o], len_at = leaf_at + 8 * (size_t)L.cols[o];
+    const size_t leaf_at = L.leaf_at(qi, o), len_at = L.leaf_len_at(qi, o);
     *index = o;
     if (p[len_at] != L.init_len) return VR_Q_INIT_SHAPE;
     if (!canonical_words(p, leaf_at, L.cols[o])) {
@@ -584,27 +658,16 @@ P2_HD uint32_t verify_query(const CircuitView &c, const Layout &L, const uint8_t
     if (!canon || !dig_same<HK>(top, cap)) return VR_Q_INIT_PATH;
   }
   *index = VR_NONE;
-  // the queried point: leaf x0 holds natural LDE row bitrev(x0), i.e. g w_N^bitrev(x0), g = GL_GEN
-  size_t e = 0;
-  for (unsigned b = 0; b < lgN; b++) e |= ((x0 >> b) & 1) << (lgN - 1 - b);
+  size_t e;
+  ext_t cur = query_initial(c, L, p, rec, qi, &e);
   unsigned lg = lgN;
   gl_t shift = GL_GEN;
-  const gl_t x_pt = gl_mul(shift, gl_pow(gl_root(lg), e));
-  // fri_combine_initial: (F0(x) - F0(zeta)) / (x - zeta) * alpha^K + (F1(x) - F1(g zeta)) / (x - g zeta)
-  ext_t acc0 = ext_from(0), acc1 = ext_from(0);
-  for (uint32_t o = 4; o-- > 0;) {
-    const size_t leaf_at = q_at + L.init_at[o];
-    for (uint32_t j = L.cols[o]; j-- > 0;) acc0 = ext_add(ext_mul(acc0, alpha), ext_from(ld64(p, leaf_at + 8 * (size_t)j)));
-  }
-  for (uint32_t j = K; j-- > 0;) acc1 = ext_add(ext_mul(acc1, alpha), ext_from(ld64(p, q_at + L.init_at[2] + 8 * (size_t)j)));
-  ext_t cur = ext_mul(ext_sub(acc0, rec->opened0), ext_inv(ext_sub(ext_from(x_pt), rec->zeta)));
-  cur = ext_add(ext_mul(cur, rec->alpha_k), ext_mul(ext_sub(acc1, rec->opened1), ext_inv(ext_sub(ext_from(x_pt), rec->g_zeta))));
   // commit-phase folds
   size_t x = x0;
   for (uint32_t s = 0; s < c.n_steps; s++) {
     const unsigned ab = c.arity[s];
     const uint32_t a = 1u << ab;
-    const size_t vals_at = q_at + L.step_at[s], len_at = vals_at + 16 * (size_t)a;
+    const size_t vals_at = L.vals_at(qi, s), len_at = L.vals_len_at(qi, s, ab);
     const uint32_t levels = lg - ab - c.cap_h;
     *index = s;
     if (!canonical_words(p, vals_at, 2 * (size_t)a) || p[len_at] != levels) return VR_Q_STEP_SHAPE;
@@ -616,11 +679,7 @@ P2_HD uint32_t verify_query(const CircuitView &c, const Layout &L, const uint8_t
     const size_t entry = leaf_index >> levels;  // < 2^cap_h: leaf_index < 2^(lg - ab)
     const dig_t cap = ld_digest<HK>(p, L.step_caps_at + ((size_t)s * L.ncap + entry) * hb, &cap_canon);
     if (!canon || !dig_same<HK>(top, cap)) return VR_Q_STEP_PATH;
-    // leaf slot i holds the point s g^bitrev(i), s = shift * w^(e mod 2^(lg-ab))
-    auto y_nat = [&](uint32_t j) { return ld_ext(p, vals_at + 16 * (size_t)bitrev32(j, ab)); };
-    e &= ((size_t)1 << (lg - ab)) - 1;
-    const gl_t s_pt = gl_mul(shift, gl_pow(gl_root(lg), e));
-    cur = interpolate_coset_fn(s_pt, ab, y_nat, rec->beta[s]);
+    cur = fold_step(p, vals_at, ab, lg, shift, &e, rec->beta[s]);
     for (unsigned i = 0; i < ab; i++) shift = gl_sqr(shift);
     lg -= ab;
     x = leaf_index;

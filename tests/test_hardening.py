@@ -78,7 +78,7 @@ def test_mutation_fuzz_of_the_host_parsers(built, corpus):
 
 
 def test_host_parsers_under_asan_ubsan(built, corpus):
-    """`make asan`: hostcore.hip + verify.hip + proofio.hip compiled host-only (no device code) with
+    """`make asan`: hostcore.hip + verify.hip + proofio.hip + vkio.hip compiled host-only (no device code) with
     -fsanitize=address,undefined, the same fuzzer linked against that build."""
     d, _, _ = corpus
     subprocess.check_call(["make", "-s", "-C", CSRC, "asan"])
