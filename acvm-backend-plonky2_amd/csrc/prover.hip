@@ -72,7 +72,8 @@ int commit_wires(p2gpu_circuit *c, Proof &P) {
 }
 
 // ---- 2. partial products and Z ----
-int commit_zs(p2gpu_circuit *c, Proof &P) {
+// the values over the subgroup -> c->zp_vals [K (1 + PP)][n] (enqueued)
+int zs_values(p2gpu_circuit *c, Proof &P) {
   hipStream_t st = c->stream;
   const uint32_t d = c->d, K = c->K;
   ZsArgs a;
@@ -105,11 +106,16 @@ int commit_zs(p2gpu_circuit *c, Proof &P) {
     zs_partial_products(st, a, c->scan_tmp.p);
   }
   TRACE(c, "zs_partial_products");
+  return 0;
+}
+int commit_zs(p2gpu_circuit *c, Proof &P) {
+  if (int rc = zs_values(c, P)) return rc;
   return batch_commit_from_values(c, c->zp, c->zp_vals.p);
 }
 
 // ---- 3. quotient: alpha powers, the gate sums of the half-domain gates, the quotient values, their chunk polynomials ----
-int commit_quotient(p2gpu_circuit *c, Proof &P) {
+// the quotient values of every LDE point -> c->qvals [K][cosets][n] (enqueued)
+int quotient_values(p2gpu_circuit *c, Proof &P) {
   hipStream_t st = c->stream;
   const uint32_t d = c->d, K = c->K, nterms = c->nterms;
   const size_t n = c->n;
@@ -169,8 +175,15 @@ int commit_quotient(p2gpu_circuit *c, Proof &P) {
   }
   quotient_eval(st, q);
   TRACE(c, "quotient_eval");
+  return 0;
+}
+// c->qvals -> the chunk polynomials, committed
+int quotient_chunks_commit(p2gpu_circuit *c) {
+  hipStream_t st = c->stream;
+  const uint32_t d = c->d, K = c->K;
+  const size_t n = c->n;
   // coset_ifft of size N = per-coset inverse transforms + cross-coset butterflies
-  ntt_batch(st, c->plan_inv, c->qvals.p, c->qtmp.p, K * c->wires.ncl, 1, nullptr, q.n_inv, false);
+  ntt_batch(st, c->plan_inv, c->qvals.p, c->qtmp.p, K * c->wires.ncl, 1, nullptr, gl_inv((gl_t)n), false);
   const gl_t *pr = c->qtmp.p;
   if (sharded(c)) {
     // every rank needs all cosets' interpolants for the cross-coset butterflies: all-gather
@@ -183,6 +196,10 @@ int commit_quotient(p2gpu_circuit *c, Proof &P) {
                   (uint32_t)c->shard_world);
   TRACE(c, "quotient_chunks");
   return batch_commit_from_coeffs(c, c->quot);
+}
+int commit_quotient(p2gpu_circuit *c, Proof &P) {
+  if (int rc = quotient_values(c, P)) return rc;
+  return quotient_chunks_commit(c);
 }
 
 // ---- 4. openings: the four batches at zeta and Z at g * zeta in one launch, summed on the host ----
@@ -786,9 +803,85 @@ int prove_impl(p2gpu_circuit *c, const gl_t *wires_dev, const uint64_t *pis, uin
   return serialise(c, P, proof_out, proof_len, tm);
 }
 
+// p2gpu_plonk_stages behind its argument checks: phases 1-3 of prove_impl -- the same phase functions -- with the caller's
+// challenges where the transcript's would be, and the raw results of phases 2 and 3 read back between them
+int plonk_stages_impl(p2gpu_circuit *c, const uint64_t *wires, const uint64_t *pi_hash, const uint64_t *betas, const uint64_t *gammas,
+                      const uint64_t *alphas, const uint64_t *zp_in, uint64_t *zp_out, uint64_t *qvals_out, uint64_t *quot_out,
+                      uint8_t *caps_out) {
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = c->n, nzp = (size_t)c->K * (1 + c->PP), nq = (size_t)c->K * c->C;
+  HIP_TRY(hipMemcpyAsync(c->wires_vals.p, wires, 8 * (size_t)c->W * n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  ProfGuard prof(c);
+  Proof P(c, c->wires_vals.p, nullptr, 0, 0.0);
+  for (int i = 0; i < 4; i++) P.pih[i] = pi_hash[i];
+  for (uint32_t k = 0; k < c->K; k++) { P.betas[k] = betas[k]; P.gammas[k] = gammas[k]; P.alphas[k] = alphas[k]; }
+  c->pin.reset();
+  use_hasher(c);
+  P.vfirst = virt_first(c);
+  const size_t hb = c->hasher ? 32 : 25, ncap = (size_t)1 << c->cap_h;
+  auto put_cap = [&](int which, const Batch &b) {
+    for (size_t i = 0; i < ncap; i++) memcpy(caps_out + (which * ncap + i) * hb, b.cap[i].w, hb);
+  };
+
+  if (int rc = commit_wires(c, P)) return rc;
+  put_cap(0, c->wires);
+
+  if (int rc = zs_values(c, P)) return rc;
+  HIP_TRY(hipMemcpyAsync(zp_out, c->zp_vals.p, 8 * nzp * n, hipMemcpyDeviceToHost, c->stream));
+  if (zp_in) HIP_TRY(hipMemcpyAsync(c->zp_vals.p, zp_in, 8 * nzp * n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (int rc = batch_commit_from_values(c, c->zp, c->zp_vals.p)) return rc;
+  put_cap(1, c->zp);
+
+  if (int rc = quotient_values(c, P)) return rc;
+  HIP_TRY(hipMemcpyAsync(qvals_out, c->qvals.p, 8 * nq * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (int rc = quotient_chunks_commit(c)) return rc;
+  put_cap(2, c->quot);
+  // the library stores coefficients at bit-reversed positions; the caller gets plonky2's natural order
+  std::vector<uint64_t> br(nq * n);
+  HIP_TRY(hipMemcpy(br.data(), c->quot.coeffs.p, 8 * nq * n, hipMemcpyDeviceToHost));
+  for (size_t col = 0; col < nq; col++)
+    for (size_t p = 0; p < n; p++) {
+      size_t e = 0;
+      for (uint32_t b = 0; b < c->d; b++) e |= ((p >> b) & 1) << (c->d - 1 - b);
+      quot_out[col * n + e] = br[col * n + p];
+    }
+  if (c->profile && c->pending.size() > 16384) flush_kstats(c);
+  return P2GPU_OK;
+}
+
 }  // namespace p2
 
 extern "C" {
+
+int p2gpu_plonk_stages(p2gpu_circuit *c, const uint64_t *wires, const uint64_t *pi_hash, const uint64_t *betas, const uint64_t *gammas,
+                       const uint64_t *alphas, const uint64_t *zp_in, uint64_t *zp_out, uint64_t *qvals_out, uint64_t *quot_out,
+                       uint8_t *caps_out) try {
+  // every refusal is decided here, before any device call
+  if (!c || !wires || !pi_hash || !betas || !gammas || !alphas || !zp_out || !qvals_out || !quot_out || !caps_out) {
+    set_err("p2gpu_plonk_stages: a null pointer (only zp_in may be null)");
+    return P2GPU_E_ARG;
+  }
+  if (int rc = prover_handle(c)) return rc;
+  if (!c->group.empty() || sharded(c) || c->shard_world > 1) {
+    set_err("p2gpu_plonk_stages: a plain handle is needed, not a device group or a sharded handle");
+    return P2GPU_E_ARG;
+  }
+  auto canonical = [](const uint64_t *v, size_t cnt) {
+    uint64_t big = 0;
+    for (size_t i = 0; i < cnt; i++) big |= (uint64_t)(v[i] >= GL_P);
+    return !big;
+  };
+  const size_t nzp = (size_t)c->K * (1 + c->PP);
+  if (!canonical(wires, (size_t)c->W * c->n) || !canonical(pi_hash, 4) || !canonical(betas, c->K) || !canonical(gammas, c->K) ||
+      !canonical(alphas, c->K) || (zp_in && !canonical(zp_in, nzp * c->n))) {
+    set_err("p2gpu_plonk_stages: a word that is not a canonical field element");
+    return P2GPU_E_ARG;
+  }
+  return plonk_stages_impl(c, wires, pi_hash, betas, gammas, alphas, zp_in, zp_out, qvals_out, quot_out, caps_out);
+} P2GPU_CATCH
 
 int p2gpu_fill_witness(p2gpu_circuit *c, uint64_t *wires_dev) try {
   if (!c || !wires_dev) return P2GPU_E_ARG;

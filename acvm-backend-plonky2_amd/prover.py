@@ -207,6 +207,7 @@ def load_library():
     lib.p2gpu_field_selftest.argtypes = [vp, vp, sz, vp]
     lib.p2gpu_field_selftest16.argtypes = [vp, vp, sz, vp]
     lib.p2gpu_forms_selftest.argtypes = [ctypes.c_uint, vp, sz, vp, vp]
+    lib.p2gpu_plonk_stages.argtypes = [vp] * 11
     lib.p2gpu_device_info.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(sz)]
     lib.p2gpu_peer_access.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int]
     lib.p2gpu_circuit_create_on.argtypes = [u8p, sz, ctypes.c_int, ctypes.POINTER(vp)]
@@ -507,6 +508,34 @@ class CircuitData:
         _check(rc)
         t = {f: getattr(tm, f) for f, _ in _Timings._fields_}
         return ProofWithPublicInputs(out[:plen.value].tobytes(), t)
+
+    def plonk_stages(self, wires, pi_hash, betas, gammas, alphas, zp_in=None):
+        """Prover phases 1-3 on caller-chosen challenges (``p2gpu_plonk_stages``, a test bed: no proof calls it).  Returns a
+        dict: ``zp`` [K (1 + PP)][n] as phase 2 computed it (before ``zp_in`` replaces it), ``qvals`` [K][2^rate_bits][n],
+        ``quot`` [K 2^rate_bits][n] (natural-order coefficients), ``caps`` (wires, zs, quotient) as bytes."""
+        hdr = (self._blob if self._blob is not None else self.to_blob())[:256].view(np.uint32)
+        K, PP, C, n = int(hdr[7]), int(hdr[26]), 1 << self.rate_bits, self.degree
+        w = _u64(wires)
+        if w.size != self.num_wires * n:
+            raise P2GpuError(-7, f"wires must be [num_wires={self.num_wires}][degree={n}]")
+        ch = [_u64(np.array([int(x) for x in v], dtype=np.uint64)) for v in (pi_hash, betas, gammas, alphas)]
+        if ch[0].size != 4 or any(v.size != K for v in ch[1:]):
+            raise P2GpuError(-7, f"pi_hash must hold 4 words, betas / gammas / alphas {K} each")
+        zi = None
+        if zp_in is not None:
+            zi = _u64(zp_in)
+            if zi.size != K * (1 + PP) * n:
+                raise P2GpuError(-7, f"zp_in must be [{K * (1 + PP)}][{n}]")
+        zp = np.zeros((K * (1 + PP), n), dtype=np.uint64)
+        qv = np.zeros((K, C, n), dtype=np.uint64)
+        quot = np.zeros((K * C, n), dtype=np.uint64)
+        hb = self.hash_bytes() << self.cap_height
+        caps = np.zeros(3 * hb, dtype=np.uint8)
+        _check(self._lib.p2gpu_plonk_stages(self._h, w.ctypes.data, ch[0].ctypes.data, ch[1].ctypes.data, ch[2].ctypes.data, ch[3].ctypes.data,
+                                            zi.ctypes.data if zi is not None else None, zp.ctypes.data, qv.ctypes.data, quot.ctypes.data,
+                                            caps.ctypes.data))
+        cb = caps.tobytes()
+        return {"zp": zp, "qvals": qv, "quot": quot, "caps": (cb[:hb], cb[hb:2 * hb], cb[2 * hb:])}
 
     def _check_call(self, call, batch, public_inputs, details):
         """Run call(pis pointer, n_pi, reports pointer, row_status pointer, cell_flags pointer) -> rc of one of the check entry

@@ -590,6 +590,22 @@ int p2gpu_field_selftest16(const uint64_t *a, const uint64_t *b, size_t n, uint6
 #define P2GPU_FORM_ACC160 8
 #define P2GPU_FORM_RANGE4 9
 int p2gpu_forms_selftest(unsigned form, const uint64_t *in, size_t n, const uint64_t *aux, uint64_t *out);
+/* Prover phases 1-3 (wires commitment; Z and partial products; quotient) on challenges the CALLER chooses, their raw results
+ * read back: a test bed for the permutation argument and the quotient kernels.  No proof calls this.  It runs the phase
+ * functions a proof runs, with betas / gammas / alphas [num_challenges] in place of the transcript's and pi_hash[4] in place
+ * of the hash of public inputs; the wires [num_wires][n] need not satisfy the circuit.  With K = num_challenges,
+ * PP = num_partial_products, C = 2^rate_bits, all buffers in host memory:
+ *   zp_in      NULL, or [K (1 + PP)][n]: replaces the Z / partial-product values of phase 2 before they are committed
+ *   zp_out     [K (1 + PP)][n]: what phase 2 computed (Z of every challenge, then the partial products), before zp_in
+ *   qvals_out  [K][C][n]: the quotient values; coset r, index k is the LDE point g w_N^(C k + r)
+ *   quot_out   [K C][n]: the coefficients of the quotient chunk polynomials, natural order
+ *   caps_out   [3][2^cap_height][hash bytes]: the wires, Z / partial-product and quotient caps
+ * The handle's knobs (half_gates, zero_columns, virtual_columns, profile) and the P2GPU_* environment switches apply as in
+ * a proof; a proof on the handle afterwards is unaffected.  P2GPU_E_ARG, decided before any device call: a null pointer
+ * (other than zp_in), a verifier-only handle, a device group or a sharded handle, a word >= p in any input. */
+int p2gpu_plonk_stages(p2gpu_circuit *c, const uint64_t *wires, const uint64_t *pi_hash, const uint64_t *betas, const uint64_t *gammas,
+                       const uint64_t *alphas, const uint64_t *zp_in, uint64_t *zp_out, uint64_t *qvals_out, uint64_t *quot_out,
+                       uint8_t *caps_out);
 
 const char *p2gpu_last_error(void);
 /* name/arch of the device in use, and peak numbers the bench prints */
