@@ -1,6 +1,7 @@
 // circuit.hpp -- host-side types shared by the prover pipeline (prover.hip) and the verifier
-// (verify.hip): the Fiat-Shamir transcript, the committed-batch bookkeeping and the circuit handle
-// behind the opaque `p2gpu_circuit` of include/p2gpu.h.
+// (verify.hip): the committed-batch bookkeeping and the circuit handle behind the opaque
+// `p2gpu_circuit` of include/p2gpu.h.  (The hasher, the Fiat-Shamir transcript and the proof's byte
+// layout are verifycore.hpp's, for the prover too; hostproof.hpp brings the two together.)
 #pragma once
 #include "internal.hpp"
 #include "poseidon.hpp"
@@ -20,114 +21,16 @@ void set_err(const char *fmt, ...);
 std::string last_error_copy();
 void last_error_restore(const std::string &s);
 
-// ---- the circuit's hasher on the host ------------------------------------------------------------
+// ---- the circuit's hasher ------------------------------------------------------------------------
 // 0 = KeccakHash<25> (KeccakGoldilocksConfig, the reference: plonky2-backend/src/lib.rs:13): 25-byte digests,
 //     Keccak "hash onion" sponge permutation;
 // 1 = PoseidonHash (PoseidonGoldilocksConfig, the north_star's "Poseidon-GL Merkle-tree hashing"): digests are 4
 //     field elements (32 bytes), leaves are absorbed 8 elements per Poseidon permutation (overwrite mode,
 //     hash/hashing.rs hash_n_to_m_no_pad), nodes are compress(l, r) = permute(l || r || 0^4)[0..4], the
 //     challenger permutes with Poseidon.
-// Every C-ABI entry point selects the hasher of the handle it was given for the calling thread (use_hasher).
-struct HostHasher {
-  int kind = 0;
-  const gl_t *prc = nullptr;  // the 360 Poseidon round constants of the handle
-};
-extern thread_local HostHasher g_hh;
-inline size_t hh_bytes() { return g_hh.kind ? 32 : 25; }
-inline void sponge_permute(gl_t st[12]) {
-  if (g_hh.kind) poseidon_permute_host(st, g_hh.prc);
-  else keccak_permutation12(st);
-}
-inline void digest_elems(const dig_t &d, gl_t e[4]) {
-  if (g_hh.kind) for (int i = 0; i < 4; i++) e[i] = d.w[i];
-  else dig_to_elems(d, e);
-}
-inline bool dig_eq(const dig_t &a, const dig_t &b) {
-  return a.w[0] == b.w[0] && a.w[1] == b.w[1] && a.w[2] == b.w[2] && (g_hh.kind ? a.w[3] == b.w[3] : (a.w[3] & 0xFF) == (b.w[3] & 0xFF));
-}
-// H::hash_or_noop of a leaf of field elements
-inline dig_t leaf_digest(const gl_t *v, size_t n) {
-  dig_t d;
-  memset(&d, 0, sizeof d);
-  if (g_hh.kind) {
-    if (n <= 4) {
-      for (size_t i = 0; i < n; i++) d.w[i] = v[i];
-    } else {
-      poseidon_hash_no_pad_host(v, n, d.w, g_hh.prc);
-    }
-    return d;
-  }
-  if (n * 8 <= 25) {
-    for (size_t i = 0; i < n; i++) d.w[i] = v[i];
-    return d;
-  }
-  uint64_t h[4];
-  keccak256_words(v, n, h);
-  return dig_from_state(h);
-}
-// H::two_to_one
-inline dig_t node_digest(const dig_t &l, const dig_t &r) {
-  if (!g_hh.kind) return keccak_two_to_one(l, r);
-  gl_t st[12] = {l.w[0], l.w[1], l.w[2], l.w[3], r.w[0], r.w[1], r.w[2], r.w[3], 0, 0, 0, 0};
-  poseidon_permute_host(st, g_hh.prc);
-  dig_t d;
-  for (int i = 0; i < 4; i++) d.w[i] = st[i];
-  return d;
-}
-
-// ---- host transcript (iop/challenger.rs, Challenger<F, H>) ----
-struct Challenger {
-  gl_t state[12];
-  gl_t in[8];
-  int n_in = 0;
-  gl_t out[8];
-  int n_out = 0;
-  Challenger() { memset(state, 0, sizeof state); }
-  void duplex() {
-    for (int i = 0; i < n_in; i++) state[i] = in[i];
-    n_in = 0;
-    sponge_permute(state);
-    for (int i = 0; i < 8; i++) out[i] = state[i];
-    n_out = 8;
-  }
-  void observe(gl_t e) {
-    n_out = 0;
-    in[n_in++] = e;
-    if (n_in == 8) duplex();
-  }
-  void observe_digest(const dig_t &d) {
-    gl_t e[4];
-    digest_elems(d, e);
-    for (int i = 0; i < 4; i++) observe(e[i]);
-  }
-  void observe_cap(const std::vector<dig_t> &cap) {
-    for (auto &d : cap) observe_digest(d);
-  }
-  void observe_ext(ext_t e) {
-    observe(e.c0);
-    observe(e.c1);
-  }
-  gl_t get() {
-    if (n_in != 0 || n_out == 0) duplex();
-    return out[--n_out];
-  }
-  ext_t get_ext() {
-    gl_t a = get();
-    gl_t b = get();
-    return ext_make(a, b);
-  }
-};
-
-inline dig_t host_hash_no_pad(const std::vector<gl_t> &v) {
-  if (g_hh.kind) {
-    dig_t d;
-    poseidon_hash_no_pad_host(v.data(), v.size(), d.w, g_hh.prc);
-    return d;
-  }
-  uint64_t h[4];
-  keccak256_words(v.data(), v.size(), h);
-  return dig_from_state(h);
-}
+// The hasher is a field of the handle (CircuitState::hasher) and nothing else: host code that hashes takes it from the
+// handle it was given and runs the functions of verifycore.hpp (template parameter HK) -- no per-thread state.
+inline size_t digest_bytes(uint32_t hasher) { return hasher ? 32 : 25; }
 
 template <class T>
 struct DBuf {
@@ -262,8 +165,7 @@ struct CircuitState {
   DBuf<uint64_t> gather_ptrs;
   DBuf<gl_t> gather_out;
   size_t gather_cap = 0;
-  std::vector<uint64_t> h_ptrs;  // host scratch that keeps its capacity from proof to proof: the gather's pointer list,
-  std::vector<uint8_t> h_out;    // the proof bytes when the caller's buffer is smaller than p2gpu_proof_size_bound
+  std::vector<uint64_t> h_ptrs;  // host scratch that keeps its capacity from proof to proof: the gather's pointer list
   // coset sharding across ranks (one process per GPU); world = 1: everything local
   int shard_rank = 0, shard_world = 1;
   p2gpu_allgather_fn shard_fn = nullptr;  // host callback transport (tests over gloo)
@@ -310,7 +212,6 @@ struct p2gpu_circuit : p2::CircuitState {};
 
 namespace p2 {
 extern void (*g_circuit_release)(p2gpu_circuit *);  // hostcore.hip; set by handle.hip
-void use_hasher(const p2gpu_circuit *c);  // select the handle's hasher for this thread (hostcore.hip)
 void shard_assemble_cap(int world, unsigned rate_bits, size_t cap_per, const dig_t *gathered, std::vector<dig_t> &cap);
 // blob header + gate table + (optional) cap + k_is -> the host-side fields of the handle; leaves
 // *off at the constants table.  Used by p2gpu_circuit_create and p2gpu_verifier_create.

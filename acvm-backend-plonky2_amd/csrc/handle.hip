@@ -5,6 +5,7 @@
 // build.hip, alloc_proof_buffers, commit_constants_sigmas, check_cap_and_digest) on a handle that a HalfBuilt owns until it is
 // handed to the caller.  The proof itself is prover.hip, the commitment operators commit.hip, the exchanges of a sharded proof
 // transport.hip.
+#include "hostproof.hpp"
 #include "prover_internal.hpp"
 #include <functional>
 
@@ -406,25 +407,22 @@ int commit_constants_sigmas(p2gpu_circuit *c, const TableSource &src) {
 int check_cap_and_digest(p2gpu_circuit *c, const uint8_t *cap_in) {
   if (cap_in) {
     for (size_t i = 0; i < c->cs.cap.size(); i++)
-      if (memcmp(cap_in + 32 * i, c->cs.cap[i].w, c->hasher ? 32 : 25)) { set_err("constants_sigmas cap mismatch"); return P2GPU_E_CAP_MISMATCH; }
+      if (memcmp(cap_in + 32 * i, c->cs.cap[i].w, digest_bytes(c->hasher))) { set_err("constants_sigmas cap mismatch"); return P2GPU_E_CAP_MISMATCH; }
   }
   if (!(c->flags & 1)) {
     // circuit_builder.rs build(): H::hash_no_pad(cap.flatten() || hash_pad([]).to_vec() || [degree_bits])  (pinned: tests/test_reference_proofs.py)
+    // (both inputs are longer than four words: hash_no_pad of hostproof.hpp hashes them)
     std::vector<gl_t> parts;
-    for (auto &dg : c->cs.cap) {
-      gl_t e[4];
-      digest_elems(dg, e);
+    auto push = [&](const dig_t &dg) {  // a digest as field elements, the way the transcript takes it
+      gl_t e[4] = {dg.w[0], dg.w[1], dg.w[2], dg.w[3]};
+      if (!c->hasher) dig_to_elems(dg, e);
       parts.insert(parts.end(), e, e + 4);
-    }
-    std::vector<gl_t> pad(8, 0);  // hash_pad([]): pad10*1 to the sponge rate
-    pad[0] = 1;
-    pad[7] = 1;
-    dig_t ds = host_hash_no_pad(pad);
-    gl_t e[4];
-    digest_elems(ds, e);
-    parts.insert(parts.end(), e, e + 4);
+    };
+    for (auto &dg : c->cs.cap) push(dg);
+    gl_t pad[8] = {1, 0, 0, 0, 0, 0, 0, 1};  // hash_pad([]): pad10*1 to the sponge rate
+    push(hash_no_pad(c->hasher, pad, 8, c->poseidon_rc_gate));
     parts.push_back(c->d);
-    c->circuit_digest = host_hash_no_pad(parts);
+    c->circuit_digest = hash_no_pad(c->hasher, parts.data(), (uint32_t)parts.size(), c->poseidon_rc_gate);
   }
   return P2GPU_OK;
 }

@@ -4,7 +4,7 @@
 // -fsanitize=address,undefined (`make asan` -> libp2gpu_host_asan.so) for the fuzz tests: these are
 // the parsers that read untrusted bytes on machines with no GPU (the reference's `verify` action,
 // plonky2-backend/src/actions/verify_action.rs:11-17, reader noir_and_plonky2_serialization.rs:16-33).
-#include "circuit.hpp"
+#include "hostproof.hpp"
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
@@ -24,11 +24,6 @@ void set_err(const char *fmt, ...) {
   vsnprintf(buf, sizeof buf, fmt, ap);
   va_end(ap);
   g_err = buf;
-}
-thread_local HostHasher g_hh;
-void use_hasher(const p2gpu_circuit *c) {
-  g_hh.kind = c && c->hasher == 1;
-  g_hh.prc = c ? c->poseidon_rc : nullptr;
 }
 std::string last_error_copy() { return g_err; }
 void last_error_restore(const std::string &s) { g_err = s; }
@@ -230,11 +225,10 @@ int circuit_parse(const uint8_t *blob, size_t len, p2gpu_circuit *c, size_t *off
   off += 8 * (size_t)c->R;
   if (c->flags & 1) {
     memset(&c->circuit_digest, 0, sizeof(dig_t));
-    memcpy(c->circuit_digest.w, &h[32], c->hasher ? 32 : 25);
+    memcpy(c->circuit_digest.w, &h[32], digest_bytes(c->hasher));
   }
   poseidon_round_constants_host(c->poseidon_rc);
   poseidon_device_constants(c->poseidon_rc, c->poseidon_rc_gate);
-  use_hasher(c);
   *off_out = off;
   return P2GPU_OK;
 }
@@ -428,19 +422,8 @@ int p2gpu_build_blob(const p2gpu_build_params *bp, const p2gpu_gate_decl *gates,
 
 const char *p2gpu_last_error(void) { return g_err.c_str(); }
 
-size_t p2gpu_proof_size_bound(const p2gpu_circuit *c) {
-  if (!c) return 0;
-  const size_t ncap = (size_t)1 << c->cap_h;
-  const size_t ncs = c->NC + c->R, nzp = c->K * (1 + c->PP), nq = c->K * c->QF;
-  const size_t hb = c->hasher ? 32 : 25;
-  size_t sz = 3 * ncap * hb + 16 * (ncs + c->W + nzp + nq + c->K) + c->n_steps * ncap * hb;
-  size_t per_q = 8 * (ncs + c->W + nzp + nq) + 4 * (1 + hb * (size_t)(c->d + c->rate_bits));
-  for (uint32_t s = 0; s < c->n_steps; s++) per_q += (16u << c->arity[s]) + 1 + hb * (size_t)(c->d + c->rate_bits);
-  size_t n_final = c->n;
-  for (uint32_t s = 0; s < c->n_steps; s++) n_final >>= c->arity[s];
-  sz += per_q * c->num_queries + 16 * n_final + 8 + 8 * c->num_pi + 64;
-  return sz;
-}
+// the length of every proof of the circuit: the layout's, the one the serialiser writes against and the verifier asks for
+size_t p2gpu_proof_size_bound(const p2gpu_circuit *c) { return c ? layout_of(c).want : 0; }
 
 void p2gpu_circuit_destroy(p2gpu_circuit *c) {
   if (!c) return;
@@ -450,15 +433,15 @@ void p2gpu_circuit_destroy(p2gpu_circuit *c) {
 
 int p2gpu_circuit_cap(const p2gpu_circuit *c, uint8_t *out) {
   if (!c || !out) return P2GPU_E_ARG;
-  const size_t hb = c->hasher ? 32 : 25;
+  const size_t hb = digest_bytes(c->hasher);
   for (size_t i = 0; i < c->cs.cap.size(); i++) memcpy(out + hb * i, c->cs.cap[i].w, hb);
   return P2GPU_OK;
 }
 int p2gpu_circuit_device(const p2gpu_circuit *c) { return c ? c->device : P2GPU_E_ARG; }
-int p2gpu_circuit_hash_bytes(const p2gpu_circuit *c) { return c ? (c->hasher ? 32 : 25) : P2GPU_E_ARG; }
+int p2gpu_circuit_hash_bytes(const p2gpu_circuit *c) { return c ? (int)digest_bytes(c->hasher) : P2GPU_E_ARG; }
 int p2gpu_circuit_digest(const p2gpu_circuit *c, uint8_t *out) {
   if (!c || !out) return P2GPU_E_ARG;
-  memcpy(out, c->circuit_digest.w, c->hasher ? 32 : 25);
+  memcpy(out, c->circuit_digest.w, digest_bytes(c->hasher));
   return P2GPU_OK;
 }
 

@@ -1,6 +1,8 @@
-// hostproof.hpp -- host-side pieces shared by the verifier (verify.hip, verifydev.hip), the proof (de)compression (proofio.hip)
-// and the verifier-key file format (vkio.hip): a bounds-checked byte cursor for input of variable length, a growing byte sink
-// with the two-call output convention of the C ABI, and the handle's view for the verifier core (verifycore.hpp).
+// hostproof.hpp -- where the handle (circuit.hpp) meets the core (verifycore.hpp), for every host file that reads or writes
+// proof or key bytes: the verifier (verify.hip, verifydev.hip), the proof (de)compression (proofio.hip), the verifier-key file
+// format (vkio.hip), the prover's transcript and serialiser (prover.hip) and the handle's digest and size getters (handle.hip,
+// hostcore.hip).  A bounds-checked byte cursor for input of variable length, a growing byte sink with the two-call output
+// convention of the C ABI, the handle's view and layout for the core, and the core's hasher chosen by the handle's.
 #pragma once
 #include "circuit.hpp"
 #include "verifycore.hpp"
@@ -43,7 +45,7 @@ struct Out {
   void u8(uint8_t x) { v.push_back(x); }
   void u32(uint32_t x) { put(&x, 4); }
   void u64(uint64_t x) { put(&x, 8); }
-  void dig(const dig_t &d) { put(d.w, hh_bytes()); }
+  void dig(const dig_t &d, size_t hb) { put(d.w, hb); }  // hb: digest_bytes of the circuit's hasher
 };
 inline int emit(const std::vector<uint8_t> &v, uint8_t *out, size_t *out_len) {
   if (!out || *out_len < v.size()) {
@@ -71,6 +73,21 @@ inline vc::CircuitView view_of(const p2gpu_circuit *c) {
   v.gates = c->gates.data(); v.k_is = c->k_is.data(); v.cs_cap = c->cs.cap.data(); v.prc = c->poseidon_rc_gate;
   v.circuit_digest = c->circuit_digest;
   return v;
+}
+
+// every offset of the circuit's proofs, and their one length (`want`)
+inline vc::Layout layout_of(const p2gpu_circuit *c) { return vc::make_layout(view_of(c)); }
+
+// a cap the prover holds (Batch::cap) into a transcript
+template <int HK>
+inline void observe_cap(vc::Transcript<HK> &ch, const std::vector<dig_t> &cap) {
+  for (const dig_t &d : cap) ch.observe_digest(d);
+}
+
+// H::hash_no_pad of n > 4 words under the circuit's hasher (at that length the core's hash_or_noop hashes); prc: CircuitView::prc
+inline dig_t hash_no_pad(uint32_t hasher, const gl_t *v, uint32_t n, const gl_t *prc) {
+  const uint8_t *p = (const uint8_t *)v;
+  return hasher ? vc::leaf_digest_at<1>(p, 0, n, prc) : vc::leaf_digest_at<0>(p, 0, n, prc);
 }
 
 // ---- verify.hip: what p2gpu_verify_batch_host and p2gpu_verify_batch (verifydev.hip) share ----

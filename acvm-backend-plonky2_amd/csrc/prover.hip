@@ -8,9 +8,13 @@
 // sequence of HIP kernel launches on one stream, with the Fiat-Shamir
 // transcript (iop/challenger.rs, Keccak duplex) run on the host between
 // phases -- each challenge needs only a 16 x 25 B Merkle cap or a few hundred
-// opening values back from the device.  Transcript order: SURVEY.md C.4.
+// opening values back from the device.  Transcript order: SURVEY.md C.4; the
+// transcript, the hasher and the proof's byte layout are the verifier core's
+// (verifycore.hpp: vc::Transcript<HK>, vc::Layout), chosen once per proof by
+// the handle's hasher (prove_impl).
 // The product path never touches oracle/; without a HIP device every entry
 // point fails with P2GPU_E_DEVICE.
+#include "hostproof.hpp"
 #include "prover_internal.hpp"
 #include <chrono>
 
@@ -23,12 +27,12 @@ bool hostprof_on() {
   return on;
 }
 
-// What one proof carries from phase to phase (everything else is a local of the phase that uses it, or lives in the handle)
+// What one proof carries from phase to phase (everything else is a local of the phase that uses it, or lives in the handle;
+// the transcript is prove_phases' own and goes to the two phases that touch it as a parameter)
 struct Proof {
   const gl_t *wires_dev;  // the witness [W][n]
   const uint64_t *pis;
   uint32_t n_pi;
-  Challenger ch;
   gl_t pih[4];  // public_inputs_hash = InnerHasher(Poseidon).hash_no_pad(public_inputs); [] -> 0^4
   gl_t betas[MAX_CHALLENGES] = {0, 0}, gammas[MAX_CHALLENGES] = {0, 0}, alphas[MAX_CHALLENGES] = {0, 0};
   ext_t zeta;
@@ -360,7 +364,8 @@ int self_check(p2gpu_circuit *c, Proof &P) {
 
 // FRI commit phase: per reduction step the tree of the step's values, its cap into the transcript, the fold with the
 // step's challenge and the next LDE; then the final polynomial back to the host
-int fri_commit_steps(p2gpu_circuit *c, Proof &P) {
+template <int HK>
+int fri_commit_steps(p2gpu_circuit *c, Proof &P, vc::Transcript<HK> &ch) {
   hipStream_t st = c->stream;
   uint32_t ds = c->d;
   gl_t shift = GL_GEN;
@@ -369,8 +374,8 @@ int fri_commit_steps(p2gpu_circuit *c, Proof &P) {
     Batch &tr = c->fri_trees[s];
     hash_fri_leaves(st, c->fri_vals[s].p, ds, tr.ncl, ab, tr.dig.p, hprc(c));
     if (int rc = tree_build(c, tr, ((size_t)1 << ds) >> ab)) return rc;
-    P.ch.observe_cap(tr.cap);
-    const ext_t beta = P.ch.get_ext();
+    observe_cap(ch, tr.cap);
+    const ext_t beta = ch.get_ext();
     fri_fold(st, c->fri_coef[s].p, ds, ab, beta, c->fri_coef[s + 1].p);
     for (uint32_t q = 0; q < ab; q++) shift = gl_sqr(shift);
     ds -= ab;
@@ -394,14 +399,13 @@ int fri_commit_steps(p2gpu_circuit *c, Proof &P) {
   return 0;
 }
 
-// PoW: minimum-witness policy (upstream's parallel find_any is not deterministic)
-int grind(p2gpu_circuit *c, Proof &P) {
+// PoW: minimum-witness policy (upstream's parallel find_any is not deterministic).  The kernel continues from the
+// transcript's sponge as it stands: the n_in pending observations already lie in the state (vc::Transcript).
+template <int HK>
+int grind(p2gpu_circuit *c, Proof &P, const vc::Transcript<HK> &ch) {
   P.pow_witness = c->pow_hint;
   if (P.pow_witness != UINT64_MAX) return 0;
   hipStream_t st = c->stream;
-  gl_t inter[12];
-  memcpy(inter, P.ch.state, sizeof inter);
-  for (int i = 0; i < P.ch.n_in; i++) inter[i] = P.ch.in[i];
   // expected minimum witness ~2^pow_bits: start with 2^(pow_bits+1) candidates, then double
   uint64_t batch = 1ull << (c->pow_bits + 1 < 20 ? c->pow_bits + 1 : 20);
   // sharded: the ranks grind disjoint slices of [base, base + batch) and take the minimum of what
@@ -418,7 +422,7 @@ int grind(p2gpu_circuit *c, Proof &P) {
     const uint64_t per = (batch + ranks - 1) / ranks;
     const uint64_t my0 = base + per * (uint64_t)(split ? c->shard_rank : 0);
     const uint64_t myn = my0 >= base + batch ? 0 : std::min(per, base + batch - my0);
-    if (myn) pow_search(st, inter, (uint32_t)P.ch.n_in, c->pow_bits, my0, myn, c->pow_result.p, hprc(c));
+    if (myn) pow_search(st, ch.st.p, ch.n_in, c->pow_bits, my0, myn, c->pow_result.p, hprc(c));
     const unsigned long long *result = c->pow_result.p;
     if (split) {
       if (int rc = shard_allgather(c, c->pow_result.p, c->xchg_recv.p, 8)) return rc;
@@ -549,15 +553,13 @@ int answer_queries(p2gpu_circuit *c, Proof &P) {
   return 0;
 }
 
-// proof bytes, written through a cursor into storage that outlives the proof (the caller's buffer when it is large enough,
-// else the handle's): a fresh 200 KB vector per proof is an mmap, its page faults and an munmap -- 20 of the serialiser's 45 us
+// proof bytes, written through a cursor straight into the caller's buffer, which holds the layout's `want` bytes (serialise).
+// A write past `cap` is counted, not made: the finished length says whether the proof is the layout's.
 struct Buf {
-  uint8_t *base = nullptr;
-  size_t len = 0, cap = 0;
-  bool overflow = false;
+  uint8_t *base;
+  size_t len, cap, hb;  // hb: bytes of a digest (Layout::hb)
   void put(const void *p, size_t n) {
-    if (len + n > cap) { overflow = true; return; }
-    memcpy(base + len, p, n);
+    if (len <= cap && n <= cap - len) memcpy(base + len, p, n);
     len += n;
   }
   void u64(uint64_t x) { put(&x, 8); }
@@ -565,7 +567,7 @@ struct Buf {
     u64(e.c0);
     u64(e.c1);
   }
-  void dig(const dig_t &d) { put(d.w, hh_bytes()); }
+  void dig(const dig_t &d) { put(d.w, hb); }
 };
 
 // plonky2 ProofWithPublicInputs::to_bytes
@@ -610,32 +612,28 @@ void write_proof(const p2gpu_circuit *c, const Proof &P, Buf &out) {
 }
 
 // ---- serialise: the proof bytes to the caller, the timings closed behind them ----
+// Every proof of the circuit has the layout's length (vc::Layout::want, what p2gpu_proof_size_bound returns): a shorter buffer
+// is refused with that length, a buffer at least as long is written in place.
 int serialise(p2gpu_circuit *c, Proof &P, uint8_t *proof_out, size_t *proof_len, p2gpu_timings *tm) {
-  Buf out;
-  out.cap = p2gpu_proof_size_bound(c);
-  if (*proof_len >= out.cap) {
-    out.base = proof_out;
-  } else {
-    if (c->h_out.size() < out.cap) c->h_out.resize(out.cap);
-    out.base = c->h_out.data();
-  }
-  write_proof(c, P, out);
+  const vc::Layout L = layout_of(c);
+  const bool fits = *proof_len >= L.want;
+  Buf out{proof_out, 0, L.want, L.hb};
+  if (fits) write_proof(c, P, out);
   P.T.fri_ms = lap(P);
   P.T.total_ms = P.T.wires_commit_ms + P.T.zs_commit_ms + P.T.quotient_ms + P.T.openings_ms + P.T.fri_ms;
   // event pairs are read back lazily (p2gpu_kernel_stats), so profiling adds no synchronisation to
   // the proof itself; bound the backlog
   if (c->profile && c->pending.size() > 16384) flush_kstats(c);
   if (tm) *tm = P.T;
-  if (out.overflow) {
-    set_err("internal: proof longer than p2gpu_proof_size_bound");
-    return P2GPU_E_DEVICE;
-  }
-  if (out.len > *proof_len) {
-    *proof_len = out.len;
-    set_err("proof buffer too small: need %zu bytes", out.len);
+  if (!fits) {
+    *proof_len = L.want;
+    set_err("proof buffer too small: need %zu bytes", L.want);
     return P2GPU_E_BUFFER;
   }
-  if (out.base != proof_out) memcpy(proof_out, out.base, out.len);
+  if (out.len != L.want) {
+    set_err("internal: serialised %zu proof bytes, the circuit's layout has %zu", out.len, L.want);
+    return P2GPU_E_DEVICE;
+  }
   *proof_len = out.len;
   g_hp.mark("serialise");
   g_hp.dump();
@@ -743,34 +741,38 @@ void flush_kstats(p2gpu_circuit *c) {
 }
 
 // The proof of one witness on one handle: the phases above in the order of SURVEY.md C.4, the transcript between them
-int prove_impl(p2gpu_circuit *c, const gl_t *wires_dev, const uint64_t *pis, uint32_t n_pi, uint8_t *proof_out, size_t *proof_len,
-               p2gpu_timings *tm, double h2d_ms) {
+template <int HK>
+static int prove_phases(p2gpu_circuit *c, const gl_t *wires_dev, const uint64_t *pis, uint32_t n_pi, uint8_t *proof_out, size_t *proof_len,
+                        p2gpu_timings *tm, double h2d_ms) {
   if (int rc = check_public_inputs(c, pis, n_pi)) return rc;
   HIP_TRY(hipSetDevice(c->device));
   ProfGuard prof(c);
   Proof P(c, wires_dev, pis, n_pi, h2d_ms);
-  Challenger &ch = P.ch;
+  // the core permutes with the round constants in their poseidon_device_constants form (CircuitView::prc); poseidon_permute_host
+  // adds all twelve words of a round, so that form and poseidon_rc give the same permutation on the host
+  gl_t sponge[12];
+  vc::Transcript<HK> ch{vc::Strided<gl_t>{sponge, 1}, c->poseidon_rc_gate};
+  ch.init();
   const uint32_t K = c->K;
   poseidon_hash_no_pad_host(pis, n_pi, P.pih, c->poseidon_rc);
   c->pin.reset();
-  use_hasher(c);
   P.vfirst = virt_first(c);
 
   if (int rc = commit_wires(c, P)) return rc;
   ch.observe_digest(c->circuit_digest);
   for (int i = 0; i < 4; i++) ch.observe(P.pih[i]);
-  ch.observe_cap(c->wires.cap);
+  observe_cap(ch, c->wires.cap);
   for (uint32_t k = 0; k < K; k++) P.betas[k] = ch.get();
   for (uint32_t k = 0; k < K; k++) P.gammas[k] = ch.get();
   P.T.wires_commit_ms = lap(P);
 
   if (int rc = commit_zs(c, P)) return rc;
-  ch.observe_cap(c->zp.cap);
+  observe_cap(ch, c->zp.cap);
   for (uint32_t k = 0; k < K; k++) P.alphas[k] = ch.get();
   P.T.zs_commit_ms = lap(P);
 
   if (int rc = commit_quotient(c, P)) return rc;
-  ch.observe_cap(c->quot.cap);
+  observe_cap(ch, c->quot.cap);
   P.zeta = ch.get_ext();
   P.T.quotient_ms = lap(P);
 
@@ -782,11 +784,11 @@ int prove_impl(p2gpu_circuit *c, const gl_t *wires_dev, const uint64_t *pis, uin
   const ext_t fri_alpha = ch.get_ext();
   if (int rc = fri_reduce(c, P, fri_alpha)) return rc;
   if (int rc = self_check(c, P)) return rc;
-  if (int rc = fri_commit_steps(c, P)) return rc;  // observes each step's cap, draws each step's beta
+  if (int rc = fri_commit_steps(c, P, ch)) return rc;  // observes each step's cap, draws each step's beta
   for (const ext_t &e : P.final_poly) ch.observe_ext(e);
   TRACE(c, "fri commit phase");
 
-  if (int rc = grind(c, P)) return rc;
+  if (int rc = grind(c, P, ch)) return rc;
   ch.observe(P.pow_witness);
   const gl_t pow_resp = ch.get();
   if (c->pow_bits && (pow_resp >> (64 - c->pow_bits)) != 0) {
@@ -801,6 +803,11 @@ int prove_impl(p2gpu_circuit *c, const gl_t *wires_dev, const uint64_t *pis, uin
   if (int rc = answer_queries(c, P)) return rc;
 
   return serialise(c, P, proof_out, proof_len, tm);
+}
+int prove_impl(p2gpu_circuit *c, const gl_t *wires_dev, const uint64_t *pis, uint32_t n_pi, uint8_t *proof_out, size_t *proof_len,
+               p2gpu_timings *tm, double h2d_ms) {
+  return c->hasher ? prove_phases<1>(c, wires_dev, pis, n_pi, proof_out, proof_len, tm, h2d_ms)
+                   : prove_phases<0>(c, wires_dev, pis, n_pi, proof_out, proof_len, tm, h2d_ms);
 }
 
 // p2gpu_plonk_stages behind its argument checks: phases 1-3 of prove_impl -- the same phase functions -- with the caller's
@@ -817,9 +824,9 @@ int plonk_stages_impl(p2gpu_circuit *c, const uint64_t *wires, const uint64_t *p
   for (int i = 0; i < 4; i++) P.pih[i] = pi_hash[i];
   for (uint32_t k = 0; k < c->K; k++) { P.betas[k] = betas[k]; P.gammas[k] = gammas[k]; P.alphas[k] = alphas[k]; }
   c->pin.reset();
-  use_hasher(c);
   P.vfirst = virt_first(c);
-  const size_t hb = c->hasher ? 32 : 25, ncap = (size_t)1 << c->cap_h;
+  const vc::Layout L = layout_of(c);
+  const size_t hb = L.hb, ncap = L.ncap;
   auto put_cap = [&](int which, const Batch &b) {
     for (size_t i = 0; i < ncap; i++) memcpy(caps_out + (which * ncap + i) * hb, b.cap[i].w, hb);
   };

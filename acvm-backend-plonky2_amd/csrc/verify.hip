@@ -101,7 +101,7 @@ int p2gpu_verifier_create(const uint8_t *blob, size_t len, p2gpu_circuit **out) 
   c->cs.cap.resize((size_t)1 << c->cap_h);
   for (size_t i = 0; i < c->cs.cap.size(); i++) {
     memset(&c->cs.cap[i], 0, sizeof(dig_t));
-    memcpy(c->cs.cap[i].w, cap_in + 32 * i, c->hasher ? 32 : 25);
+    memcpy(c->cs.cap[i].w, cap_in + 32 * i, digest_bytes(c->hasher));
   }
   if (c->hasher) {  // Poseidon digests are field elements: canonical encodings only (as verifycore.hpp ld_digest asks of a proof)
     bool canon = true;
@@ -135,7 +135,7 @@ int p2gpu_circuit_export_vk(const p2gpu_circuit *c, uint8_t *out, size_t *len) t
   h[13] = c->n_steps;
   for (int i = 0; i < 8; i++) h[14 + i] = c->arity[i];
   h[22] = c->hasher; h[23] = c->num_gates; h[24] = c->num_pi; h[25] = 3; h[26] = c->PP;
-  memcpy(&h[32], c->circuit_digest.w, c->hasher ? 32 : 25);
+  memcpy(&h[32], c->circuit_digest.w, digest_bytes(c->hasher));
   memcpy(out, h, sizeof h);
   size_t off = 256;
   for (const GateDesc &G : c->gates) {
@@ -150,7 +150,7 @@ int p2gpu_circuit_export_vk(const p2gpu_circuit *c, uint8_t *out, size_t *len) t
   }
   for (size_t i = 0; i < ncap; i++) {
     memset(out + off, 0, 32);
-    memcpy(out + off, c->cs.cap[i].w, c->hasher ? 32 : 25);
+    memcpy(out + off, c->cs.cap[i].w, digest_bytes(c->hasher));
     off += 32;
   }
   memcpy(out + off, c->k_is.data(), 8 * (size_t)c->R);

@@ -8,6 +8,9 @@
 //                                       polynomial at the folded point
 // Both return a reason code (0: passed); reason_text() below holds the wording of every code, once.  Their parts that the proof
 // formats need too (proofio.hip) have names of their own: well_formed, head_challenges, query_initial, fold_step.
+// The prover (prover.hip) writes what these functions read: its Fiat-Shamir transcript is Transcript<HK> below, it serialises
+// against make_layout (digest width `hb`, finished length `want` = p2gpu_proof_size_bound), and the handle's circuit digest is
+// leaf_digest_at<HK> (handle.hip, through hostproof.hpp) -- one statement of hasher, transcript and layout for both sides.
 //
 // WHAT NO PROOF BYTE CAN DO: move a read.  The length of a proof is fixed by its circuit (make_layout: `want`), and a proof
 // of another length never reaches these functions (shape_reason answers for it).  After that every read of the proof is at

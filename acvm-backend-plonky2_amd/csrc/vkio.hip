@@ -116,8 +116,9 @@ int vk_write(const p2gpu_circuit *c, VkOut &o) {
   }
   // VerifierOnlyCircuitData comes LAST (write_verifier_circuit_data: common, then verifier_only)
   o.usize(c->cap_h);
-  for (auto &dg : c->cs.cap) o.dig(dg);
-  o.dig(c->circuit_digest);
+  const size_t hb = digest_bytes(c->hasher);
+  for (auto &dg : c->cs.cap) o.dig(dg, hb);
+  o.dig(c->circuit_digest, hb);
   return P2GPU_OK;
 }
 
@@ -155,7 +156,7 @@ bool vk_read_fri_config(VkIn &in, VkFri &f) {
 int vk_read(const uint8_t *bytes, size_t len, int hasher, Out &blob) {
   VkIn in;
   in.p = bytes; in.len = len;
-  const size_t hb = hasher ? 32 : 25;
+  const size_t hb = digest_bytes((uint32_t)hasher);
   auto fail = [](const char *what) { set_err("malformed verifier key: %s", what); return P2GPU_E_BLOB; };
   uint32_t h[64];
   memset(h, 0, sizeof h);
@@ -267,7 +268,6 @@ extern "C" {
 // ---- verifier key in the reference's file format (UNPINNED restatement, see the head of this file) ----
 int p2gpu_circuit_export_vk_plonky2(const p2gpu_circuit *c, uint8_t *out, size_t *out_len) try {
   if (!c || !out_len) return P2GPU_E_ARG;
-  use_hasher(c);
   VkOut o;
   if (int rc = vk_write(c, o)) return rc;
   return emit(o, out, out_len);

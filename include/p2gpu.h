@@ -141,7 +141,8 @@ int p2gpu_circuit_cap(const p2gpu_circuit *c, uint8_t *out);
 int p2gpu_circuit_digest(const p2gpu_circuit *c, uint8_t *out);
 /* HIP device index the handle lives on (< 0: verifier-only handle / bad argument) */
 int p2gpu_circuit_device(const p2gpu_circuit *c);
-/* upper bound of the proof size in bytes for this circuit */
+/* The size in bytes of every proof of this circuit: a proof's length is fixed by its circuit (the value p2gpu_verify
+ * asks of a proof), so a buffer of this size always suffices and a shorter one is refused with P2GPU_E_BUFFER. */
 size_t p2gpu_proof_size_bound(const p2gpu_circuit *c);
 
 /* wires: host pointer, [num_wires][n] column-major.  proof_len: in = capacity,
