@@ -6,6 +6,7 @@
 #pragma once
 #include "circuit.hpp"
 #include "verifycore.hpp"
+#include "decompresscore.hpp"
 
 namespace p2 {
 
@@ -91,10 +92,18 @@ inline dig_t hash_no_pad(uint32_t hasher, const gl_t *v, uint32_t n, const gl_t 
 }
 
 // ---- verify.hip: what p2gpu_verify_batch_host and p2gpu_verify_batch (verifydev.hip) share ----
-// the refusals that need no device (P2GPU_E_ARG; 0: the call may go on)
-int verify_batch_args(const p2gpu_circuit *c, const uint8_t *proofs, const size_t *offsets, size_t batch, const p2gpu_verify_report *reports);
+// the refusals that need no device (P2GPU_E_ARG; 0: the call may go on); reports: the per-proof output, whatever its type
+int verify_batch_args(const p2gpu_circuit *c, const uint8_t *proofs, const size_t *offsets, size_t batch, const void *reports);
 void verify_report_fill(p2gpu_verify_report *r, const vc::Verdict &v);
 int verify_batch_finish(size_t batch, const size_t *offsets, const vc::Layout &L, const p2gpu_verify_report *reports);
 vc::Verdict verify_one_host(const vc::CircuitView &v, const vc::Layout &L, const uint8_t *proof, size_t len, std::vector<ext_t> &terms);
+
+// ---- decompressbatch.hip: what the entry points for a batch of compressed proofs share (decompressdev.hip has the device's) ----
+// The container walk of every proof.  slot: the batch index of each proof that goes on to the core, tabs: their offset tables
+// back to back (dc::table_words each); reason[b]: for every other proof its verdict from the lone path, a dc::VR_C_* code.
+int cbatch_walk(const p2gpu_circuit *c, const vc::CircuitView &v, const vc::Layout &L, const uint8_t *cproofs, const size_t *offsets, size_t batch,
+                std::vector<uint32_t> &reason, std::vector<size_t> &slot, std::vector<uint32_t> &tabs);
+// p2gpu_last_error for the lowest failing proof, in p2gpu_verify_compressed's words; the batch's return code
+int cbatch_finish(size_t batch, const p2gpu_verify_report *reports);
 
 }  // namespace p2

@@ -39,7 +39,7 @@ bool plonk_identity_holds(const p2gpu_circuit *c, const std::vector<ext_t> &op, 
 }
 
 // ---- what the batch entry points share (p2gpu_verify_batch_host below, p2gpu_verify_batch in verifydev.hip) ----
-int verify_batch_args(const p2gpu_circuit *c, const uint8_t *proofs, const size_t *offsets, size_t batch, const p2gpu_verify_report *reports) {
+int verify_batch_args(const p2gpu_circuit *c, const uint8_t *proofs, const size_t *offsets, size_t batch, const void *reports) {
   if (!c || !proofs || !offsets || !reports || batch == 0) return P2GPU_E_ARG;
   for (size_t b = 0; b < batch; b++)
     if (offsets[b + 1] < offsets[b]) {
@@ -189,7 +189,8 @@ int p2gpu_verify_batch_host(const p2gpu_circuit *c, const uint8_t *proofs, const
 
 int p2gpu_verify_reason(const p2gpu_verify_report *r, char *out, size_t cap) {
   if (!r || !out || cap == 0) return P2GPU_E_ARG;
-  const int n = vc::reason_text(r->reason, r->query, r->index, out, cap);
+  const char *words = dc::reason_words(r->reason);  // a reject site of the decompression: the text behind "malformed proof: "
+  const int n = words ? snprintf(out, cap, "%s", words) : vc::reason_text(r->reason, r->query, r->index, out, cap);
   if (n < 0 || (size_t)n >= cap) {
     set_err("p2gpu_verify_reason: the text needs %d bytes", n + 1);
     return P2GPU_E_BUFFER;

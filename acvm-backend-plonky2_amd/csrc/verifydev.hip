@@ -15,25 +15,17 @@
 // the buffer padded so that the aligned words ld64() reads are inside it.
 // Proofs of another length than the circuit's get their verdict on the host and are not uploaded.  Scratch, the proofs and the
 // circuit's share (gate table, cap, k_is, round constants: a few kilobytes) are allocated per call and freed before it returns.
-#include "hostproof.hpp"
-#include "prover_internal.hpp"
+// The entry points for compressed proofs (decompressdev.hip) end in the query and verdict kernels of this file: launch_queries,
+// the device and the circuit's upload are shared through verifydev.hpp, and DevArgs::cflags carries what the decompression found.
+#include "verifydev.hpp"
 
 using namespace p2;
+using p2::vdev::CallState;
+using p2::vdev::DevArgs;
 
 namespace {
 
-struct DevArgs {
-  vc::CircuitView c;  // device pointers
-  vc::Layout L;
-  const uint8_t *proofs;  // [m] proofs of L.want bytes, back to back
-  uint32_t m;
-  gl_t *sponge;            // [12][m]
-  ext_t *terms;            // [identity_terms][m]
-  vc::HeadRecord *rec;     // [m]
-  uint32_t *head_reason;   // [m]
-  uint32_t *query_reason;  // [m * num_queries][2]: reason, oracle / step
-  uint32_t *verdict;       // [m][3]: reason, query, index
-};
+const char *const VB_ENTRY = "p2gpu_verify_batch";
 
 template <int HK>
 __global__ __launch_bounds__(64) void verify_head_kernel(const DevArgs a) {
@@ -47,7 +39,7 @@ template <int HK>
 __global__ __launch_bounds__(64) void verify_query_kernel(const DevArgs a) {
   const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x, nq = a.c.num_queries;
   const uint32_t b = lane / nq, q = lane - b * nq;
-  if (b >= a.m || a.head_reason[b] != vc::VR_OK) return;
+  if (b >= a.m || a.head_reason[b] != vc::VR_OK || (a.cflags && a.cflags[b])) return;
   uint32_t index = vc::VR_NONE;
   const uint32_t r = vc::verify_query<HK>(a.c, a.L, a.proofs + (size_t)b * a.L.want, a.rec + b, q, &index);
   a.query_reason[2 * (size_t)lane] = r;
@@ -57,7 +49,8 @@ __global__ __launch_bounds__(64) void verify_query_kernel(const DevArgs a) {
 __global__ __launch_bounds__(64) void verify_verdict_kernel(const DevArgs a) {
   const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x, nq = a.c.num_queries;
   if (b >= a.m) return;
-  uint32_t reason = a.head_reason[b], query = vc::VR_NONE, index = vc::VR_NONE;
+  // a compressed proof: the container, the indices against the transcript's, the initial paths, the step paths -- then the head
+  uint32_t reason = a.cflags && a.cflags[b] ? dc::flags_reason(a.cflags[b]) : a.head_reason[b], query = vc::VR_NONE, index = vc::VR_NONE;
   if (reason == vc::VR_OK)
     for (uint32_t q = 0; q < nq; q++) {
       const uint32_t r = a.query_reason[2 * ((size_t)b * nq + q)];
@@ -73,53 +66,57 @@ __global__ __launch_bounds__(64) void verify_verdict_kernel(const DevArgs a) {
   a.verdict[3 * (size_t)b + 2] = index;
 }
 
-// what one call allocates: freed, the stream of a verifier-only handle destroyed and the caller's device selected again when it ends
-struct CallState {
-  std::vector<void *> ptrs;
-  hipStream_t own_stream = nullptr;
-  int prev_device = -1;
-  ~CallState() {
-    for (void *p : ptrs) (void)hipFree(p);
-    if (own_stream) (void)hipStreamDestroy(own_stream);
-    if (prev_device >= 0) (void)hipSetDevice(prev_device);
-  }
-  template <class T> T *alloc(size_t n) {
-    void *p = nullptr;
-    if (hipMalloc(&p, (n ? n : 1) * sizeof(T)) != hipSuccess) {
-      (void)hipGetLastError();
-      return nullptr;
-    }
-    ptrs.push_back(p);
-    return (T *)p;
-  }
-};
-
-int device_fail(const char *what, hipError_t e) {
-  (void)hipGetLastError();
-  set_err("p2gpu_verify_batch: %s: %s", what, hipGetErrorString(e));
-  return P2GPU_E_DEVICE;
+void launch_head(const DevArgs &a, hipStream_t st) {
+  ProfScope ps("verify_head_kernel", (double)a.L.queries_at * a.m);
+  if (a.c.hasher) hipLaunchKernelGGL(verify_head_kernel<1>, dim3((a.m + 63) / 64), dim3(64), 0, st, a);
+  else hipLaunchKernelGGL(verify_head_kernel<0>, dim3((a.m + 63) / 64), dim3(64), 0, st, a);
 }
-#define VB_TRY(expr, what)                              \
-  do {                                                  \
-    const hipError_t e_ = (expr);                       \
-    if (e_ != hipSuccess) return device_fail(what, e_); \
-  } while (0)
 
-template <int HK>
-void launch(const DevArgs &a, hipStream_t st) {
+}  // namespace
+
+namespace p2 {
+namespace vdev {
+
+void launch_queries(const DevArgs &a, hipStream_t st) {
   const uint32_t lanes = a.m * a.c.num_queries;
   {
-    ProfScope ps("verify_head_kernel", (double)a.L.queries_at * a.m);
-    hipLaunchKernelGGL(verify_head_kernel<HK>, dim3((a.m + 63) / 64), dim3(64), 0, st, a);
-  }
-  {
     ProfScope ps("verify_query_kernel", (double)a.L.query_bytes * lanes);
-    hipLaunchKernelGGL(verify_query_kernel<HK>, dim3((lanes + 63) / 64), dim3(64), 0, st, a);
+    if (a.c.hasher) hipLaunchKernelGGL(verify_query_kernel<1>, dim3((lanes + 63) / 64), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(verify_query_kernel<0>, dim3((lanes + 63) / 64), dim3(64), 0, st, a);
   }
   hipLaunchKernelGGL(verify_verdict_kernel, dim3((a.m + 63) / 64), dim3(64), 0, st, a);
 }
 
-}  // namespace
+int open_device(const char *VB_ENTRY, const p2gpu_circuit *c, CallState &S, hipStream_t *st) {
+  int prev = 0;
+  VB_TRY(hipGetDevice(&prev), "query the device");
+  S.prev_device = prev;
+  VB_TRY(hipSetDevice(c->device >= 0 ? c->device : g_devices[0]), "select the device");
+  if (c->device >= 0) *st = c->stream;
+  else {
+    VB_TRY(hipStreamCreateWithFlags(&S.own_stream, hipStreamNonBlocking), "create a stream");
+    *st = S.own_stream;
+  }
+  return 0;
+}
+
+int upload_circuit(const char *VB_ENTRY, CallState &S, const vc::CircuitView &hv, vc::CircuitView *dv, hipStream_t st) {
+  const size_t ncap = (size_t)1 << hv.cap_h;
+  GateDesc *d_gates = S.alloc<GateDesc>(hv.num_gates);
+  gl_t *d_kis = S.alloc<gl_t>(hv.R), *d_prc = S.alloc<gl_t>(360);
+  dig_t *d_cap = S.alloc<dig_t>(ncap);
+  if (!d_gates || !d_kis || !d_prc || !d_cap) return device_fail(VB_ENTRY, "scratch", hipErrorOutOfMemory);
+  *dv = hv;
+  dv->gates = d_gates; dv->k_is = d_kis; dv->prc = d_prc; dv->cs_cap = d_cap;
+  VB_TRY(hipMemcpyAsync(d_gates, hv.gates, sizeof(GateDesc) * hv.num_gates, hipMemcpyHostToDevice, st), "copy the gate table");
+  if (hv.R) VB_TRY(hipMemcpyAsync(d_kis, hv.k_is, 8 * (size_t)hv.R, hipMemcpyHostToDevice, st), "copy k_is");
+  VB_TRY(hipMemcpyAsync(d_prc, hv.prc, 8 * 360, hipMemcpyHostToDevice, st), "copy the round constants");
+  VB_TRY(hipMemcpyAsync(d_cap, hv.cs_cap, sizeof(dig_t) * ncap, hipMemcpyHostToDevice, st), "copy the cap");
+  return 0;
+}
+
+}  // namespace vdev
+}  // namespace p2
 
 extern "C" int p2gpu_verify_batch(const p2gpu_circuit *c, const uint8_t *proofs, const size_t *offsets, size_t batch,
                                   p2gpu_verify_report *reports) try {
@@ -144,46 +141,30 @@ extern "C" int p2gpu_verify_batch(const p2gpu_circuit *c, const uint8_t *proofs,
   const uint32_t m = (uint32_t)slot.size();
   CallState S;
   hipStream_t st = nullptr;
-  if (m) {
-    int prev = 0;
-    VB_TRY(hipGetDevice(&prev), "query the device");
-    S.prev_device = prev;
-    VB_TRY(hipSetDevice(c->device >= 0 ? c->device : g_devices[0]), "select the device");
-    if (c->device >= 0) st = c->stream;
-    else {
-      VB_TRY(hipStreamCreateWithFlags(&S.own_stream, hipStreamNonBlocking), "create a stream");
-      st = S.own_stream;
-    }
-  }
+  if (m)
+    if (int rc = vdev::open_device(VB_ENTRY, c, S, &st)) return rc;
   if (m) {
     // the "profile" knob of a prover handle times the launches below like every other launch on its stream: the kernel
     // statistics are the one part of a handle this call changes (include/p2gpu.h says so), hence the cast
     p2gpu_circuit *pc = c->device >= 0 ? const_cast<p2gpu_circuit *>(c) : nullptr;
     std::unique_ptr<ProfGuard> prof(pc && pc->profile ? new ProfGuard(pc) : nullptr);
-    const size_t ncap = L.ncap, nterms = vc::identity_terms(hv), lanes = (size_t)m * hv.num_queries;
+    const size_t nterms = vc::identity_terms(hv), lanes = (size_t)m * hv.num_queries;
     const size_t proof_bytes = (size_t)m * L.want;
     DevArgs a;
-    a.c = hv;
     a.L = L;
     a.m = m;
+    a.cflags = nullptr;
     uint8_t *d_proofs = S.alloc<uint8_t>(proof_bytes + 16);
-    GateDesc *d_gates = S.alloc<GateDesc>(hv.num_gates);
-    gl_t *d_kis = S.alloc<gl_t>(hv.R), *d_prc = S.alloc<gl_t>(360);
-    dig_t *d_cap = S.alloc<dig_t>(ncap);
     a.sponge = S.alloc<gl_t>(12 * (size_t)m);
     a.terms = S.alloc<ext_t>(nterms * m);
     a.rec = S.alloc<vc::HeadRecord>(m);
     a.head_reason = S.alloc<uint32_t>(m);
     a.query_reason = S.alloc<uint32_t>(2 * lanes);
     a.verdict = S.alloc<uint32_t>(3 * (size_t)m);
-    if (!d_proofs || !d_gates || !d_kis || !d_prc || !d_cap || !a.sponge || !a.terms || !a.rec || !a.head_reason || !a.query_reason || !a.verdict)
-      return device_fail("scratch", hipErrorOutOfMemory);
+    if (!d_proofs || !a.sponge || !a.terms || !a.rec || !a.head_reason || !a.query_reason || !a.verdict)
+      return vdev::device_fail(VB_ENTRY, "scratch", hipErrorOutOfMemory);
     a.proofs = d_proofs;
-    a.c.gates = d_gates; a.c.k_is = d_kis; a.c.prc = d_prc; a.c.cs_cap = d_cap;
-    VB_TRY(hipMemcpyAsync(d_gates, hv.gates, sizeof(GateDesc) * hv.num_gates, hipMemcpyHostToDevice, st), "copy the gate table");
-    if (hv.R) VB_TRY(hipMemcpyAsync(d_kis, hv.k_is, 8 * (size_t)hv.R, hipMemcpyHostToDevice, st), "copy k_is");
-    VB_TRY(hipMemcpyAsync(d_prc, hv.prc, 8 * 360, hipMemcpyHostToDevice, st), "copy the round constants");
-    VB_TRY(hipMemcpyAsync(d_cap, hv.cs_cap, sizeof(dig_t) * ncap, hipMemcpyHostToDevice, st), "copy the cap");
+    if (int rc = vdev::upload_circuit(VB_ENTRY, S, hv, &a.c, st)) return rc;
     VB_TRY(hipMemsetAsync(d_proofs + proof_bytes, 0, 16, st), "clear the padding");
     // proofs that lie back to back in the caller's buffer go up in one copy
     for (uint32_t i = 0; i < m;) {
@@ -193,8 +174,8 @@ extern "C" int p2gpu_verify_batch(const p2gpu_circuit *c, const uint8_t *proofs,
              "copy the proofs");
       i = j;
     }
-    if (hv.hasher) launch<1>(a, st);
-    else launch<0>(a, st);
+    launch_head(a, st);
+    vdev::launch_queries(a, st);
     VB_TRY(hipGetLastError(), "launch");
     std::vector<uint32_t> verdict(3 * (size_t)m);
     VB_TRY(hipMemcpyAsync(verdict.data(), a.verdict, 12 * (size_t)m, hipMemcpyDeviceToHost, st), "read the verdicts");

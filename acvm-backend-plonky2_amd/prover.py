@@ -68,7 +68,9 @@ class VerifyReport:
     """The verdict on one proof of a batch (``p2gpu_verify_batch``).  `ok`; `reason`: the P2GPU_VR_* code of the check that
     failed (0: none); `query`, `index`: the query and the initial oracle or fold step the reason names, None where it names
     none (for a wrong length: the length given and the length the circuit fixes); `message`: the words of ``verify``'s error
-    behind "proof rejected: " ("accepted" for a valid proof)."""
+    behind "proof rejected: " ("accepted" for a valid proof).  For a compressed proof (``p2gpu_verify_batch_compressed``) the
+    reason may also be a P2GPU_VR_C_* code, a reject site of the decompression (16 and up): `message` is then the words of
+    ``verify_compressed``'s error behind "malformed proof: "."""
 
     def __init__(self, raw, message):
         self.ok, self.reason, self.message = raw.status == 0, int(raw.reason), message
@@ -188,6 +190,9 @@ def load_library():
     lib.p2gpu_verify_batch.argtypes = [vp, u8p, vp, sz, vp]
     lib.p2gpu_verify_batch_host.argtypes = [vp, u8p, vp, sz, vp]
     lib.p2gpu_verify_reason.argtypes = [vp, ctypes.c_char_p, sz]
+    lib.p2gpu_verify_batch_compressed.argtypes = [vp, u8p, vp, sz, vp]
+    lib.p2gpu_verify_batch_compressed_host.argtypes = [vp, u8p, vp, sz, vp]
+    lib.p2gpu_proof_decompress_batch.argtypes = [vp, u8p, vp, sz, vp, vp]
     lib.p2gpu_circuit_export_vk.argtypes = [vp, u8p, ctypes.POINTER(sz)]
     lib.p2gpu_circuit_export_vk_plonky2.argtypes = [vp, u8p, ctypes.POINTER(sz)]
     lib.p2gpu_verifier_create_plonky2.argtypes = [u8p, sz, ctypes.c_int, ctypes.POINTER(vp)]
@@ -679,6 +684,16 @@ class CircuitData:
         raises nothing; P2GpuError is for argument and device errors."""
         return _verify_batch(self._lib, self._h, proofs, True)
 
+    def verify_batch_compressed(self, proofs):
+        """``p2gpu_verify_batch_compressed`` on this handle's device and stream: ``verify_batch`` for compressed proofs (the
+        on-disk format), decompressed on the device; the verdict of each is ``verify_compressed``'s."""
+        return _verify_batch(self._lib, self._h, proofs, True, compressed=True)
+
+    def decompress_batch(self, proofs):
+        """``p2gpu_proof_decompress_batch``: the device's decompression of each compressed proof, read back -- per member a
+        :class:`ProofWithPublicInputs` with the bytes of ``decompress``, or the :class:`P2GpuError` ``decompress`` raises."""
+        return _decompress_batch(self._lib, self._h, proofs)
+
     def verifier_data(self):
         """``circuit_data.verifier_data()``: the verifier's share of the circuit."""
         return VerifierCircuitData(self.verifier_blob())
@@ -930,13 +945,21 @@ def _verify(lib, handle, proof):
     _check(lib.p2gpu_verify(handle, buf.ctypes.data if buf.size else None, buf.size))
 
 
-def _verify_batch(lib, handle, proofs, device):
+def _batch_bytes(proofs):
+    """(the members' bytes, back to back; offsets [batch + 1]; the members)"""
     datas = [p.to_bytes() if hasattr(p, "to_bytes") else bytes(p) for p in proofs]
     offsets = np.zeros(len(datas) + 1, dtype=np.uintp)
     offsets[1:] = np.cumsum([len(d) for d in datas], dtype=np.uint64)
-    buf = np.frombuffer(b"".join(datas) or b"\0", dtype=np.uint8)
+    return np.frombuffer(b"".join(datas) or b"\0", dtype=np.uint8), offsets, datas
+
+
+def _verify_batch(lib, handle, proofs, device, compressed=False):
+    buf, offsets, datas = _batch_bytes(proofs)
     reports = (_VerifyReport * max(len(datas), 1))()
-    fn = lib.p2gpu_verify_batch if device else lib.p2gpu_verify_batch_host
+    if compressed:
+        fn = lib.p2gpu_verify_batch_compressed if device else lib.p2gpu_verify_batch_compressed_host
+    else:
+        fn = lib.p2gpu_verify_batch if device else lib.p2gpu_verify_batch_host
     rc = fn(handle, buf.ctypes.data, offsets.ctypes.data, len(datas), ctypes.byref(reports))
     if rc not in (0, -9):
         _check(rc)
@@ -946,6 +969,26 @@ def _verify_batch(lib, handle, proofs, device):
         _check(lib.p2gpu_verify_reason(ctypes.byref(r), text, len(text)))
         out.append(VerifyReport(r, text.value.decode(errors="replace")))
     return out
+
+
+def _decompress_batch(lib, handle, proofs):
+    """``p2gpu_proof_decompress_batch``: per member its ProofWithPublicInputs, or the P2GpuError the lone ``decompress`` raises."""
+    buf, offsets, datas = _batch_bytes(proofs)
+    want = int(lib.p2gpu_proof_size_bound(handle))
+    out = np.zeros((max(len(datas), 1), want), dtype=np.uint8)
+    status = np.zeros(max(len(datas), 1), dtype=np.int32)
+    _check(lib.p2gpu_proof_decompress_batch(handle, buf.ctypes.data, offsets.ctypes.data, len(datas), out.ctypes.data, status.ctypes.data))
+    res = []
+    for i, data in enumerate(datas):
+        if status[i] == 0:
+            res.append(ProofWithPublicInputs(out[i].tobytes()))
+            continue
+        try:  # (the words of that member's error: the host's lone call says them)
+            _convert(lib.p2gpu_proof_decompress, handle, data)
+            res.append(P2GpuError(int(status[i]), "malformed proof"))
+        except P2GpuError as e:
+            res.append(e)
+    return res
 
 
 def _convert(fn, handle, data):
@@ -1049,6 +1092,17 @@ class VerifierCircuitData(_ProofFormats):
         same checks in a plain loop on this thread.  An invalid proof raises nothing; P2GpuError is for argument and device
         errors (without a GPU, device=True raises: there is no silent fall-back)."""
         return _verify_batch(self._lib, self._h, proofs, device)
+
+    def verify_batch_compressed(self, proofs, device=True):
+        """``verify_batch`` for compressed proofs (the on-disk format): device=True: ``p2gpu_verify_batch_compressed``, the
+        decompression on the device too; device=False: ``p2gpu_verify_batch_compressed_host``, the same core in a plain loop on
+        this thread.  The verdict of each proof is ``verify_compressed``'s."""
+        return _verify_batch(self._lib, self._h, proofs, device, compressed=True)
+
+    def decompress_batch(self, proofs):
+        """``p2gpu_proof_decompress_batch``: the device's decompression of each compressed proof, read back -- per member a
+        :class:`ProofWithPublicInputs` with the bytes of ``decompress``, or the :class:`P2GpuError` ``decompress`` raises."""
+        return _decompress_batch(self._lib, self._h, proofs)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

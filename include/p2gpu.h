@@ -420,8 +420,8 @@ int p2gpu_verify(const p2gpu_circuit *c, const uint8_t *proof, size_t len);
  *   reason  P2GPU_VR_*: the check that failed (0: none); there is one per rejection of p2gpu_verify
  *   query   the query the reason names, index: the initial oracle or the fold step it names; UINT32_MAX where it names none.
  *           For P2GPU_VR_LENGTH the two hold the length given and the length the circuit fixes.
- * proofs: host bytes; proof b is proofs[offsets[b] .. offsets[b + 1]) (uncompressed, as p2gpu_prove writes it: decompress
- * the on-disk format first); reports: host, [batch], complete whatever the return value is.
+ * proofs: host bytes; proof b is proofs[offsets[b] .. offsets[b + 1]) (uncompressed, as p2gpu_prove writes it: for the
+ * on-disk format there is p2gpu_verify_batch_compressed below); reports: host, [batch], complete whatever the return value is.
  * Returns P2GPU_OK when every proof is valid and P2GPU_E_VERIFY when one is not: p2gpu_last_error then words the lowest
  * failing proof exactly as p2gpu_verify would, behind "proof <b> of the batch: " when batch > 1.  Proofs of a batch do not
  * affect each other.  A proof whose length is not the circuit's is answered on the host (truncated or non-canonical header,
@@ -463,6 +463,47 @@ int p2gpu_verify_batch(const p2gpu_circuit *c, const uint8_t *proofs, const size
 int p2gpu_verify_batch_host(const p2gpu_circuit *c, const uint8_t *proofs, const size_t *offsets /* [batch + 1] */, size_t batch,
                             p2gpu_verify_report *reports);
 int p2gpu_verify_reason(const p2gpu_verify_report *r, char *out, size_t cap);
+
+/* ---- a batch of compressed proofs of one circuit (the on-disk format, see p2gpu_proof_compress below) ----
+ * p2gpu_verify_batch_compressed is p2gpu_verify_batch for the bytes `plonky2-backend prove` writes: the decompression runs on
+ * the device too (csrc/decompresscore.hpp as kernels, csrc/decompressdev.hip) -- one wave per proof scatters head, tail and
+ * leaves, one lane per proof replays the transcript once, one lane per (proof, query) infers the dropped evaluation of every
+ * fold step, one wave per (proof, tree) rebuilds the Merkle paths layer by layer -- and the uncompressed bytes exist only in
+ * device memory, where the query kernel of p2gpu_verify_batch then reads them.
+ * The verdict of proof b is p2gpu_verify_compressed's on that byte string: the first failure in its order, the reject sites of
+ * the decompression first (P2GPU_VR_C_*, one per site; query and index are UINT32_MAX), then p2gpu_verify's (P2GPU_VR_* above).
+ * p2gpu_verify_reason writes, for a P2GPU_VR_C_* code, the text behind "malformed proof: " in p2gpu_verify_compressed's message.
+ * cproofs: host bytes; proof b is cproofs[offsets[b] .. offsets[b + 1]); reports: host, [batch], complete whatever the return
+ * value is.  Returns P2GPU_OK when every proof is valid and P2GPU_E_VERIFY when one is not: p2gpu_last_error then words the lowest
+ * failing proof exactly as p2gpu_verify_compressed would, behind "proof <b> of the batch: " when batch > 1.
+ * The host only walks the container (lengths and indices: no hash, no field arithmetic) and uploads each proof at its own
+ * length with a table of offsets.  A proof the walk cannot get through -- it runs out of bytes, a path is longer than its tree,
+ * a stored index is >= the size of the domain, bytes trail -- is answered on the host by p2gpu_verify_compressed and never
+ * uploaded.  Handles, P2GPU_E_ARG (before any device call), P2GPU_E_DEVICE (no HIP device: there is no host fallback), scratch
+ * and the "profile" knob: as for p2gpu_verify_batch.
+ * p2gpu_verify_batch_compressed_host runs the same core in a plain loop on the calling thread and touches no device: the core's
+ * test bed and its sanitised build, not a fallback.
+ * p2gpu_proof_decompress_batch runs the device stages up to the rebuilt bytes and reads them back: out is host memory,
+ * [batch][p2gpu_proof_size_bound bytes]; status[b] is what p2gpu_proof_decompress returns for proof b, and where it is P2GPU_OK
+ * the bytes are that call's; the bytes of every other proof are zero.  It does not judge a proof.  Returns P2GPU_OK when the
+ * call itself went through, whatever the statuses are. */
+#define P2GPU_VR_C_ARITY 16        /* bad reduction arity in circuit */
+#define P2GPU_VR_C_HEADER 17       /* caps / openings */
+#define P2GPU_VR_C_INDICES 18      /* query indices */
+#define P2GPU_VR_C_INIT_ENTRY 19   /* initial tree entry */
+#define P2GPU_VR_C_STEP_ENTRY 20   /* fold step entry */
+#define P2GPU_VR_C_LENGTH 21       /* final polynomial / length */
+#define P2GPU_VR_C_TAIL 22         /* final polynomial / public inputs */
+#define P2GPU_VR_C_INDEX_CHECK 23  /* query indices differ from the transcript's */
+#define P2GPU_VR_C_INIT_PATH 24    /* compressed Merkle path (initial tree) */
+#define P2GPU_VR_C_STEP_PATH 25    /* compressed Merkle path (fold step) */
+#define P2GPU_VR_C_FOLD_CHAIN 26   /* fold chain (unreachable: an equal leaf at one step implies equal leaves after) */
+int p2gpu_verify_batch_compressed(const p2gpu_circuit *c, const uint8_t *cproofs, const size_t *offsets /* [batch + 1] */, size_t batch,
+                                  p2gpu_verify_report *reports);
+int p2gpu_verify_batch_compressed_host(const p2gpu_circuit *c, const uint8_t *cproofs, const size_t *offsets /* [batch + 1] */, size_t batch,
+                                       p2gpu_verify_report *reports);
+int p2gpu_proof_decompress_batch(const p2gpu_circuit *c, const uint8_t *cproofs, const size_t *offsets /* [batch + 1] */, size_t batch,
+                                 uint8_t *out /* host, [batch][proof length of the circuit] */, int32_t *status /* [batch] */);
 /* The verifier's share of a circuit -- header, gate table, constants_sigmas cap, circuit digest, k_is
  * (the blob prefix up to the constants table, flags 0b11) -- like the VK file of
  * actions/write_vk_action.rs:65-81.  out == NULL: only report the size in *len. */
