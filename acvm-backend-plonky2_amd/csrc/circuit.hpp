@@ -187,6 +187,8 @@ struct CircuitState {
   uint64_t pow_hint = UINT64_MAX;
   int profile = 0;
   int self_check = 1;
+  uint32_t prove_batch_slab = 0;     // knob "prove_batch_slab": proofs per slab of p2gpu_prove_batch_dev (0: from the byte budget)
+  void *prove_batch = nullptr;       // the slab buffers of p2gpu_prove_batch_dev (provebatch.hip), made by the first call
   int blocking_sync = 0;             // knob: sleep (blocking event) instead of spinning at the transcript sync points
   hipEvent_t sync_event = nullptr;
   std::map<std::string, KernelStat> kstats;

@@ -63,6 +63,7 @@ std::vector<int> g_peer_access;  // [a * n + b]: see p2gpu_peer_access
 std::vector<int> g_devices;  // p2gpu_init's list; more than one entry: circuit handles are device groups
 
 void circuit_release(p2gpu_circuit *c) {
+  prove_batch_release(c);
   c->tw_fwd.release(); c->tw_inv.release(); c->scale.release(); c->inv_scale.release(); c->d_kis.release();
   c->d_sigmas.release(); c->fri_scale.release(); c->d_gates.release(); c->qconst.release(); c->l0_lde.release();
   c->d_row_gate.release(); c->d_gconsts.release(); c->d_prc.release(); c->d_prc_hash.release();
@@ -766,6 +767,7 @@ int p2gpu_circuit_set(p2gpu_circuit *c, const char *key, uint64_t value) try {
   else if (k == "shard_zs") c->shard_zs = (int)value;
   else if (k == "half_gates") c->half_gates = (int)value;
   else if (k == "blocking_sync") c->blocking_sync = (int)value;
+  else if (k == "prove_batch_slab") c->prove_batch_slab = (uint32_t)std::min<uint64_t>(value, UINT32_MAX);
   else if (k == "virtual_columns") {
     c->virtual_columns = (int)value;
     // a clean mark set while the knob was on vouches for the coefficients only (the LDE was never written): forget them

@@ -80,6 +80,9 @@ struct ProfGuard {
 void flush_kstats(p2gpu_circuit *c);                 // read the pending per-launch event pairs into c->kstats
 int prove_impl(p2gpu_circuit *c, const gl_t *wires_dev, const uint64_t *pis, uint32_t n_pi, uint8_t *proof_out, size_t *proof_len,
                p2gpu_timings *tm, double h2d_ms);
+// ---- provebatch.hip ----
+// frees the slab buffers p2gpu_prove_batch_dev left on the handle (none: nothing to do)
+void prove_batch_release(p2gpu_circuit *c);
 // ---- commit.hip ----
 int pin_exhausted();
 const gl_t *hprc(const p2gpu_circuit *c);

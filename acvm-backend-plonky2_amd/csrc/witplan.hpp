@@ -28,10 +28,11 @@ struct p2gpu_witness_plan {
   size_t cap = 0;
   p2::DBuf<p2::gl_t> val, seed_vals;
   p2::DBuf<unsigned long long> err;
+  p2::DBuf<p2::gl_t> batch_wires;  // [batch][W][n]: the matrices of p2gpu_prove_seeds_batch, grown to the largest batch seen
   uint64_t *pin = nullptr;  // page-locked: [n_seeds][B] staging of the seed values, then the B contradiction words
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   void release_values() {
-    val.release(); seed_vals.release(); err.release();
+    val.release(); seed_vals.release(); err.release(); batch_wires.release();
     if (pin) (void)hipHostFree(pin);
     pin = nullptr;
     cap = 0;

@@ -183,6 +183,10 @@ def load_library():
     lib.p2gpu_generate_witness.argtypes = [vp, vp, vp]
     lib.p2gpu_generate_witness_batch.argtypes = [vp, vp, sz, vp, vp, vp]
     lib.p2gpu_prove_seeds.argtypes = [vp, vp, vp, ctypes.c_uint32, u8p, ctypes.POINTER(sz), ctypes.POINTER(_Timings)]
+    lib.p2gpu_prove_batch_dev.argtypes = [vp, vp, sz, vp, ctypes.c_uint32, u8p, vp]
+    lib.p2gpu_prove_seeds_batch.argtypes = [vp, vp, sz, vp, ctypes.c_uint32, u8p, vp, vp]
+    lib.p2gpu_prove_batch_max_degree_bits.restype = ctypes.c_uint32
+    lib.p2gpu_prove_batch_info.argtypes = [vp, vp]
     lib.p2gpu_check_witness_dev.argtypes = [vp, vp, sz, vp, ctypes.c_uint32, vp, vp, vp]
     lib.p2gpu_check_witness.argtypes = [vp, vp, vp, ctypes.c_uint32, vp, vp, vp]
     lib.p2gpu_check_seeds.argtypes = [vp, vp, vp, ctypes.c_uint32, vp, vp, vp]
@@ -513,6 +517,56 @@ class CircuitData:
         _check(rc)
         t = {f: getattr(tm, f) for f, _ in _Timings._fields_}
         return ProofWithPublicInputs(out[:plen.value].tobytes(), t)
+
+    # the words of the lone call for the codes a member of a batch can end with
+    _MEMBER_WORDS = {-5: "witness does not satisfy the circuit: the plonk identity fails at zeta (vanishing != Z_H * quotient)",
+                     -4: "Opening point is in the subgroup."}
+
+    def _batch_pis(self, batch, public_inputs):
+        pis = [()] * batch if public_inputs is None else [list(p) for p in public_inputs]
+        if len(pis) != batch:
+            raise P2GpuError(-7, f"{batch} lists of public inputs expected, {len(pis)} given")
+        n_pi = len(pis[0])
+        if any(len(p) != n_pi for p in pis):
+            raise P2GpuError(-7, "every member needs the same number of public inputs")
+        return _u64(np.array(pis, dtype=np.uint64).reshape(batch, n_pi)), n_pi
+
+    def _batch_results(self, rc, out, status):
+        """Per member the proof or the error the lone call raises; a code that belongs to no member raises here."""
+        if rc not in (0, -4, -5) or (rc and not any(int(s) == rc for s in status)):
+            _check(rc)
+        res = []
+        for b, st in enumerate(status):
+            st = int(st)
+            res.append(ProofWithPublicInputs(out[b].tobytes()) if st == 0 else P2GpuError(st, self._MEMBER_WORDS.get(st, "error %d" % st)))
+        return res
+
+    def prove_batch(self, wires, public_inputs=None):
+        """``p2gpu_prove_batch_dev``: the proofs of B witnesses of this (small) circuit in one call.  `wires`: an int64 tensor
+        [B][num_wires][degree] on the circuit's GPU (the layout of ``WitnessPlan.generate_batch``), only read;
+        `public_inputs`: one list per member.  Returns per member the ``ProofWithPublicInputs`` -- the bytes ``prove`` gives for
+        that matrix -- or the ``P2GpuError`` the lone call raises."""
+        import torch
+
+        if not (hasattr(wires, "data_ptr") and getattr(wires, "is_cuda", False)) or wires.dim() != 3 or not wires.is_contiguous() \
+                or wires.element_size() != 8 or wires[0].numel() != self.num_wires * self.degree:
+            raise P2GpuError(-7, "wires tensor must be contiguous int64/uint64 [batch][num_wires][degree] on the GPU")
+        if wires.device.index != self.device_index():
+            raise P2GpuError(-7, f"wires tensor lives on cuda:{wires.device.index}, the circuit on cuda:{self.device_index()}")
+        batch = wires.shape[0]
+        pis, n_pi = self._batch_pis(batch, public_inputs)
+        out = np.zeros((batch, self._bound), dtype=np.uint8)
+        status = np.zeros(batch, dtype=np.intc)
+        torch.cuda.current_stream(wires.device).synchronize()
+        rc = self._lib.p2gpu_prove_batch_dev(self._h, ctypes.c_void_p(wires.data_ptr()), batch, pis.ctypes.data, n_pi, out.ctypes.data,
+                                             status.ctypes.data)
+        return self._batch_results(rc, out, status)
+
+    def prove_batch_info(self):
+        """``p2gpu_prove_batch_info``: launches of the last slab, proofs in it, bytes of the slab buffers, the byte budget."""
+        v = np.zeros(4, dtype=np.uint64)
+        _check(self._lib.p2gpu_prove_batch_info(self._h, v.ctypes.data))
+        return {"launches": int(v[0]), "slab": int(v[1]), "arena_bytes": int(v[2]), "budget_bytes": int(v[3])}
 
     def plonk_stages(self, wires, pi_hash, betas, gammas, alphas, zp_in=None):
         """Prover phases 1-3 on caller-chosen challenges (``p2gpu_plonk_stages``, a test bed: no proof calls it).  Returns a
@@ -879,21 +933,45 @@ class WitnessPlan:
             _check(rc)
         return out, [int(s) for s in status], [(int(r), int(c)) if s else None for s, (r, c) in zip(status, bad)]
 
-    def prove_batch(self, values_list, public_inputs=None, verify=False):
+    def _prove_batch_one_call(self, values_list, public_inputs):
+        """``p2gpu_prove_seeds_batch``: (per member the proof or the error, the walk's cell per member or None)."""
+        rows = [self._values(v) for v in values_list]
+        if not rows:
+            raise P2GpuError(-7, "prove_batch needs at least one set of values")
+        v = np.ascontiguousarray(np.stack(rows))
+        cd = self._cd
+        pis, n_pi = cd._batch_pis(len(rows), public_inputs)
+        out = np.zeros((len(rows), cd._bound), dtype=np.uint8)
+        status = np.zeros(len(rows), dtype=np.intc)
+        bad = np.full((len(rows), 2), 0xFFFFFFFF, dtype=np.uint32)
+        rc = self._lib.p2gpu_prove_seeds_batch(self._h, v.ctypes.data if v.size else None, len(rows), pis.ctypes.data, n_pi, out.ctypes.data,
+                                               status.ctypes.data, bad.ctypes.data)
+        res = cd._batch_results(rc, out, status)
+        cells = [(int(r), int(c)) if int(r) != 0xFFFFFFFF else None for r, c in bad]
+        for b, cell in enumerate(cells):
+            if cell is not None:
+                res[b] = P2GpuError(int(status[b]), "unsatisfiable: witness %d of the batch contradicts itself at cell (row %d, column %d)" % (b, *cell))
+        return res, cells
+
+    def prove_batch(self, values_list, public_inputs=None, verify=False, one_call=False):
         """`generate_batch`, then the resident proof (``CircuitData.prove`` on the member's matrix) of every good member, in
         order.  `public_inputs`: one list per member.  Returns per member the ``ProofWithPublicInputs``, or the ``P2GpuError``
         a lone ``prove`` would have raised.  verify=True: also one ``CircuitData.verify_batch`` over the proofs just made;
-        returns (that list, the :class:`VerifyReport` per member, None where there is no proof)."""
-        wires, status, bad = self.generate_batch(values_list)
-        out = []
-        for b, st in enumerate(status):
-            if st:
-                out.append(P2GpuError(st, "unsatisfiable: witness %d of the batch contradicts itself at cell (row %d, column %d)" % (b, *bad[b])))
-                continue
-            try:
-                out.append(self._cd.prove(wires[b], public_inputs[b] if public_inputs is not None else ()))
-            except P2GpuError as e:
-                out.append(e)
+        returns (that list, the :class:`VerifyReport` per member, None where there is no proof).  one_call=True: the walk and
+        every proof in one ``p2gpu_prove_seeds_batch`` (small circuits: ``CircuitData.prove_batch``) -- the same proofs."""
+        if one_call:
+            out, _ = self._prove_batch_one_call(values_list, public_inputs)
+        else:
+            wires, status, bad = self.generate_batch(values_list)
+            out = []
+            for b, st in enumerate(status):
+                if st:
+                    out.append(P2GpuError(st, "unsatisfiable: witness %d of the batch contradicts itself at cell (row %d, column %d)" % (b, *bad[b])))
+                    continue
+                try:
+                    out.append(self._cd.prove(wires[b], public_inputs[b] if public_inputs is not None else ()))
+                except P2GpuError as e:
+                    out.append(e)
         if not verify:
             return out
         made = [i for i, o in enumerate(out) if not isinstance(o, P2GpuError)]

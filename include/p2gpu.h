@@ -30,6 +30,10 @@
  *   p2gpu_generate_witness_batch
  *                          <- the same for many value sets of one circuit at once (the reference has no counterpart: it
  *                             calls `prove` once per witness)
+ *   p2gpu_prove_batch_dev / p2gpu_prove_seeds_batch
+ *                          <- `circuit_data.prove(witnesses)` for many witnesses of one small circuit (degree_bits <=
+ *                             P2GPU_PROVE_BATCH_MAX_DEGREE_BITS) in one call: the reference calls `prove` once per witness and so
+ *                             does p2gpu_prove_dev; here every launch covers a slab of proofs and the transcripts run on the GPU
  *   p2gpu_check_witness / p2gpu_check_witness_dev / p2gpu_check_seeds
  *                          <- the panic of plonky2's witness generator that names a partition (iop/generator.rs), for a matrix
  *                             that arrives complete: which gate row and which copy constraint a witness breaks
@@ -153,6 +157,43 @@ int p2gpu_prove(p2gpu_circuit *c, const uint64_t *wires, const uint64_t *public_
  * circuit's device; it is only read. */
 int p2gpu_prove_dev(p2gpu_circuit *c, const uint64_t *wires_dev, const uint64_t *public_inputs, uint32_t n_pi,
                     uint8_t *proof_out, size_t *proof_len, p2gpu_timings *opt_timings);
+/* ---- a batch of witnesses of one small circuit, proved in one call ----
+ * A second, plain prover (csrc/provebatch.hip, csrc/provebatchcore.hpp) whose every launch covers a slab of proofs: each
+ * proof's challenges, zeta, FRI betas, proof-of-work witness and query indices stay in device memory, the Fiat-Shamir transcript
+ * runs on the device with one lane per proof, and the host synchronises once per slab -- a lone proof costs eleven round trips
+ * and ~55 launches whatever its size, which is all a circuit of 2^2 .. 2^12 gates costs.  The number of launches per slab does
+ * not depend on the batch (p2gpu_prove_batch_info).
+ *   wires_dev      device, [batch][num_wires][n]: the layout of p2gpu_generate_witness_batch; only read
+ *   public_inputs  host, [batch][n_pi]
+ *   proofs_out     host, [batch][p2gpu_proof_size_bound(c)]
+ *   status         host, [batch]: the code p2gpu_prove_dev returns for that matrix and those public inputs on this handle --
+ *                  P2GPU_OK, P2GPU_E_UNSATISFIED (knob "self_check" at its default 1: the verifier's identity at zeta, checked per
+ *                  proof on the device; with 0 the proof is emitted anyway, like the lone call) or P2GPU_E_OPENING_IN_SUBGROUP
+ * Where status[b] is P2GPU_OK, proofs_out[b] holds exactly the bytes p2gpu_prove_dev writes, the minimal proof-of-work witness
+ * included; the bytes of a failing member are zero.  Members do not affect each other.  Returns P2GPU_OK when every member is
+ * good, otherwise the code of the lowest failing member, p2gpu_last_error reading "witness <b> of the batch: " and the lone
+ * call's words.  P2GPU_E_ARG, decided before any device call and worded in p2gpu_last_error: a null handle, matrix, output or
+ * status; batch == 0; n_pi different from the circuit's, or a public input >= p; a verifier-only handle; a device group or a
+ * handle with sharding configured; degree_bits > P2GPU_PROVE_BATCH_MAX_DEGREE_BITS (a column of 2^12 elements is transformed by
+ * one workgroup in LDS; above that the tuned lone path takes over: p2gpu_prove_dev).
+ * MEASURED (profiles/prove_batch.md, one MI355X, 256 witnesses of the `arith` mix): 16x the lone-call loop and 4.5x four proofs in
+ * flight at 2^3 gates, 10x and 3.0x at 2^10; at degree_bits 12 it still beats the loop (2.2x) but loses to four lone proofs in
+ * flight on four handles (0.75x).  Do not use it above degree_bits 10 where four handles can be kept busy (11 is not measured).
+ * Both hashers.  The "pow_hint" knob is not consulted: the batch always grinds for the minimum.  "half_gates", "zero_columns"
+ * and "virtual_columns" have nothing to act on here.  The call works in slabs of proofs: as many as a byte budget
+ * (SLAB_BUDGET_BYTES in csrc/provebatch.hip) and three quarters of the free device memory hold, or the knob "prove_batch_slab"
+ * (proofs per slab, 0 = automatic).  The slab's buffers stay on the handle, grow to the largest slab seen and are freed by
+ * p2gpu_circuit_destroy; a handle that never makes the call allocates nothing.  One call per handle at a time, as for every
+ * entry point; other handles may prove beside it. */
+#define P2GPU_PROVE_BATCH_MAX_DEGREE_BITS 12
+int p2gpu_prove_batch_dev(p2gpu_circuit *c, const uint64_t *wires_dev, size_t batch, const uint64_t *public_inputs, uint32_t n_pi,
+                          uint8_t *proofs_out, int *status);
+/* the limit the library enforces (= P2GPU_PROVE_BATCH_MAX_DEGREE_BITS of the header it was built from) */
+uint32_t p2gpu_prove_batch_max_degree_bits(void);
+/* out: launches of the last slab, proofs in it, bytes of the slab buffers the handle holds, the byte budget.  Zeros before the
+ * first call (and for a verifier-only handle). */
+int p2gpu_prove_batch_info(const p2gpu_circuit *c, uint64_t out[4]);
+
 /* Row-local witness generators on the GPU (the reference's SimpleGenerator
  * impls: arithmetic_u32.rs:376-426, add_many_u32.rs:329-378, subtraction_u32.rs:298-343,
  * range_check_u32.rs:198-220, comparison.rs:439-537 + the stock gates'): given a device wire
@@ -320,6 +361,14 @@ int p2gpu_generate_witness_batch(p2gpu_witness_plan *p, const uint64_t *seed_val
  * holds the time the witness took. */
 int p2gpu_prove_seeds(p2gpu_witness_plan *p, const uint64_t *seed_values, const uint64_t *public_inputs, uint32_t n_pi,
                       uint8_t *proof_out, size_t *proof_len, p2gpu_timings *opt_timings);
+/* p2gpu_generate_witness_batch into a buffer the plan owns (it grows with the largest batch seen, like the plan's other batch
+ * buffers), then p2gpu_prove_batch_dev on the members the level walk accepted: the same proofs.  seed_values: host,
+ * [batch][n_seeds]; the other arguments are p2gpu_prove_batch_dev's.  A member the walk refuses keeps the walk's status and, in
+ * bad_cells ([batch][2], may be NULL), its cell; its proof bytes are zero.  The return value and p2gpu_last_error speak for the
+ * lowest failing member, whichever stage refused it. */
+int p2gpu_prove_seeds_batch(p2gpu_witness_plan *p, const uint64_t *seed_values /* host, [batch][n_seeds] */, size_t batch,
+                            const uint64_t *public_inputs, uint32_t n_pi, uint8_t *proofs_out, int *status,
+                            uint32_t *bad_cells /* [batch][2], may be NULL */);
 
 /* ---- why a witness is wrong: the gate rows and copy constraints it breaks, found on the GPU ----
  * The prover's self-check answers P2GPU_E_UNSATISFIED after the commitments and names nothing; these entry points evaluate the
@@ -552,7 +601,8 @@ int p2gpu_verify_compressed(const p2gpu_circuit *c, const uint8_t *cproof, size_
  * "shard_zs" (0/1, default 0; sharded proofs only: the chunk quotients of the permutation argument are computed for n / ranks rows
  * per rank and all-gathered in place -- SURVEY 8(e) step 5), "shard_reduce" (0/1, default 0; sharded proofs only: every rank
  * batch-reduces only its block of the opened polynomials for FRI, the partial sums are all-gathered and added -- step 8); same
- * rules: no proof byte depends on them, every rank sets them alike */
+ * rules: no proof byte depends on them, every rank sets them alike; "prove_batch_slab" (default 0: p2gpu_prove_batch_dev sizes its
+ * slabs from its byte budget and the free memory; otherwise proofs per slab; no proof byte depends on it) */
 int p2gpu_circuit_set(p2gpu_circuit *c, const char *key, uint64_t value);
 /* statistics accumulated while "profile" = 1, one entry per kernel symbol:
  * names[64*i] (NUL-terminated), total milliseconds, total algorithmic bytes,
